@@ -18,9 +18,22 @@ under "strong"; --strong swaps the two.  After the timed steps each mesh is gath
 (distributed.gather_mesh, timed as "gather_ms") and checked against the oracle's summary of the
 same workload.
 
-Prints ONE JSON line (rank 0).  Extra fields: per-kernel times from HIP events on the launch
-stream, the HBM roofline of the eval+MC kernel sequence (SURVEY.md 8d's algorithmic bytes), and
-the CPU baseline (the oracle restatement, single thread, on a bounded sample of the same workload).
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: it sets up, warms
+up, times --steps steps, writes the last step's mesh if --dump-outputs is given, and prints the line
+(metric, value, unit, higher_is_better, dtype, ms_per_step and the workload's description).
+
+--full adds everything else the benchmark measures or checks, in runs of their own after the
+headline: per-kernel times from HIP events on the launch stream, the HBM roofline of the eval+MC
+kernel sequence (SURVEY.md 8d's algorithmic bytes), the other sizes and scenes, concurrent builds,
+config 5, the OB02 legs, first-call and end-to-end latencies, the N > 1 side leg with its gathered
+meshes checked against the oracle's summaries, and the CPU baseline (the oracle restatement, single
+thread, on a bounded sample of the same workload).  The --skip-* switches choose among those legs.
+
+--dump-outputs DIR writes what the timed path computed in its last timed step -- the mesh a caller
+of that path receives -- as DIR/verts.npy (float32 [V, 3]), DIR/faces.npy (float64 [F, 3], the
+vertex ids) and DIR/counts.npy (float64 [V, F]); past 64 MB in all, a fixed seeded sample of the
+rows.  The workload is seeded, so two builds of the library run with the same arguments can be
+compared array for array.
 """
 import argparse
 import json
@@ -251,6 +264,31 @@ def headline_parity(name, v, f):
             "max_abs_v_diff": diff, "v_diff_over": over}
 
 
+DUMP_BUDGET = 64 << 20      # --dump-outputs writes at most this many bytes in all
+DUMP_SEED = 20251015
+
+
+def dump_outputs(dirname, v, f):
+    """The mesh of the last timed step as DIR/verts.npy (float32), DIR/faces.npy and DIR/counts.npy
+    (float64: the ids and counts are exact).  Arrays that would pass DUMP_BUDGET together are cut to
+    a fixed seeded sample of their rows (sorted, the same rows for the same counts)."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {"verts": np.ascontiguousarray(v, dtype=np.float32), "faces": np.ascontiguousarray(f, dtype=np.float64)}
+    counts = np.array([len(v), len(f)], dtype=np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET - 4096:
+        keep = (DUMP_BUDGET - 4096) * 0.95 / total
+        rng = np.random.default_rng(DUMP_SEED)
+        for k in sorted(arrays):
+            a = arrays[k]
+            rows = np.sort(rng.choice(len(a), size=max(1, int(len(a) * keep)), replace=False))
+            arrays[k] = np.ascontiguousarray(a[rows])
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+    np.save(os.path.join(dirname, "counts.npy"), counts)
+    return {k: list(a.shape) for k, a in arrays.items()}
+
+
 def copy_attainable(dev, nbytes=1 << 30, reps=10):
     """Measured device-to-device copy rate (GB/s, read + write bytes): the attainable HBM figure
     SURVEY.md 8d asks to report beside the 8 TB/s peak."""
@@ -294,7 +332,14 @@ def main():
                     help="tree modules with the matrices baked in: 0 never, 1 every object, 2 hot objects (library default)")
     ap.add_argument("--graph", action="store_true",
                     help="N = 1: replay the step as a hipGraph (an A/B switch; direct launches are the default)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other leg and check (other sizes and scenes, per-kernel and "
+                         "roofline figures, concurrent builds, config 5, OB02, latencies, oracle parity, CPU baselines); "
+                         "the --skip-* switches choose among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the mesh of the headline's last timed step as DIR/verts.npy, DIR/faces.npy, DIR/counts.npy")
     args = ap.parse_args()
+    full = args.full
 
     import torch
     import torch.distributed as dist
@@ -324,7 +369,7 @@ def main():
     stream = torch.cuda.current_stream(dev)
     sp = stream.cuda_stream
 
-    def run(R, steps, warmup, scene=None, gather=False):
+    def run(R, steps, warmup, scene=None, gather=False, dump=None):
         shape, mc = scene if scene is not None else scenes.config4(R)
         # N > 1: balanced Z-slab cuts from one interval pass of the whole grid, computed by every
         # rank alike (no exchange; implisolid_slab_balance), unless --equal-slabs
@@ -337,7 +382,7 @@ def main():
         slab = I.Slab(shape, mc, rank, world, cuts=cuts)
         gath = torch.zeros(world, 4, dtype=torch.int32, device=dev)
         totals = D.counts_tensor(slab, dev) if backend == "nccl" else None
-        ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(steps)]
+        ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(min(steps, 10) if full else 0)]
 
         def step(e=None):
             if e: e[0].record(stream)
@@ -439,6 +484,30 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dist.all_reduce(tot)
         el = float(t.item())
+        dumped = None
+        if dump:
+            # the last timed step's mesh, as a caller receives it: read from the engine's buffers
+            # (N > 1: gathered to rank 0 after one more step, which recomputes the same mesh with
+            # the gathered counts in place)
+            if world > 1:
+                step()
+                torch.cuda.synchronize(dev)
+                dist.barrier()
+                res = D.gather_mesh(slab, gath, rank, world)
+            else:
+                res = slab.download(nv, nf, sp)
+            if rank == 0:
+                dumped = dump_outputs(dump, *res)
+        if not full:   # a plain run: the headline alone
+            info = dict(R=R, nv=int(tot[0]), nf=int(tot[1]), elapsed=el, shape=shape, graph=graph is not None,
+                        cuts=cuts, cut_s=t_cut, jit_module=slab.jit_module(), dumped=dumped)
+            if world > 1:
+                rt = torch.tensor([el], dtype=torch.float64, device=dev)
+                allt = [torch.zeros_like(rt) for _ in range(world)]
+                dist.all_gather(allt, rt)
+                info["rank_ms"] = [round(float(x.item()) / steps * 1e3, 4) for x in allt]
+            slab.close()
+            return info
         n_phase = min(steps, 10)   # phase split (eval / count + scan / emit): extra steps with events
         for k in range(n_phase):
             if graph is not None:
@@ -482,7 +551,7 @@ def main():
             repeat_ms[name] = e0.elapsed_time(e1) / 20
         info = dict(R=R, nv=int(tot[0]), nf=int(tot[1]), elapsed=el, kernels_ms=kms, kernel_ms=kernel_ms, each_ms=each_ms, repeat_ms=repeat_ms,
                     shape=shape, slab_layers=slab.cz1 - slab.cz_emit, depth=slab.depth, bricks=slab.brick_stats(),
-                    graph=graph is not None, cuts=cuts, cut_s=t_cut,
+                    graph=graph is not None, cuts=cuts, cut_s=t_cut, dumped=dumped,
                     fz=(slab.fz0, slab.fz1), jit=slab.used_jit(), jit_module=slab.jit_module(), stats=slab.stats())
         if world > 1:
             # every rank's own step time (the max over ranks is the headline's): the balance
@@ -519,7 +588,53 @@ def main():
         return r
     weak = world > 1 and not args.strong
     R_weak = int(round(args.resolution * world ** (1.0 / 3.0)))
-    main_run = leg("headline", lambda: run(R_weak if weak else args.resolution, args.steps, args.warmup, gather=True))
+    main_run = leg("headline", lambda: run(R_weak if weak else args.resolution, args.steps, args.warmup, gather=full,
+                                           dump=args.dump_outputs))
+    if not full:
+        # a plain run ends here: the result line of the headline alone
+        if rank == 0:
+            R = main_run["R"]
+            ms = main_run["elapsed"] / args.steps * 1e3
+            _, n_instr, depth = program_flops(main_run["shape"])
+            out = {
+                "metric": "Mvoxels/s (eval+MC) at 256^3 & 512^3",
+                "value": round(R ** 3 / (ms * 1e-3) / 1e6, 2),
+                "unit": "Mvoxels/s",
+                "n_gpus": world,
+                "steps": args.steps,
+                "warmup": args.warmup,
+                "ms_per_step": round(ms, 4),
+                "higher_is_better": True,
+                "scaling": "weak" if weak else "strong",
+                "vs_baseline": None,
+                "dtype": "f32",
+                "data": "synthetic",
+                "full": False,
+                "config": {
+                    "workload": "config4: seeded ~20-node MP5 CSG tree with twist/union/difference (scenes.config4, seed 20251015), box [-1,1]^3, "
+                                "R=%d, eval+MC, mesh resident in HBM%s" % (
+                                    R, (", weak scaling: R = %d N^(1/3), ~%d^3 voxels per rank" % (args.resolution, args.resolution))
+                                    if weak else (", strong scaling: the grid over %d balanced Z-slabs" % world) if world > 1 else ""),
+                    "resolution": R, "voxels": R ** 3, "samples": (R + 1) ** 3, "cells": (R + 2) ** 3,
+                    "verts": main_run["nv"], "faces": main_run["nf"], "program_instr": n_instr, "tree_depth": depth,
+                    "parallelism": "zslab%d" % world,
+                    "voxels_per_rank": R ** 3 // world,
+                },
+                "eval_kernel": {"shape": "jit", "baked": "jit (object's module, matrices as literals)"}.get(
+                    main_run["jit_module"], "interpreter"),
+                "launch": "hipGraph replay of the step" if main_run["graph"] else "direct launches",
+            }
+            if world > 1:
+                out["slabs"] = {"cuts": main_run["cuts"], "balanced": main_run["cuts"] is not None,
+                                "cut_probe_s": round(main_run["cut_s"], 4), "rank_ms": main_run.get("rank_ms")}
+            if main_run["dumped"] is not None:
+                out["dumped_outputs"] = main_run["dumped"]
+            out["wall_s"] = round(time.perf_counter() - T_START, 2)
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     side_run = None
     if world > 1:
         side_run = leg("side", lambda: run(args.resolution if weak else R_weak, args.steps, args.warmup, gather=True))
@@ -1059,6 +1174,7 @@ def main():
         "vs_baseline": None,
         "dtype": "f32",
         "data": "synthetic",
+        "full": True,
         "config": {
             "workload": "config4: seeded ~20-node MP5 CSG tree with twist/union/difference (scenes.config4, seed 20251015), box [-1,1]^3, "
                         "R=%d, eval+MC, mesh resident in HBM%s" % (
@@ -1124,6 +1240,8 @@ def main():
         for k in ("gather_ms", "parity"):
             if k in side_run:
                 out["strong" if weak else "weak"][k] = side_run[k]
+    if main_run["dumped"] is not None:
+        out["dumped_outputs"] = main_run["dumped"]
     if rdense:
         msd = rdense["elapsed"] / args.steps * 1e3
         out["value_union_scene"] = round(R ** 3 / (msd * 1e-3) / 1e6, 2)

@@ -1,5 +1,9 @@
+# kernel-trace stats of the bench's headline and per-kernel legs, then the same bench unprofiled
+# usage (from the repository root): tools/ab_fill.sh [output folder, default out]
 set -e
-cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-mkdir -p gpurun_out
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/ab -o run -- python bench.py --steps 20 --skip-256 --skip-config5 --skip-ob02 --no-cpu-baseline > gpurun_out/ab.json 2>gpurun_out/ab.err
-timeout -k 10 300 python bench.py --steps 50 --skip-256 --skip-config5 --skip-ob02 --no-cpu-baseline > gpurun_out/ab2.json 2>gpurun_out/ab2.err
+export TMPDIR=/tmp
+out=${1:-out}
+mkdir -p "$out"
+B="python bench.py --full --skip-256 --skip-config5 --skip-ob02 --no-cpu-baseline"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$out/ab" -o run -- $B --steps 20 > "$out/ab.json" 2>"$out/ab.err"
+timeout -k 10 300 $B --steps 50 > "$out/ab2.json" 2>"$out/ab2.err"

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of library variants (tools/build_variant.sh) on the config-4 bench: usage tools/ab_variants.sh v1 v2 ...
 set -e
-B="python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --skip-256 --skip-config5 --skip-ob02"
+B="python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --skip-256 --skip-config5 --skip-ob02"
 for rep in 1 2; do
   for v in main "$@"; do
     lib=""

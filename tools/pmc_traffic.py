@@ -4,7 +4,7 @@
     python tools/pmc_traffic.py --fetch D1 --write D2 [--cal-fetch D3 --cal-write D4] --R 512 \\
         > profiles/traffic_r01.json
 
-D1/D2: `bench.py --skip-256 --no-cpu-baseline` (default pruning) under `rocprofv3 --pmc FETCH_SIZE`
+D1/D2: `bench.py --full --skip-256 --no-cpu-baseline` (default pruning) under `rocprofv3 --pmc FETCH_SIZE`
 and `--pmc WRITE_SIZE`.  D3/D4: the same with `--prune 0`, whose dense kernels move a known byte
 count (k_eval_field stores exactly 4 B per stored sample, k_signs_from_field loads exactly that
 field): they calibrate the counters for this code's 4-byte-per-lane accesses, a width

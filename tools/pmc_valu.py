@@ -2,7 +2,7 @@
 """VALU utilisation and wave-state breakdown per kernel from one rocprofv3 SQ counter pass.
 
     rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU \\
-        SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_VALU -d D -o run -- python3 bench.py ...
+        SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_VALU -d D -o run -- python3 bench.py --full ...
     python tools/pmc_valu.py D > profiles/valu_<tag>.json
 
 SURVEY.md H6 asks for VALU utilisation beside the HBM fraction.  Per kernel (summed over its

@@ -11,7 +11,7 @@ out=gpurun_out/$tag
 mkdir -p "$out"
 root=$(pwd)
 export TMPDIR=/tmp
-B="bench.py --steps 10 --warmup 4 --no-cpu-baseline --skip-256 --skip-config5 --skip-ob02 --skip-concurrent"
+B="bench.py --full --steps 10 --warmup 4 --no-cpu-baseline --skip-256 --skip-config5 --skip-ob02 --skip-concurrent"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$root/$out/trace" -o run -- python3 $B > "$out/trace.log" 2>&1
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$root/$out/fetch" -o run -- python3 $B > "$out/fetch.log" 2>&1
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$root/$out/write" -o run -- python3 $B > "$out/write.log" 2>&1
@@ -24,5 +24,5 @@ cp "$out/trace/run_kernel_stats.csv" profiles/${tag}_kernel_stats.csv
 python3 tools/pmc_traffic.py --fetch "$out/fetch" --write "$out/write" --cal-fetch "$out/cfetch" --cal-write "$out/cwrite" \
     --R 512 --lib implisolid_amd/lib/libimplisolid_mi355x.so > "$out/traffic.json"
 cp "$out/traffic.json" profiles/traffic_$tag.json
-timeout -k 10 600 python3 bench.py > "$out/bench.log" 2>&1
+timeout -k 10 600 python3 bench.py --full > "$out/bench.log" 2>&1
 echo done

@@ -16,7 +16,7 @@ timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$root
 cp "$out/ob02/run_kernel_stats.csv" profiles/${tag}_ob02_kernel_stats.csv
 cp "$out/ob02_probe.log" profiles/${tag}_ob02_probe.log
 IMPLISOLID_DIST_BACKEND=gloo timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-    --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline \
+    --master-addr 127.0.0.1 --master-port 29611 bench.py --full --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline \
     --skip-config5 > "$out/bench_n2_gloo.log" 2> "$out/bench_n2_gloo.err"
 cp "$out/bench_n2_gloo.log" profiles/${tag}_n2_gloo_rehearsal.json
 echo done

@@ -24,9 +24,9 @@ for what in "$@"; do
       timeout -k 10 600 python3 -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread -k "${what#tests:}" \
           > "$out/tests_k.log" 2>&1 ;;
     bench)
-      timeout -k 10 600 python3 -u bench.py > "$out/bench.json" 2> "$out/bench.err" ;;
+      timeout -k 10 600 python3 -u bench.py --full > "$out/bench.json" 2> "$out/bench.err" ;;
     benchob)
-      timeout -k 10 600 python3 -u bench.py --steps 10 --skip-config5 --skip-concurrent --no-cpu-baseline --skip-256 \
+      timeout -k 10 600 python3 -u bench.py --full --steps 10 --skip-config5 --skip-concurrent --no-cpu-baseline --skip-256 \
           > "$out/bench_ob.json" 2> "$out/bench_ob.err" ;;
     ob02prof)
       timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$root/$out/ob02" -o run -- \

@@ -9,7 +9,7 @@ out=gpurun_out/$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
 root=$(pwd)
-B="python3 bench.py --steps 30 --warmup 5 --no-cpu-baseline --skip-256 --skip-config5 --skip-ob02 --skip-concurrent"
+B="python3 bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --skip-256 --skip-config5 --skip-ob02 --skip-concurrent"
 for rep in $(seq 1 "$rounds"); do
   for v in main "$@"; do
     lib=""; envs=""; name=$v

@@ -24,7 +24,7 @@ if [ "$part" = all ] || [ "$part" = b ]; then
       python3 tools/ob02_probe.py 5 > "$out/ob02_probe.log" 2>&1
   bash tools/r06_run.sh "$tag" slabtrace
   IMPLISOLID_DIST_BACKEND=gloo timeout -k 10 500 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-      --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline \
+      --master-addr 127.0.0.1 --master-port 29611 bench.py --full --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline \
       --skip-config5 > "$out/bench_n2_gloo.log" 2> "$out/bench_n2_gloo.err"
 fi
 echo done
