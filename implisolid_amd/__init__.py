@@ -40,7 +40,8 @@ ABI_SYMBOLS = [
     "implisolid_set_jit_max_modules", "implisolid_jit_modules",
     "implisolid_set_progress_callback", "implisolid_ob02_profile", "implisolid_last_build_stats",
     "implisolid_jit_compile_points", "implisolid_debug_libm", "implisolid_debug_cos", "implisolid_slab_stats_n",
-    "implisolid_slab_kernel_times_each", "implisolid_debug_fold",
+    "implisolid_slab_kernel_times_each", "implisolid_debug_fold", "implisolid_debug_intervals",
+    "implisolid_debug_eval_modes",
     "implisolid_ob02_create", "implisolid_ob02_destroy", "implisolid_ob02_load", "implisolid_ob02_resample",
     "implisolid_ob02_project", "implisolid_ob02_subdivide", "implisolid_ob02_counts", "implisolid_ob02_ranges",
     "implisolid_ob02_get_verts", "implisolid_ob02_set_verts", "implisolid_ob02_download",
@@ -95,6 +96,9 @@ def lib():
         "implisolid_debug_libm": ([c_int, fp, fp, ctypes.c_int64, fp], c_int),
         "implisolid_debug_cos": ([ctypes.POINTER(ctypes.c_double), ctypes.c_int64, ctypes.POINTER(ctypes.c_double)], c_int),
         "implisolid_debug_fold": ([fp, ctypes.c_int64, fp, ctypes.POINTER(ctypes.c_int64)], c_int),
+        "implisolid_debug_intervals": ([c_char_p, c_int, c_int, fp, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int64, fp,
+                                        ctypes.POINTER(ctypes.c_uint64)], c_int),
+        "implisolid_debug_eval_modes": ([c_char_p, c_int, fp, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int64, fp], c_int),
         "implisolid_ob02_create": ([c_char_p, c_char_p], c_void_p),
         "implisolid_ob02_destroy": ([c_void_p], None),
         "implisolid_ob02_load": ([c_void_p, c_void_p, ctypes.c_int64, c_void_p, ctypes.c_int64, ctypes.c_int64,
@@ -555,6 +559,45 @@ def debug_fold(terms):
     if rc != 0:
         raise ImplisolidError(last_error())
     return np.float32(out[0]), int(tc.value)
+
+
+def debug_intervals(shape, boxes, variant=0, modes_in=None, ignore_root_matrix=False):
+    """Diagnostics: the interval evaluator on boxes [n, 6] = {xlo, xhi, ylo, yhi, zlo, zhi} of the
+    tree; variant 0 the interpreter, 1 the shape's JIT module, 2 the baked module.  modes_in: per box
+    the modes word of an enclosing box.  Returns (iv float32[n, 2] = {lo, hi}, modes uint64[n])."""
+    b = np.ascontiguousarray(boxes, np.float32).reshape(-1, 6)
+    n = b.shape[0]
+    up64 = ctypes.POINTER(ctypes.c_uint64)
+    mi = None
+    if modes_in is not None:
+        mi = np.ascontiguousarray(modes_in, np.uint64).reshape(-1)
+        if mi.size != n:
+            raise ValueError("debug_intervals: one modes word per box")
+    iv = np.empty((n, 2), np.float32)
+    mo = np.zeros(n, np.uint64)
+    fp = ctypes.POINTER(ctypes.c_float)
+    rc = lib().implisolid_debug_intervals(_s(shape), int(bool(ignore_root_matrix)), int(variant), b.ctypes.data_as(fp),
+                                          mi.ctypes.data_as(up64) if mi is not None else None, n,
+                                          iv.ctypes.data_as(fp), mo.ctypes.data_as(up64))
+    if rc != 0:
+        raise ImplisolidError(last_error())
+    return iv, mo
+
+
+def debug_eval_modes(shape, pts, modes, ignore_root_matrix=False):
+    """Diagnostics: the pruned point interpreter at pts [n, 3], each with its own modes word."""
+    x = np.ascontiguousarray(pts, np.float32).reshape(-1, 3)
+    m = np.ascontiguousarray(modes, np.uint64).reshape(-1)
+    if m.size != x.shape[0]:
+        raise ValueError("debug_eval_modes: one modes word per point")
+    out = np.empty(x.shape[0], np.float32)
+    fp = ctypes.POINTER(ctypes.c_float)
+    rc = lib().implisolid_debug_eval_modes(_s(shape), int(bool(ignore_root_matrix)), x.ctypes.data_as(fp),
+                                           m.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), x.shape[0],
+                                           out.ctypes.data_as(fp))
+    if rc != 0:
+        raise ImplisolidError(last_error())
+    return out
 
 
 def program_info(shape, ignore_root_matrix=False):

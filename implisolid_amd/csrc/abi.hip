@@ -657,6 +657,108 @@ int implisolid_debug_cos(const double* a, int64_t n, double* out) {
     return 0;
 }
 
+// the diagnostics below hold their own copy of the program on the device (the engine's object, if
+// any, is left alone); freed on every path
+namespace {
+struct ProbeProgram {
+    DevBuf buf;
+    explicit ProbeProgram(const Program& p) {
+        buf.reserve(sizeof(Program));
+        IMPLI_HIP(hipMemcpy(buf.p, &p, sizeof(Program), hipMemcpyHostToDevice));
+    }
+    ~ProbeProgram() { buf.release(); }
+    const Program* get() const { return buf.as<Program>(); }
+};
+}  // namespace
+
+int implisolid_debug_intervals(const char* shape_json, int ignore_root_matrix, int variant, const float* boxes,
+                               const uint64_t* modes_in, int64_t n, float* iv_out, uint64_t* modes_out) {
+    if (!shape_json || variant < 0 || variant > 2 || n < 0 || (n && (!boxes || !iv_out || !modes_out))) {
+        report("implisolid_debug_intervals: bad arguments", false);
+        return -1;
+    }
+    if (n == 0) return 0;
+    TreeJit::Slot* slot = nullptr;
+    try {
+        const Program p = compile_mp5(shape_json, ignore_root_matrix != 0);
+        Engine& E = engine();
+        hipStream_t s = abi_stream();
+        hipFunction_t fn = nullptr;
+        if (variant) {   // the shape module (1) or the object's baked module (2), compiled before the launch
+            TreeJit& J = TreeJit::instance();
+            const int mode = J.mode();
+            J.set_mode(TreeJit::kSync);
+            slot = J.request(p, TreeJit::kBricks, variant == 2, s);
+            J.set_mode(mode);
+            if (!slot || !slot->ready.load(std::memory_order_acquire) || !slot->k.debug_iv)
+                throw std::runtime_error("implisolid_debug_intervals: the tree module did not compile");
+            fn = slot->k.debug_iv;
+        }
+        ProbeProgram dp(p);
+        DevBuf& db = E.scratch(0);
+        DevBuf& dm = E.scratch(1);
+        DevBuf& dout = E.scratch(2);
+        db.reserve((size_t)n * 24);
+        dm.reserve((size_t)n * 16);   // modes_in, then modes_out
+        dout.reserve((size_t)n * 8);
+        uint64_t* d_mi = modes_in ? dm.as<uint64_t>() : nullptr;
+        uint64_t* d_mo = dm.as<uint64_t>() + n;
+        IMPLI_HIP(hipMemcpyAsync(db.p, boxes, (size_t)n * 24, hipMemcpyHostToDevice, s));
+        if (modes_in) IMPLI_HIP(hipMemcpyAsync(d_mi, modes_in, (size_t)n * 8, hipMemcpyHostToDevice, s));
+        launch_iv_probe(dp.get(), p.max_depth, E.d_rabbit(), E.tab_range(), db.as<float>(), d_mi, n, dout.as<float>(), d_mo, s,
+                        fn);
+        IMPLI_HIP(hipGetLastError());
+        IMPLI_HIP(hipMemcpyAsync(iv_out, dout.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+        IMPLI_HIP(hipMemcpyAsync(modes_out, d_mo, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+        IMPLI_HIP(hipStreamSynchronize(s));
+        TreeJit::instance().release(slot);
+    } catch (const InputError& e) {
+        TreeJit::instance().release(slot);
+        report(e.what(), true);
+        return -1;
+    } catch (const std::exception& e) {
+        (void)hipDeviceSynchronize();
+        TreeJit::instance().release(slot);
+        report(e.what(), false);
+        return -1;
+    }
+    return 0;
+}
+
+int implisolid_debug_eval_modes(const char* shape_json, int ignore_root_matrix, const float* xyz, const uint64_t* modes,
+                                int64_t n, float* f_out) {
+    if (!shape_json || n < 0 || (n && (!xyz || !modes || !f_out))) {
+        report("implisolid_debug_eval_modes: bad arguments", false);
+        return -1;
+    }
+    if (n == 0) return 0;
+    try {
+        const Program p = compile_mp5(shape_json, ignore_root_matrix != 0);
+        Engine& E = engine();
+        hipStream_t s = abi_stream();
+        ProbeProgram dp(p);
+        DevBuf& dx = E.scratch(0);
+        DevBuf& dm = E.scratch(1);
+        DevBuf& df = E.scratch(2);
+        dx.reserve((size_t)n * 12);
+        dm.reserve((size_t)n * 8);
+        df.reserve((size_t)n * 4);
+        IMPLI_HIP(hipMemcpyAsync(dx.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, s));
+        IMPLI_HIP(hipMemcpyAsync(dm.p, modes, (size_t)n * 8, hipMemcpyHostToDevice, s));
+        launch_eval_modes_probe(dp.get(), p.max_depth, E.d_rabbit(), dx.as<float>(), dm.as<uint64_t>(), n, df.as<float>(), s);
+        IMPLI_HIP(hipGetLastError());
+        IMPLI_HIP(hipMemcpyAsync(f_out, df.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        IMPLI_HIP(hipStreamSynchronize(s));
+    } catch (const InputError& e) {
+        report(e.what(), true);
+        return -1;
+    } catch (const std::exception& e) {
+        report(e.what(), false);
+        return -1;
+    }
+    return 0;
+}
+
 void calculate_implicit_values(void) {
     if (!g_eval.has_x || !g_eval.has_object) {
         report("Error: You need to set_x() and set_object() first.", false);

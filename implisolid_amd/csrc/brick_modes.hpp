@@ -185,4 +185,22 @@ __device__ __forceinline__ void brick_refine_body(const IvEval& ev, const GridDe
     }
 }
 
+// diagnostics (implisolid_debug_intervals): bound n caller-given boxes {xlo, xhi, ylo, yhi, zlo, zhi},
+// one thread per box, starting from modes_in[i] (null: none pruned) -- the tests' direct view of the
+// bounds and decisions the passes above take per grid box
+template <class IvEval>
+__device__ __forceinline__ void debug_iv_body(const IvEval& ev, const float* __restrict__ boxes,
+                                              const uint64_t* __restrict__ modes_in, int64_t n,
+                                              float* __restrict__ iv_out, uint64_t* __restrict__ modes_out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* b = boxes + 6 * i;
+    const dev::Box p{dev::Iv{b[0], b[1]}, dev::Iv{b[2], b[3]}, dev::Iv{b[4], b[5]}};
+    uint64_t m = 0;
+    const dev::Iv r = ev(p, modes_in ? modes_in[i] : (uint64_t)0, m);
+    iv_out[2 * i] = r.lo;
+    iv_out[2 * i + 1] = r.hi;
+    modes_out[i] = m;
+}
+
 }  // namespace impli

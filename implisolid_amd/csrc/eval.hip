@@ -764,4 +764,54 @@ void launch_cos_probe(const double* d_a, int64_t n, double* d_out, hipStream_t s
     k_cos_probe<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(d_a, n, d_out);
 }
 
+// diagnostics: the interval interpreter on n caller-given boxes, one thread per box (the JIT
+// modules' counterpart is impli_debug_iv, jit.cpp) -- the tests compare the bounds and the modes
+// with the oracle's point values inside each box
+template <int D>
+__global__ __launch_bounds__(256) void k_iv_probe(const Program* __restrict__ prog, const float* __restrict__ tab,
+                                                   float2 tab_range, const float* __restrict__ boxes,
+                                                   const uint64_t* __restrict__ modes_in, int64_t n,
+                                                   float* __restrict__ iv_out, uint64_t* __restrict__ modes_out) {
+    debug_iv_body(InterpIv<D>{prog, tab, tab_range}, boxes, modes_in, n, iv_out, modes_out);
+}
+
+void launch_iv_probe(const Program* d_prog, int depth, const float* d_rabbit, float2 tab_range, const float* d_boxes,
+                     const uint64_t* d_modes_in, int64_t n, float* d_iv, uint64_t* d_modes_out, hipStream_t s,
+                     hipFunction_t jit_fn) {
+    if (n <= 0) return;
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    if (jit_fn) {
+        const float* d_mats = reinterpret_cast<const float*>(reinterpret_cast<const char*>(d_prog) + offsetof(Program, mats));
+        void* a[] = {&d_mats, &d_rabbit, &tab_range, &d_boxes, &d_modes_in, &n, &d_iv, &d_modes_out};
+        TreeJit::launch(jit_fn, blocks, a, s, "impli_debug_iv");
+        return;
+    }
+    depth = eval_depth(depth);
+    if (depth <= 4) k_iv_probe<4><<<blocks, 256, 0, s>>>(d_prog, d_rabbit, tab_range, d_boxes, d_modes_in, n, d_iv, d_modes_out);
+    else if (depth <= 8) k_iv_probe<8><<<blocks, 256, 0, s>>>(d_prog, d_rabbit, tab_range, d_boxes, d_modes_in, n, d_iv, d_modes_out);
+    else if (depth <= 12) k_iv_probe<12><<<blocks, 256, 0, s>>>(d_prog, d_rabbit, tab_range, d_boxes, d_modes_in, n, d_iv, d_modes_out);
+    else k_iv_probe<16><<<blocks, 256, 0, s>>>(d_prog, d_rabbit, tab_range, d_boxes, d_modes_in, n, d_iv, d_modes_out);
+}
+
+// diagnostics: the pruned point interpreter with a caller-given modes word per point
+template <int D>
+__global__ __launch_bounds__(256) void k_eval_modes_probe(const Program* __restrict__ prog, const float* __restrict__ tab,
+                                                           const float* __restrict__ xyz, const uint64_t* __restrict__ modes,
+                                                           int64_t n, float* __restrict__ f_out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    f_out[i] = dev::eval_f_pruned<D>(prog, tab, modes[i], xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
+}
+
+void launch_eval_modes_probe(const Program* d_prog, int depth, const float* d_rabbit, const float* d_xyz,
+                             const uint64_t* d_modes, int64_t n, float* d_f, hipStream_t s) {
+    if (n <= 0) return;
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    depth = eval_depth(depth);
+    if (depth <= 4) k_eval_modes_probe<4><<<blocks, 256, 0, s>>>(d_prog, d_rabbit, d_xyz, d_modes, n, d_f);
+    else if (depth <= 8) k_eval_modes_probe<8><<<blocks, 256, 0, s>>>(d_prog, d_rabbit, d_xyz, d_modes, n, d_f);
+    else if (depth <= 12) k_eval_modes_probe<12><<<blocks, 256, 0, s>>>(d_prog, d_rabbit, d_xyz, d_modes, n, d_f);
+    else k_eval_modes_probe<16><<<blocks, 256, 0, s>>>(d_prog, d_rabbit, d_xyz, d_modes, n, d_f);
+}
+
 }  // namespace impli

@@ -646,7 +646,8 @@ void TreeJit::build(Slot* slot) {
             if (ok && slot->kind == kBricks)
                 ok = hipModuleGetFunction(&k.bricks, slot->mod, "impli_eval_bricks") == hipSuccess &&
                      hipModuleGetFunction(&k.coarse, slot->mod, "impli_coarse_modes") == hipSuccess &&
-                     hipModuleGetFunction(&k.refine, slot->mod, "impli_brick_refine") == hipSuccess;
+                     hipModuleGetFunction(&k.refine, slot->mod, "impli_brick_refine") == hipSuccess &&
+                     hipModuleGetFunction(&k.debug_iv, slot->mod, "impli_debug_iv") == hipSuccess;
             if (ok && slot->kind == kPoints)
                 ok = hipModuleGetFunction(&pk.cnormals, slot->mod, "impli_pt_centroid_normals") == hipSuccess &&
                      hipModuleGetFunction(&pk.prep, slot->mod, "impli_pt_project_prep") == hipSuccess &&
@@ -1001,6 +1002,11 @@ std::string TreeJit::kernel_source(const Program& p, bool bake) {
       << "    impli::BrickGrid cg, const uint64_t* cmodes, const uint32_t* clist, const uint32_t* ccount,\n"
       << "    uint64_t* modes, uint8_t* cls) {\n"
       << "    impli::brick_refine_body(impli::JitIv{M, tab, tab_range}, g, bg, cg, cmodes, clist, ccount, modes, cls);\n}\n"
+      // diagnostics (implisolid_debug_intervals): tree_iv on caller-given boxes, one thread per box
+      << "extern \"C\" __global__ __launch_bounds__(256) void impli_debug_iv(\n"
+      << "    const float* M, const float* tab, float2 tab_range, const float* boxes, const uint64_t* modes_in,\n"
+      << "    int64_t n, float* iv_out, uint64_t* modes_out) {\n"
+      << "    impli::debug_iv_body(impli::JitIv{M, tab, tab_range}, boxes, modes_in, n, iv_out, modes_out);\n}\n"
 ;
     return s.str();
 }

@@ -43,6 +43,7 @@ public:
         hipFunction_t bricks = nullptr;   // brick-pruned field (eval_bricks_body)
         hipFunction_t coarse = nullptr;   // interval pass, coarse boxes (coarse_modes_body)
         hipFunction_t refine = nullptr;   // interval pass, bricks of mixed boxes (brick_refine_body)
+        hipFunction_t debug_iv = nullptr; // diagnostics: tree_iv on caller-given boxes (debug_iv_body)
     };
     struct PointKernels {                 // the point module (ob02_device.hpp bodies)
         hipFunction_t cnormals = nullptr, prep = nullptr, early = nullptr, early2 = nullptr, late = nullptr,

@@ -48,6 +48,13 @@ void launch_eval_points(const Program* d_prog, int depth, const float* d_rabbit,
 // diagnostics: glibc sinf (0) / atanf (1) / atan2f (2) restatements on device operands
 void launch_libm_probe(int which, const float* d_a, const float* d_b, int64_t n, float* d_out, hipStream_t s);
 void launch_cos_probe(const double* d_a, int64_t n, double* d_out, hipStream_t s);
+// diagnostics: the interval evaluator on n boxes, one thread per box (jit_fn: a tree module's
+// impli_debug_iv instead of the interpreter), and the pruned point interpreter with a modes word per point
+void launch_iv_probe(const Program* d_prog, int depth, const float* d_rabbit, float2 tab_range, const float* d_boxes,
+                     const uint64_t* d_modes_in /* nullable */, int64_t n, float* d_iv, uint64_t* d_modes_out,
+                     hipStream_t s, hipFunction_t jit_fn = nullptr);
+void launch_eval_modes_probe(const Program* d_prog, int depth, const float* d_rabbit, const float* d_xyz,
+                             const uint64_t* d_modes, int64_t n, float* d_f, hipStream_t s);
 
 // K2 (count per group) and K2b (group bases + flat list of non-empty units)
 void launch_mc_count(const CaseInfo* d_cases, const GridDesc& g, const MCBuffers& b, hipStream_t s);

@@ -152,6 +152,20 @@ int implisolid_debug_cos(const double* a, int64_t n, double* out);
    build_geometry computes it -- the chunk table and the device walk; *sum_out = s, *table_chunks
    (may be NULL) = chunks the walk took from the table.  0, or -1 with implisolid_last_error(). */
 int implisolid_debug_fold(const float* terms, int64_t n, float* sum_out, int64_t* table_chunks);
+/* Additive, diagnostics (never called by build_geometry or the slab pipeline): the interval evaluator
+   that prunes CSG operands per brick, on n caller-given world-space boxes {xlo, xhi, ylo, yhi, zlo,
+   zhi} of the MP5 tree, one thread per box.  variant 0: the interpreter (eval_iv); 1: the tree
+   shape's hipRTC module (tree_iv, matrices read from memory); 2: the object's baked module (matrices
+   as literals) -- 1 and 2 compile the module first if need be.  modes_in (may be NULL: nothing
+   pruned) holds per box the modes word of an enclosing box; iv_out receives {lo, hi} of the root and
+   modes_out the 2-bit decision per CSG node (0 both operands, 1 left only, 2 right only; nodes past
+   the 32nd are never pruned).  0, or -1 with implisolid_last_error(). */
+int implisolid_debug_intervals(const char* shape_json, int ignore_root_matrix, int variant, const float* boxes,
+                               const uint64_t* modes_in, int64_t n, float* iv_out, uint64_t* modes_out);
+/* Additive, diagnostics: the pruned point interpreter (eval_f_pruned) at n points, each with its own
+   modes word (as implisolid_debug_intervals returns them for a box holding the point); 0 or -1 */
+int implisolid_debug_eval_modes(const char* shape_json, int ignore_root_matrix, const float* xyz, const uint64_t* modes,
+                                int64_t n, float* f_out);
 
 /* host-only: compile an MP5 tree to the node program; info = {n_instr, depth, n_mats, 0};
    mats_out receives n_mats inverse matrices (12 floats each, up to 256) */

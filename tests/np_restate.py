@@ -6,7 +6,7 @@ evaluation, numpy's ``np.unique`` instead of a hash map for first-appearance num
 float32/float64 arithmetic is one IEEE operation per ufunc call, with no FMA contraction, so
 results are comparable bit for bit.
 
-Covered: the MP5 factory for scale+translate trees, node evaluation (egg, rabbit cube, cylinder,
+Covered: the MP5 factory, the node matrices' LU inverse (invert_matrix), node evaluation (egg, rabbit cube, cylinder,
 cone, heart, torus, double mushroom, union/intersection/difference), prepare_grid + sealing and
 marching cubes with the std::map first-appearance vertex numbering.
 """
@@ -136,7 +136,8 @@ PRIMS = {"iellipsoid": egg, "ellipsoid": egg, "cube": cube, "icube": cube, "icyl
 # ---- factory + evaluation (object_factory.hpp:56-758; transformed_*.hpp) -------------------------
 def _inverse_scale_translate(m):
     """Inverse of a scale+translate matrix.  For such a matrix ublas' LU (basic_functions.hpp:77-128)
-    needs no pivoting, L = I and back substitution gives exactly 1/s and (0 - t*1)/s = -t/s."""
+    needs no pivoting, L = I and back substitution gives exactly 1/s, (0 - t*1)/s and, off the diagonal,
+    0/s (zeros whose sign follows the scale's)."""
     m = np.asarray([np.float32(float(v)) for v in m[:12]], np.float32)
     for k in (1, 2, 4, 6, 8, 9):
         if m[k] != 0:
@@ -144,9 +145,55 @@ def _inverse_scale_translate(m):
     inv = np.zeros(12, np.float32)
     for r, (d, t) in enumerate(((0, 3), (5, 7), (10, 11))):
         s = m[d]
+        inv[4 * r:4 * r + 3] = f32(0) / s                    # the row's other entries: 0 / s, -0 under a negative scale
         inv[d] = f32(1) / s
-        inv[t] = -m[t] / s
+        inv[t] = (f32(0) - m[t]) / s                      # a zero translation inverts to +0, not -0
     return inv
+
+
+def _inverse_general(m):
+    """Inverse of a general 3x4 node matrix (last row 0 0 0 1), restating invert_matrix
+    (basic_functions.hpp:77-128): uBLAS lu_factorize with partial pivoting -- per column the first
+    entry of largest magnitude, the sub-column multiplied by the float reciprocal of the pivot, then
+    the rank-1 update of the trailing block -- and lu_substitute on the identity (row swaps, unit
+    lower forward solve, upper backward solve, each right-hand-side column independent).  Whole
+    rows / columns at a time, every numpy operation one IEEE float32 operation per element (the
+    oracle's C loop goes entry by entry).  uBLAS's solves skip the update where the solved entry t is
+    0 (so a -0 there survives); the mask below does the same.  Returns None for a singular matrix."""
+    A = np.zeros((4, 4), np.float32)
+    A[:3, :] = np.asarray([np.float32(float(v)) for v in m[:12]], np.float32).reshape(3, 4)
+    A[3, 3] = f32(1)
+    E = np.eye(4, dtype=np.float32)
+    for i in range(4):
+        col = np.abs(A[i:, i])
+        piv = i + int(np.argmax(col))                    # first maximum, as index_norm_inf
+        if A[piv, i] == 0:
+            return None
+        if piv != i:
+            A[[i, piv], :] = A[[piv, i], :]
+            E[[i, piv], :] = E[[piv, i], :]              # swap_rows(pm, identity): the same swaps in order
+        A[i + 1:, i] = A[i + 1:, i] * (f32(1) / A[i, i])
+        A[i + 1:, i + 1:] = A[i + 1:, i + 1:] - np.outer(A[i + 1:, i], A[i, i + 1:]).astype(np.float32)
+    for n in range(4):                                   # unit lower triangle, forward
+        upd = E[n + 1:, :] - np.outer(A[n + 1:, n], E[n, :]).astype(np.float32)
+        E[n + 1:, :] = np.where(E[n, :] != 0, upd, E[n + 1:, :])
+    for n in range(3, -1, -1):                           # upper triangle, backward
+        E[n, :] = E[n, :] / A[n, n]
+        upd = E[:n, :] - np.outer(A[:n, n], E[n, :]).astype(np.float32)
+        E[:n, :] = np.where(E[n, :] != 0, upd, E[:n, :])
+    return E[:3, :].reshape(12).copy()
+
+
+def _inverse(m):
+    """The node's inverse matrix: the closed form for scale + translate (no pivoting happens), the
+    LU restatement otherwise."""
+    try:
+        return _inverse_scale_translate(m)
+    except ValueError:
+        inv = _inverse_general(m)
+        if inv is None:
+            raise ValueError("singular node matrix")
+        return inv
 
 
 def _xform(mi, x, y, z):               # matrix_vector_product basic_functions.hpp:140-177
@@ -159,10 +206,10 @@ EYE = [1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0]
 
 
 def evaluate(shape, x, y, z, _root=True):
-    """f at float32 points for an MP5 tree of scale+translate nodes."""
+    """f at float32 points for an MP5 tree of the restated primitives under any invertible matrices."""
     d = json.loads(shape) if isinstance(shape, str) else shape
     t = d["type"]
-    mi = _inverse_scale_translate(d["matrix"])
+    mi = _inverse(d["matrix"])
     X, Y, Z = _xform(mi, x, y, z)
     if t in PRIMS:
         return PRIMS[t](X, Y, Z)

@@ -91,6 +91,78 @@ def test_point_eval_matches_numpy_restatement(oracle):
         assert np.array_equal(_u32(fo), _u32(fn)), name
 
 
+def _matrix_trees():
+    """One tree per matrix family (tests/matrices.py): the family on the leaves, on the CSG nodes and
+    nested three deep, over the seven primitives the numpy restatement covers."""
+    import matrices
+    t = {}
+    for k, fam in enumerate(matrices.FAMILIES):
+        types = [matrices.NP_TYPES[(k + j) % 7] for j in range(4)]
+        t[fam] = matrices.family_tree(fam, seed=k, types=types)
+    t["perm_cube"] = matrices.family_tree("perm", seed=4, types=["cube", "icone", "iheart", "iellipsoid"])
+    return t
+
+
+MATRIX_TREES = _matrix_trees()
+
+
+@pytest.mark.parametrize("name", sorted(MATRIX_TREES))
+def test_oracle_matches_numpy_restatement_on_matrix_families(oracle, name):
+    """The C oracle is pinned by the independent numpy restatement on general node matrices
+    (rotations, shears, permutations with +-0 translations, mirrors, anisotropic scales): the LU
+    inverse of every node (invert_matrix, basic_functions.hpp:77-128), point values including
+    +-0 and lattice coordinates, the grid field and the marching-cubes mesh."""
+    import matrices
+    shape = MATRIX_TREES[name]
+    tree = oracle.mp5_to_nodes(json.dumps(shape))
+    for node in tree[0]:
+        m = [float(v) for v in node.m[:]]
+        assert np.array_equal(_u32(np_restate._inverse(m)), _u32(np.array(node.minv[:], np.float32))), m
+    pts = matrices.lattice_points(20000, 5, reach=1.3)
+    fo = oracle.eval_implicit(tree, pts)
+    fn = np_restate.evaluate(shape, pts[:, 0].copy(), pts[:, 1].copy(), pts[:, 2].copy())
+    assert np.array_equal(_u32(fo), _u32(fn)), np.flatnonzero(_u32(fo) != _u32(fn))[:10]
+    R, box = 29, [-1, 1] * 3
+    F, w = np_restate.field(shape, R, box)
+    assert np.array_equal(_u32(F), _u32(oracle.mc_field(tree, R, box)))
+    v, f = np_restate.marching_cubes(F, w, box, R)
+    vo, fo_ = oracle.marching_cubes(tree, R, box)
+    assert len(f) > 200 and np.array_equal(f, fo_) and np.array_equal(_u32(v), _u32(vo))
+
+
+def test_matrix_families_are_what_they_claim():
+    """tests/matrices.py: deterministic, float32-exact, and each family's defining property."""
+    import matrices
+    for fam in matrices.FAMILIES:
+        for seed in range(12):
+            m = matrices.matrix(fam, seed)
+            assert m == matrices.matrix(fam, seed) and all(float(np.float32(v)) == v for v in m)
+            A = np.array([m[0:3], m[4:7], m[8:11]])
+            off = A[~np.eye(3, dtype=bool)]
+            assert abs(np.linalg.det(A)) > 1e-4
+            if fam == "rot":
+                assert (A != 0).all() and np.linalg.det(A) > 0
+            elif fam in ("aniso", "thin"):
+                assert (off == 0).all()
+            elif fam == "shear":
+                assert (A[np.triu_indices(3, 1)] != 0).all() and (A[np.tril_indices(3, -1)] == 0).all()
+            elif fam == "perm":
+                assert set(np.abs(A).ravel()) == {0.0, 1.0} and (np.abs(A).sum(0) == 1).all()
+            elif fam == "rotz":
+                assert (off == 0).sum() == 4 and (A == 1).sum() == 1
+            elif fam == "mirror":
+                assert np.linalg.det(A) < 0
+    thin = [matrices.matrix("thin", s) for s in range(12)]
+    assert max(max(m[0], m[5], m[10]) / min(m[0], m[5], m[10]) for m in thin) > 12
+    # perm: the three translation kinds all occur (+0.0, -0.0, non-zero)
+    kinds = set()
+    for seed in range(6):
+        m = matrices.matrix("perm", seed)
+        for t in (m[3], m[7], m[11]):
+            kinds.add("nz" if t != 0 else ("-0" if np.signbit(t) else "+0"))
+    assert kinds == {"nz", "-0", "+0"}
+
+
 # ---- golden fixtures ------------------------------------------------------------------------------
 def test_golden_config1(oracle):
     g = np.load(os.path.join(GOLDEN, "config1_mc.npz"))
