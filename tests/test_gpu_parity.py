@@ -681,6 +681,15 @@ def test_ob02_projection_no_qem(impli, oracle):
     ref_tree = oracle.mp5_to_nodes(json.dumps(scenes.union_sphere_cube()))
     p = impli.get_pointset("post_p_centroids")
     assert p is not None and p.shape[1] == 3
+    # without QEM the projection moves no vertex: the mesh compared above cannot see a wrong centroid,
+    # so the centroids themselves are compared with the oracle's, bit for bit
+    taps = {}
+    oracle.polygonize(json.dumps(scenes.union_sphere_cube()), json.dumps(mc), taps)
+    cr = taps["post_p_centroids"][-1]
+    assert p.shape == cr.shape
+    bad = np.flatnonzero(~_same_bits(p, cr).all(1))
+    assert bad.size == 0, (bad.size, bad[:10])
+    assert (p != impli.get_pointset("pre_p_centroids")).any(1).mean() > 0.95   # and most of them did move
 
 
 @pytest.mark.parametrize("repeats", [1, 2])
