@@ -62,6 +62,41 @@ __device__ __forceinline__ void eval_pair(const Eval& ev, uint64_t m, float x, f
     f1 = ev(m, x, y, z1);
 }
 
+// The JIT kernel's arguments are one EvalBricksArgs (grid.hpp) by value: its kernarg segment.  Kept
+// in SGPRs across the tree code they were parked in VGPR lanes (a lane write or read plus a hazard
+// slot each): the JIT evaluator reads them again where they are used, with scalar loads from the
+// kernarg segment that cost no vector slot (kernarg_again; JitEval::again in jit.cpp takes the
+// offsets from the struct that is the kernel's parameter, so they cannot drift from it).
+// T at byte offset `off` of the calling kernel's kernarg segment, loaded anew: the empty asm (no
+// instruction) hides the pointer's origin, so the loads are not merged with earlier ones
+template <class T>
+__device__ __forceinline__ T kernarg_again(unsigned off) {
+    const __attribute__((address_space(4))) char* p =
+        (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    static_assert(sizeof(T) % 4 == 0, "whole words");
+    // word by word through the constant address space (scalar loads; the unused ones go away)
+    const __attribute__((address_space(4))) uint32_t* src = (const __attribute__((address_space(4))) uint32_t*)(p + off);
+    uint32_t w[sizeof(T) / 4];
+#pragma unroll
+    for (unsigned k = 0; k < sizeof(T) / 4; ++k) w[k] = src[k];
+    T v;
+    __builtin_memcpy(&v, w, sizeof(T));
+    return v;
+}
+// a pointer read that way is a kernel argument like the first copy: global memory, not generic
+// (through its integer value: a global address is the same number in both address spaces, and a
+// plain cast there and back folds away)
+template <class T>
+__device__ __forceinline__ T* as_global(T* p) { return (T*)(__attribute__((address_space(1))) T*)(uint64_t)p; }
+// whether the evaluator re-reads the kernel's arguments (ev.again(v): the JIT kernel's evaluator;
+// the interpreter kernels' evaluators do not, and run eval_listed as it always was)
+template <class Eval, class = void> struct HasAgain { static constexpr bool value = false; };
+template <class Eval>
+struct HasAgain<Eval, decltype(static_cast<const Eval*>(nullptr)->again(*static_cast<const GridDesc*>(nullptr)), void())> {
+    static constexpr bool value = true;
+};
+
 // one brick (b, its modes m) by the calling wave; neg[k]: layer k's sign bits, valid: the lanes
 // inside the grid
 template <class Eval, bool Pair = IMPLI_EVAL_PAIR != 0>
@@ -216,6 +251,83 @@ __device__ __forceinline__ void eval_listed(const Eval& ev, const GridDesc& g, c
     }
 }
 
+// eval_one_brick's layer pair for an evaluator that re-reads the kernel's arguments: nothing of
+// them is live across the tree code
+template <class Eval>
+__device__ __forceinline__ void eval_one_brick_again(const Eval& ev, const GridDesc& g, const BrickGrid& bg, int b,
+                                                     uint64_t m64, const StorePtrs& ptrs, bool write_signs,
+                                                     uint64_t neg[kBZ], uint64_t& valid) {
+    static_assert(kBZ == 2, "the layer pair needs two layers per brick");
+    const int lane = threadIdx.x & 63;
+    int bx, by, bz;
+    brick_of(b, bg, bx, by, bz);
+    const int sx = bx * kBX + (lane % kBX), sy = by * kBY + (lane / kBX);
+    const uint64_t m = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(m64 >> 32)) << 32) |
+                       (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)m64);
+    const int l0 = bz * kBZ, l1 = l0 + 1;
+    float f0, f1;
+    {   // before the tree code: the sample coordinates
+        const GridDesc ga = ev.again(g);
+        const bool ok = sx < ga.n && sy < ga.n;
+        const float x = sample_xy(ga, 0, ok ? sx : 0), y = sample_xy(ga, 1, ok ? sy : 0);
+        eval_pair(ev, m, x, y, sample_z(ga, l0), sample_z(ga, l1 < ga.fz1 - ga.fz0 ? l1 : l0), f0, f1, 0);
+    }
+    // after it: what the stores need
+    const GridDesc gs = ev.again(g);
+    const StorePtrs sp = ev.again(ptrs);
+    float* __restrict__ const field = sp.field;
+    sign_piece_t* __restrict__ const signs = static_cast<sign_piece_t*>(sp.signs);
+    const int n = gs.n, layers = gs.fz1 - gs.fz0, row_pieces = (64 / kBX) * sign_row_words(gs);
+    valid = __ballot(sx < n && sy < n);
+    const bool sealed_col = sealed_xy(gs, sx) || sealed_xy(gs, sy);
+    float* out = field + (size_t)b * kBrickSamples + lane;
+    neg[0] = neg[1] = 0;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int layer = l0 + k;
+        if (layer >= layers) break;
+        const float v = (sealed_col || sealed_z(gs, layer)) ? kSealed : 0.f + (k ? f1 : f0);
+        out[k * kBX * kBY] = v;
+        neg[k] = __ballot(v < 0.f);
+        if (write_signs && lane < kBY) {
+            const int yy = by * kBY + lane;
+            if (yy < n) signs[((size_t)layer * n + yy) * row_pieces + bx] = (sign_piece_t)(neg[k] >> (kBX * lane));
+        }
+    }
+}
+
+// eval_listed for such an evaluator.  The claim takes the loop-carried cur (equal to b in the first
+// iteration, the only one that claims): given b, its brick arithmetic -- six neighbour addresses,
+// in-grid flags, atomic words and shifts -- is invariant in this loop, was hoisted above the tree
+// code and lived across it in 45 VGPR lanes.  cur is wave-uniform and said so, or instruction
+// selection moves its whole chain (brick_of's divisions, the addresses) to the vector unit.
+template <class Eval>
+__device__ __forceinline__ void eval_listed_again(const Eval& ev, const GridDesc& g, const BrickGrid& bg, const ClaimCtx& cc,
+                                                  uint32_t entry, uint64_t m64, const StorePtrs& ptrs) {
+    const int b = (int)(entry & ~kListCheck);
+    const bool check = (entry & kListCheck) && cc.fill;
+    int cur = b;
+    uint64_t mcur = m64;
+    uint32_t claimed = 0;
+    for (bool first = true;; first = false) {
+        uint64_t neg[kBZ], valid;
+        cur = __builtin_amdgcn_readfirstlane(cur);
+        eval_one_brick_again(ev, g, bg, cur, mcur, ptrs, first, neg, valid);
+        if (first && check) claimed = claim_neighbours(ev.again(g), bg, ev.again(cc), cur, neg, valid);
+        if (!claimed) break;
+        const ClaimCtx cn = ev.again(cc);
+        const int d = __builtin_ctz(claimed);
+        claimed &= claimed - 1u;
+        const int ax = d >> 1, up = d & 1;
+        const int step = ax == 0 ? 1 : ax == 1 ? bg.nbx : bg.nbx * bg.nby;
+        cur = up ? b + step : b - step;
+        int cx, cy, cz;
+        brick_of(cur, bg, cx, cy, cz);
+        const int cb = cx + cy * cn.cnbx + (cz / kCZ) * cn.cplane;
+        mcur = cn.ccls[cb] == kBrickMixed ? cn.bmodes[cur] : cn.cmodes[cb];
+    }
+}
+
 // The same entry without evaluating the claimed candidates in this wave: they are appended to
 // `claimed` (one atomic per claiming wave) for a second pass (eval.hip k_eval_claimed_b).  The
 // merged object-stream eval runs the interpreter, whose candidate loop kept its state live across a
@@ -269,7 +381,10 @@ __device__ __forceinline__ void eval_bricks_body(const Eval& ev, const GridDesc&
             b_next = list[i + stride];
             m_next = modes[i + stride];
         }
-        eval_listed<Eval, Pair>(ev, g, bg, cc, e, m64, field, signs);
+        if constexpr (Pair && HasAgain<Eval>::value)
+            eval_listed_again(ev, g, bg, cc, e, m64, StorePtrs{field, signs_raw});
+        else
+            eval_listed<Eval, Pair>(ev, g, bg, cc, e, m64, field, signs);
     }
 }
 

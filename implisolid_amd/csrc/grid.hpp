@@ -64,6 +64,21 @@ struct ClaimCtx {
     const uint64_t* cmodes;   // per-coarse-box modes
     int cnbx, cplane;         // coarse grid: boxes per row, per layer
 };
+// impli_eval_bricks' (jit.cpp) argument block: the kernel's single by-value parameter, filled by
+// TreeJit::launch_bricks; the kernel's evaluator re-reads members from the kernarg segment by their
+// offsets in this struct (eval_bricks.hpp kernarg_again)
+struct StorePtrs { float* field; void* signs; };
+struct EvalBricksArgs {
+    const float* M;
+    const float* tab;
+    GridDesc g;
+    BrickGrid bg;
+    const uint64_t* modes;
+    const uint32_t* list;
+    const uint32_t* count;
+    StorePtrs out;
+    ClaimCtx cc;
+};
 // list entry: brick index | kListCheck if the brick is of mixed class (its wave claims candidates)
 constexpr uint32_t kListCheck = 0x80000000u;
 

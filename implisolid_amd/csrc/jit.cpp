@@ -980,7 +980,17 @@ std::string TreeJit::kernel_source(const Program& p, bool bake) {
       << "        return tree_f(M, tab, m, x, y, z);\n    }\n"
       << "    __device__ __forceinline__ void pair(uint64_t m, float x, float y, float z0, float z1, float& f0,\n"
       << "                                         float& f1) const {\n"
-      << "        tree_f2(M, tab, m, x, y, z0, z1, f0, f1);\n    }\n};\n"
+      << "        tree_f2(M, tab, m, x, y, z0, z1, f0, f1);\n    }\n"
+      // impli_eval_bricks' arguments read again from its kernarg segment (eval_bricks.hpp)
+      << "    __device__ __forceinline__ GridDesc again(const GridDesc&) const {\n"
+      << "        return kernarg_again<GridDesc>(__builtin_offsetof(EvalBricksArgs, g));\n    }\n"
+      << "    __device__ __forceinline__ StorePtrs again(const StorePtrs&) const {\n"
+      << "        const StorePtrs s = kernarg_again<StorePtrs>(__builtin_offsetof(EvalBricksArgs, out));\n"
+      << "        return StorePtrs{as_global(s.field), as_global(static_cast<uint8_t*>(s.signs))};\n    }\n"
+      << "    __device__ __forceinline__ ClaimCtx again(const ClaimCtx&) const {\n"
+      << "        const ClaimCtx c = kernarg_again<ClaimCtx>(__builtin_offsetof(EvalBricksArgs, cc));\n"
+      << "        return ClaimCtx{as_global(c.fill), as_global(c.ccls), as_global(c.bmodes), as_global(c.cmodes), c.cnbx, c.cplane};\n"
+      << "    }\n};\n"
       << "__device__ __forceinline__ Iv tree_iv(const float* __restrict__ M, const float* __restrict__ tab,\n"
       << "                                      float2 tab_range, Box p0, uint64_t modes_in, uint64_t& modes) {\n"
       << "    modes = modes_in;\n"
@@ -990,9 +1000,9 @@ std::string TreeJit::kernel_source(const Program& p, bool bake) {
       << "        return tree_iv(M, tab, tab_range, p, mi, m);\n    }\n};\n"
       << "}  // namespace impli\n"
       << "extern \"C\" __global__ __launch_bounds__(" << kEvalBlock << ")" << eval_waves_attr() << " void impli_eval_bricks(\n"
-      << "    const float* M, const float* tab, impli::GridDesc g, impli::BrickGrid bg, const uint64_t* modes,\n"
-      << "    const uint32_t* list, const uint32_t* count, float* field, void* signs, impli::ClaimCtx cc) {\n"
-      << "    impli::eval_bricks_body(impli::JitEval{M, tab}, g, bg, cc, modes, list, count, field, signs);\n}\n"
+      << "    impli::EvalBricksArgs a) {\n"
+      << "    impli::eval_bricks_body(impli::JitEval{a.M, a.tab}, a.g, a.bg, a.cc, a.modes, a.list, a.count, a.out.field,\n"
+      << "                            a.out.signs);\n}\n"
       << "extern \"C\" __global__ __launch_bounds__(256) void impli_coarse_modes(\n"
       << "    const float* M, const float* tab, float2 tab_range, impli::GridDesc g, impli::BrickGrid cg,\n"
       << "    uint64_t* cmodes, uint8_t* ccls, uint32_t* clist, uint32_t* counters) {\n"
@@ -1163,11 +1173,8 @@ void TreeJit::launch_bricks(hipFunction_t fn, const float* d_mats, const float* 
                             const uint32_t* d_count, float* d_field, void* d_signs, const ClaimCtx& cc, unsigned blocks,
                             hipStream_t s) {
     if (bg.n_bricks <= 0) return;
-    GridDesc gg = g;
-    BrickGrid bb = bg;
-    ClaimCtx c = cc;
-    void* args[] = {(void*)&d_mats, (void*)&d_rabbit, (void*)&gg, (void*)&bb, (void*)&d_modes,
-                    (void*)&d_list, (void*)&d_count, (void*)&d_field, (void*)&d_signs, (void*)&c};
+    EvalBricksArgs a{d_mats, d_rabbit, g, bg, d_modes, d_list, d_count, StorePtrs{d_field, d_signs}, cc};
+    void* args[] = {(void*)&a};
     if (hipModuleLaunchKernel(fn, blocks, 1, 1, kEvalBlock, 1, 1, 0, s, args, nullptr) != hipSuccess)
         throw std::runtime_error("hipModuleLaunchKernel(impli_eval_bricks) failed");
 }
