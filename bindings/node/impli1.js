@@ -18,6 +18,9 @@ const impli1 = {
   get_f_size: () => native.get_f_size(),
   get_v: () => native.get_v(),              // Float32Array, 3 per vertex
   get_f: () => native.get_f(),              // Uint32Array, 3 per face
+  // per-vertex normals of the same build, when params had "normals": {"enabled": 1} (else size 0)
+  get_n_size: () => native.get_n_size(),
+  get_n: () => native.get_n(),              // Float32Array, 3 per vertex
   finish_geometry: () => native.finish_geometry(),
   set_object: (mp5_str, ignore_root_matrix) => native.set_object(mp5_str, !!ignore_root_matrix),
   unset_object: (id) => native.unset_object(id),

@@ -127,6 +127,11 @@ static napi_value js_get_v(napi_env env, napi_callback_info info) {   /* get_v_p
     (void)info;
     return typed_copy(env, get_v_ptr(), (size_t)get_v_size() * 3, napi_float32_array);
 }
+static napi_value js_get_n_size(napi_env env, napi_callback_info info) { (void)info; return number(env, get_n_size()); }
+static napi_value js_get_n(napi_env env, napi_callback_info info) {   /* get_n_ptr: empty without the "normals" key */
+    (void)info;
+    return typed_copy(env, get_n_ptr(), (size_t)get_n_size() * 3, napi_float32_array);
+}
 static napi_value js_get_f(napi_env env, napi_callback_info info) {   /* get_f_ptr + HEAPU32 view */
     (void)info;
     return typed_copy(env, get_f_ptr(), (size_t)get_f_size() * 3, napi_uint32_array);
@@ -257,6 +262,8 @@ static napi_value init(napi_env env, napi_value exports) {
     EXPORT("get_v_size", js_get_v_size);
     EXPORT("get_f_size", js_get_f_size);
     EXPORT("get_v", js_get_v);
+    EXPORT("get_n_size", js_get_n_size);
+    EXPORT("get_n", js_get_n);
     EXPORT("get_f", js_get_f);
     EXPORT("finish_geometry", js_finish_geometry);
     EXPORT("set_object", js_set_object);

@@ -47,6 +47,8 @@ ABI_SYMBOLS = [
     "implisolid_ob02_get_verts", "implisolid_ob02_set_verts", "implisolid_ob02_download",
     "implisolid_ob02_attach", "implisolid_ob02_stream", "implisolid_ob02_resample_async", "implisolid_ob02_project_async",
     "implisolid_ob02_unpack", "implisolid_ob02_halo",
+    "get_n_size", "get_n_ptr", "get_n", "implisolid_normals_stats", "implisolid_eval_normals",
+    "implisolid_slab_emit_normals", "implisolid_slab_normals", "implisolid_slab_download_normals",
 ]
 
 # implisolid_progress_callback (include/implisolid.h): verts, n_verts, faces, n_faces,
@@ -174,6 +176,12 @@ def lib():
         "implisolid_jit_compile_points": ([c_char_p, ctypes.c_char_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_double)],
                                           ctypes.c_int64),
         "implisolid_last_build_stats": ([ctypes.POINTER(ctypes.c_double)], c_int),
+        "get_n_size": ([], c_int), "get_n_ptr": ([], c_void_p), "get_n": ([fp, c_int], None),
+        "implisolid_normals_stats": ([ctypes.POINTER(ctypes.c_int64)], c_int),
+        "implisolid_eval_normals": ([fp, ctypes.c_int64, fp, ctypes.POINTER(ctypes.c_int64)], c_int),
+        "implisolid_slab_emit_normals": ([c_void_p, c_void_p], c_int),
+        "implisolid_slab_normals": ([c_void_p], c_void_p),
+        "implisolid_slab_download_normals": ([c_void_p, fp, c_void_p], c_int),
     }
     for name, (args, res) in sig.items():
         try:
@@ -330,12 +338,25 @@ def last_error():
 
 
 # ---- mesh API (implisolid_main.js make_geometry :201-249) -----------------------------------------
-def make_geometry(shape, mc_settings):
-    """Polygonise an MP5 shape; returns (verts float32 [V,3], faces int32 [F,3]) host copies."""
+def _with_normals(mc_settings, normals):
+    """The settings as given, or (normals=True) a copy of them with "normals": {"enabled": 1} merged
+    in: the caller's dict is never changed."""
+    if not normals:
+        return mc_settings
+    d = json.loads(mc_settings.decode() if isinstance(mc_settings, bytes) else mc_settings) \
+        if isinstance(mc_settings, (str, bytes)) else dict(mc_settings)
+    d["normals"] = dict(d["normals"], enabled=1) if isinstance(d.get("normals"), dict) else {"enabled": 1}
+    return d
+
+
+def make_geometry(shape, mc_settings, normals=False):
+    """Polygonise an MP5 shape; returns (verts float32 [V,3], faces int32 [F,3]) host copies, and with
+    normals=True a third array, the per-vertex normals float32 [V,3] of the same build (the
+    "normals" settings key, include/implisolid.h get_n_ptr)."""
     L = lib()
     L.finish_geometry()             # implisolid_main.js:214-217
     _VIEW_GEN[0] += 1   # earlier make_geometry_views arrays are stale from here on
-    L.build_geometry(_s(shape), _s(mc_settings))
+    L.build_geometry(_s(shape), _s(_with_normals(mc_settings, normals)))
     _check()
     nv, nf = L.get_v_size(), L.get_f_size()
     v = np.empty((nv, 3), np.float32)
@@ -344,35 +365,58 @@ def make_geometry(shape, mc_settings):
         L.get_v(v.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), nv)
     if nf:
         L.get_f(f.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), nf)
+    if normals:
+        nn = L.get_n_size()
+        if nn != nv:
+            raise ImplisolidError("make_geometry: %d normals for %d vertices" % (nn, nv))
+        n = np.empty((nn, 3), np.float32)
+        if nn:
+            L.get_n(n.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), nn)
     L.finish_geometry()
-    return v, f
+    return (v, f, n) if normals else (v, f)
+
+
+def normals_stats():
+    """[normals computed, rows that took the -42 branch (|grad| <= 1e-4 or not a number)] of the last build."""
+    out = (ctypes.c_int64 * 2)()
+    if lib().implisolid_normals_stats(out) != 0:
+        raise ImplisolidError(last_error())
+    return int(out[0]), int(out[1])
 
 
 _VIEW_GEN = [0]   # build_geometry calls through make_geometry_views: the generation of its views
 
 
-def make_geometry_views(shape, mc_settings):
+def make_geometry_views(shape, mc_settings, normals=False):
     """build_geometry as the reference's front end reads it (implisolid_main.js:227-237): the mesh is
     left in the library's result buffers (pinned host memory) and returned as read-only numpy views
     over get_v_ptr / get_f_ptr -- no copy.  The views are valid until the next build_geometry or
     finish_geometry (a larger next build frees the pinned buffers they point into): keep them with
     copy_geometry_views(v, f), which refuses stale views; views_current(v) tells whether a view
-    still holds the last build's mesh."""
+    still holds the last build's mesh.  normals=True: a third view, over get_n_ptr, with the same
+    staleness rule."""
     L = lib()
     _VIEW_GEN[0] += 1
     L.finish_geometry()
-    L.build_geometry(_s(shape), _s(mc_settings))
+    L.build_geometry(_s(shape), _s(_with_normals(mc_settings, normals)))
     _check()
     nv, nf = L.get_v_size(), L.get_f_size()
     v = np.ctypeslib.as_array(ctypes.cast(L.get_v_ptr(), ctypes.POINTER(ctypes.c_float)), shape=(nv, 3)) if nv \
         else np.zeros((0, 3), np.float32)
     f = np.ctypeslib.as_array(ctypes.cast(L.get_f_ptr(), ctypes.POINTER(ctypes.c_int32)), shape=(nf, 3)) if nf \
         else np.zeros((0, 3), np.int32)
-    v, f = v.view(_GeometryView), f.view(_GeometryView)
-    for a in (v, f):
+    out = [v, f]
+    if normals:
+        nn = L.get_n_size()
+        if nn != nv:
+            raise ImplisolidError("make_geometry_views: %d normals for %d vertices" % (nn, nv))
+        out.append(np.ctypeslib.as_array(ctypes.cast(L.get_n_ptr(), ctypes.POINTER(ctypes.c_float)), shape=(nn, 3)) if nn
+                   else np.zeros((0, 3), np.float32))
+    out = [a.view(_GeometryView) for a in out]
+    for a in out:
         a.flags.writeable = False
         a._gen = _VIEW_GEN[0]
-    return v, f
+    return tuple(out)
 
 
 class _GeometryView(np.ndarray):
@@ -491,6 +535,19 @@ class ImplicitService:
         if rc != 0:
             raise ImplisolidError(last_error())
         return (f, g) if gradient else f
+
+    def normals(self, pts, return_problems=False):
+        """Surface normals -g / |g| at any number of points (implisolid_eval_normals: the kernel of
+        make_geometry(..., normals=True); rows with |g| <= 1e-4 or a non-finite g are -42 g).  With
+        return_problems: (normals, the number of such rows)."""
+        p = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 3)
+        out = np.empty((p.shape[0], 3), np.float32)
+        bad = ctypes.c_int64(0)
+        fp = ctypes.POINTER(ctypes.c_float)
+        rc = lib().implisolid_eval_normals(p.ctypes.data_as(fp), p.shape[0], out.ctypes.data_as(fp), ctypes.byref(bad))
+        if rc != 0:
+            raise ImplisolidError(last_error())
+        return (out, int(bad.value)) if return_problems else out
 
     def query_implicit_values(self, pts):
         """The reference call sequence set_x / calculate_implicit_values / get_values / unset_x."""
@@ -680,6 +737,20 @@ class Slab:
         self._rc(lib().implisolid_slab_download(self.h, v.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
                                                 f.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ctypes.c_void_p(stream)))
         return v, f
+
+    def emit_normals(self, stream=0):
+        """async, after emit / emit_verts: the normals of the slab's emitted vertices (device)"""
+        self._rc(lib().implisolid_slab_emit_normals(self.h, ctypes.c_void_p(stream)))
+
+    def normals_ptr(self):
+        return lib().implisolid_slab_normals(self.h)
+
+    def download_normals(self, nv, stream=0):
+        """blocking host copy of the normals emit_normals wrote, float32 [nv, 3]"""
+        n = np.empty((nv, 3), np.float32)
+        self._rc(lib().implisolid_slab_download_normals(self.h, n.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                                        ctypes.c_void_p(stream)))
+        return n
 
     def run(self, stream=0):
         """eval + count + emit with the host-set offsets; returns (nv, nf) (blocking)."""

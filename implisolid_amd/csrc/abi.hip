@@ -12,6 +12,7 @@
 #include <thread>
 #include <mutex>
 #include <algorithm>
+#include <functional>
 
 #include "../../include/implisolid.h"
 #include "engine.hpp"
@@ -65,6 +66,11 @@ struct GeometryState {               // state_t, mcc2.cpp:165-193
     bool active = false;
     PinnedVec<float> verts;
     PinnedVec<int32_t> faces;
+    // "normals.enabled" builds: one row per vertex (mcc2.cpp:852-871), beside verts; exposed
+    // (get_n_*) only once the build has ended -- a progress hook's intermediate meshes carry none
+    PinnedVec<float> normals;
+    bool normals_ready = false;
+    int64_t normal_stats[2] = {0, 0};   // normals computed, rows that took the -42 branch
 };
 GeometryState g_state;
 
@@ -171,7 +177,10 @@ std::vector<std::unique_ptr<SlabEngine>> g_slab_engines;
 // polygonize_step_0 on g_devices: balanced cuts (cached per object and grid), every slab evaluated
 // and counted on its device concurrently, vertex / face offsets from the counts (host), emission,
 // and the slabs' meshes copied into the host result at their offsets -- byte-identical to one GPU.
-void multi_device_mc(const Program& prog, const MCSettings& st, PinnedVec<float>& verts, PinnedVec<int32_t>& faces) {
+// normals (optional): each slab engine also computes the normals of the vertices it emitted, on its
+// device, concatenated like the vertices; *problems = their -42 rows
+void multi_device_mc(const Program& prog, const MCSettings& st, PinnedVec<float>& verts, PinnedVec<int32_t>& faces,
+                     PinnedVec<float>* normals = nullptr, int64_t* problems = nullptr) {
     DeviceGuard guard;
     const int n = (int)g_devices.size();
     while ((int)g_slab_engines.size() < n) {
@@ -218,9 +227,12 @@ void multi_device_mc(const Program& prog, const MCSettings& st, PinnedVec<float>
         IMPLI_HIP(hipSetDevice(se.device));
         se.engine->set_offsets((uint32_t)voff[(size_t)r], (uint32_t)foff[(size_t)r]);
         se.engine->emit(nullptr, se.stream);
+        if (normals) se.engine->emit_normals(se.stream);
     }
     verts.resize((size_t)voff[(size_t)n] * 3);
     faces.resize((size_t)foff[(size_t)n] * 3);
+    if (normals) normals->resize((size_t)voff[(size_t)n] * 3);
+    if (problems) *problems = 0;
     for (int r = 0; r < n; ++r) {
         SlabEngine& se = *g_slab_engines[(size_t)r];
         IMPLI_HIP(hipSetDevice(se.device));
@@ -228,6 +240,11 @@ void multi_device_mc(const Program& prog, const MCSettings& st, PinnedVec<float>
         const SlabCounts cr = se.engine->read_counts(se.stream, &of);
         if (of) throw HipError("build_geometry: slab output overflow after sizing");
         se.engine->download(verts.data() + 3 * voff[(size_t)r], faces.data() + 3 * foff[(size_t)r], cr, se.stream);
+        if (normals) {
+            uint64_t bad = 0;
+            se.engine->download_normals(normals->data() + 3 * voff[(size_t)r], cr, se.stream, &bad);
+            if (problems) *problems += (int64_t)bad;
+        }
     }
 }
 
@@ -240,6 +257,15 @@ void grand_algorithm(const char* shape_json, const MCSettings& st, const CallSpe
     Engine& E = engine();
     hipStream_t s = abi_stream();
     E.set_object(prog);
+    // the last build's normals go with its mesh; this build's appear when it ends (normals_done)
+    g_state.normals.resize(0);
+    g_state.normals_ready = false;
+    g_state.normal_stats[0] = g_state.normal_stats[1] = 0;
+    auto normals_done = [&](int64_t problems) {
+        g_state.normal_stats[0] = (int64_t)g_state.normals.size() / 3;
+        g_state.normal_stats[1] = problems;
+        g_state.normals_ready = true;
+    };
     int64_t nv = 0, nf = 0;
     std::unique_ptr<Ob02>& ob_ptr = g_ob02;   // one refinement state, its buffers reused by every build
     // the MC faces' early copy to the host (below); a build that ended in an error left it to finish
@@ -248,15 +274,19 @@ void grand_algorithm(const char* shape_json, const MCSettings& st, const CallSpe
     if (faces_copied) (void)hipEventSynchronize(faces_copied);
     if (!g_devices.empty()) {
         // polygonize_step_0 over several devices: balanced Z-slabs, concatenated on the host
-        multi_device_mc(prog, st, g_state.verts, g_state.faces);
+        const bool refine = st.overall_repeats > 0 && (st.vresampl_iters > 0 || st.projection || st.subdiv);
+        // the MC mesh's normals come from the slabs' devices; a refined mesh's from the loop's (below)
+        const bool slab_normals = st.normals && !refine;
+        int64_t problems = 0;
+        multi_device_mc(prog, st, g_state.verts, g_state.faces, slab_normals ? &g_state.normals : nullptr, &problems);
         nv = (int64_t)g_state.verts.size() / 3;
         nf = (int64_t)g_state.faces.size() / 3;
-        const bool refine = st.overall_repeats > 0 && (st.vresampl_iters > 0 || st.projection || st.subdiv);
         if (!refine) {
             g_last_refined = false;
             send_mesh_back_to_client(nullptr, cs);   // mcc2.cpp:351
             // the repeats of an empty loop still report after their (empty) resampling (:372)
             for (int rep = 0; rep < st.overall_repeats; ++rep) send_mesh_back_to_client(nullptr, cs);
+            if (st.normals) normals_done(problems);
             g_state.active = true;
             return;
         }
@@ -274,17 +304,22 @@ void grand_algorithm(const char* shape_json, const MCSettings& st, const CallSpe
         const bool refine = st.overall_repeats > 0 && (st.vresampl_iters > 0 || st.projection || st.subdiv);
         if (!refine) {   // the MC mesh is the result: straight into the library's pinned result buffers
             roctxRangePush("marching cubes");
+            const std::function<float*(int64_t)> normals_host = [](int64_t v) {
+                g_state.normals.resize((size_t)v * 3);
+                return g_state.normals.data();
+            };
             E.marching_cubes_to_host(s, abi_copy_stream(), [](int64_t v, int64_t f, float** hv, int32_t** hf) {
                 g_state.verts.resize((size_t)v * 3);
                 g_state.faces.resize((size_t)f * 3);
                 *hv = g_state.verts.data();
                 *hf = g_state.faces.data();
-            });
+            }, st.normals ? &normals_host : nullptr);
             roctxRangePop();
             g_last_refined = false;
             send_mesh_back_to_client(nullptr, cs);   // mcc2.cpp:351
             // the repeats of an empty loop still report after their (empty) resampling (:372)
             for (int rep = 0; rep < st.overall_repeats; ++rep) send_mesh_back_to_client(nullptr, cs);
+            if (st.normals) normals_done((int64_t)E.normal_problems_host());
             g_state.active = true;
             return;
         }
@@ -337,6 +372,10 @@ void grand_algorithm(const char* shape_json, const MCSettings& st, const CallSpe
     nv = ob.n_verts();
     nf = ob.n_faces();
     g_state.verts.resize((size_t)nv * 3);
+    if (st.normals) {   // one more pass over the final vertices, behind the loop's last step; fetch() drains s
+        g_state.normals.resize((size_t)nv * 3);
+        ob.normals_to_host(g_state.normals.data());
+    }
     if (faces_early && (int64_t)g_state.faces.size() == 3 * nf) {
         ob.fetch(g_state.verts.data(), nullptr);
         IMPLI_HIP(hipEventSynchronize(faces_copied));
@@ -346,6 +385,7 @@ void grand_algorithm(const char* shape_json, const MCSettings& st, const CallSpe
         ob.fetch(g_state.verts.data(), g_state.faces.data());
     }
     ob.capture_replace = true;
+    if (st.normals) normals_done((int64_t)E.normal_problems_host());
     g_pointsets_dirty = true;              // copied to the host when asked for
     g_state.active = true;                 // polygonize_terminate, ob02:163-176
 }
@@ -481,6 +521,24 @@ void get_f(int* f_out, int fcount) {
 void* get_v_ptr(void) { return g_state.verts.data(); }
 void* get_f_ptr(void) { return g_state.faces.data(); }
 
+int get_n_size(void) { return g_state.normals_ready ? (int)(g_state.normals.size() / 3) : 0; }
+void* get_n_ptr(void) { return get_n_size() ? g_state.normals.data() : nullptr; }
+void get_n(float* n_out, int vcount) {
+    const size_t n = (size_t)get_n_size() * 3;
+    if (n) std::memcpy(n_out, g_state.normals.data(), n * sizeof(float));
+    if ((size_t)vcount * 3 != n) std::fprintf(stderr, "sizes dont match: %g %d\n", (double)n / 3., vcount);
+}
+int implisolid_normals_stats(int64_t out[2]) {
+    g_last_error.clear();
+    if (!out) {
+        report("implisolid_normals_stats: null output", false);
+        return -1;
+    }
+    out[0] = g_state.normals_ready ? g_state.normal_stats[0] : 0;
+    out[1] = g_state.normals_ready ? g_state.normal_stats[1] : 0;
+    return 0;
+}
+
 void finish_geometry(void) { g_state.active = false; }
 
 // ---- direct evaluation ------------------------------------------------------------------------
@@ -568,6 +626,33 @@ int implisolid_eval_points(const float* xyz, int64_t n, float* f_out, float* gra
         if (f_out) IMPLI_HIP(hipMemcpyAsync(f_out, df.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
         if (grad_out) IMPLI_HIP(hipMemcpyAsync(grad_out, dg.p, (size_t)n * 12, hipMemcpyDeviceToHost, s));
         IMPLI_HIP(hipStreamSynchronize(s));
+    } catch (const std::exception& e) {
+        report(e.what(), false);
+        return -1;
+    }
+    return 0;
+}
+
+int implisolid_eval_normals(const float* xyz, int64_t n, float* out, int64_t* problems) {
+    if (!g_eval.has_object) {
+        report("Error: You need to set_x() and set_object() first.", false);
+        return -1;
+    }
+    if (problems) *problems = 0;
+    if (n <= 0) return 0;
+    if (!xyz || !out) {
+        report("implisolid_eval_normals: null points or output", false);
+        return -1;
+    }
+    try {
+        Engine& E = engine();
+        hipStream_t s = abi_stream();
+        DevBuf& dx = E.scratch(0);
+        dx.reserve((size_t)n * 12);
+        IMPLI_HIP(hipMemcpyAsync(dx.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, s));
+        (void)E.normals_to_host(dx.as<float>(), n, out, s);
+        IMPLI_HIP(hipStreamSynchronize(s));
+        if (problems) *problems = (int64_t)E.normal_problems_host();
     } catch (const std::exception& e) {
         report(e.what(), false);
         return -1;
@@ -1029,6 +1114,18 @@ int implisolid_slab_download(implisolid_slab* s, float* verts, int32_t* faces, v
         const SlabCounts c = s->engine.read_counts((hipStream_t)stream, &of);
         if (of) throw HipError("slab output overflowed; call implisolid_slab_counts and emit again");
         s->engine.download(verts, faces, c, (hipStream_t)stream);
+    } catch (const std::exception& e) {
+        report(e.what(), false);
+        return -1;
+    }
+    return 0;
+}
+int implisolid_slab_emit_normals(implisolid_slab* s, void* stream) { SLAB_TRY(s->engine.emit_normals((hipStream_t)stream)) }
+float* implisolid_slab_normals(implisolid_slab* s) { return s->engine.d_normals(); }
+int implisolid_slab_download_normals(implisolid_slab* s, float* out, void* stream) {
+    try {
+        const SlabCounts c = s->engine.read_counts((hipStream_t)stream, nullptr);
+        s->engine.download_normals(out, c, (hipStream_t)stream);
     } catch (const std::exception& e) {
         report(e.what(), false);
         return -1;

@@ -310,7 +310,7 @@ Engine::~Engine() {
     if (ev_counts_) (void)hipEventDestroy(ev_counts_);
     if (ev_verts_) (void)hipEventDestroy(ev_verts_);
     DevBuf* all[] = {&offsets_, &cmodes_, &ccls_, &clist_, &modes_, &cls_, &fill_, &blist_, &prog_, &rabbit_, &cases_, &field_, &signs_, &scan_blk_, &unit_cnt_, &unit_part_, &unit_cmask_, &ulist_, &upart_, &umark_, &counters_, &lmodes_, &claimed_, &vid_,
-                     &records_, &verts_, &faces_};
+                     &records_, &verts_, &faces_, &normals_, &nproblems_};
     for (auto* b : all) b->release();
     for (auto& b : scratch_) b.release();
     // the buffers went to the pool (no hipFree and its implicit synchronisation): the modules'
@@ -736,7 +736,8 @@ SlabCounts Engine::marching_cubes(hipStream_t s) {
 }
 
 SlabCounts Engine::marching_cubes_to_host(hipStream_t s, hipStream_t cs,
-                                          const std::function<void(int64_t, int64_t, float**, int32_t**)>& host) {
+                                          const std::function<void(int64_t, int64_t, float**, int32_t**)>& host,
+                                          const std::function<float*(int64_t)>* normals_host) {
     if (!ev_counts_) IMPLI_HIP(hipEventCreateWithFlags(&ev_counts_, hipEventDisableTiming));
     if (!ev_verts_) IMPLI_HIP(hipEventCreateWithFlags(&ev_verts_, hipEventDisableTiming));
     hcounters_.reserve(kCounterWords * sizeof(uint32_t));
@@ -762,6 +763,7 @@ SlabCounts Engine::marching_cubes_to_host(hipStream_t s, hipStream_t cs,
         float* hv = nullptr;
         int32_t* hf = nullptr;
         host(c.n_verts(), c.n_faces(), &hv, &hf);
+        if (normals_host) (void)normals_to_host(verts_.as<float>(), c.n_verts(), (*normals_host)(c.n_verts()), s);
         download(hv, hf, c, s);
         return c;
     }
@@ -772,6 +774,8 @@ SlabCounts Engine::marching_cubes_to_host(hipStream_t s, hipStream_t cs,
         IMPLI_HIP(hipStreamWaitEvent(cs, ev_verts_, 0));
         IMPLI_HIP(hipMemcpyAsync(hv, verts_.p, (size_t)c.n_verts() * 12, hipMemcpyDeviceToHost, cs));
     }
+    // the normals kernel on s behind the face pass, while the vertices' copy runs on cs
+    if (normals_host) (void)normals_to_host(verts_.as<float>(), c.n_verts(), (*normals_host)(c.n_verts()), s);
     if (c.n_faces()) IMPLI_HIP(hipMemcpyAsync(hf, faces_.p, (size_t)c.n_faces() * 12, hipMemcpyDeviceToHost, s));
     IMPLI_HIP(hipMemcpyAsync(h + kOverflowWord, counters_.as<uint32_t>() + kOverflowWord, sizeof(uint32_t),
                              hipMemcpyDeviceToHost, s));
@@ -817,6 +821,61 @@ void Engine::eval_points(const float* d_xyz, int64_t n, float* d_f, float* d_gra
     }
     launch_eval_points(prog_.as<Program>(), depth_, rabbit_.as<float>(), d_xyz, n, d_f, d_grad, s);
     IMPLI_HIP(hipGetLastError());
+}
+
+bool Engine::vertex_normals(const float* d_pts, int64_t n, const uint32_t* d_counters, float* d_normals,
+                            unsigned long long* d_problems, hipStream_t s) {
+    if (!have_object_) throw InputError("engine: no object set");
+    if (n <= 0) return false;
+    if (const TreeJit::PointKernels* pk = point_jit(s)) {
+        const float* m = d_mats();
+        const float* tab = rabbit_.as<float>();
+        void* args[] = {&m, &tab, &d_pts, &n, &d_counters, &d_normals, &d_problems};
+        TreeJit::launch(pk->vnormals, (unsigned)((n + 255) / 256), args, s, "impli_pt_vertex_normals");
+        IMPLI_HIP(hipGetLastError());
+        return true;
+    }
+    launch_vertex_normals(prog_.as<Program>(), depth_, rabbit_.as<float>(), d_pts, n, d_counters, d_normals, d_problems, s);
+    IMPLI_HIP(hipGetLastError());
+    return false;
+}
+
+unsigned long long* Engine::d_normal_problems() {
+    nproblems_.reserve(sizeof(unsigned long long));
+    return nproblems_.as<unsigned long long>();
+}
+
+void Engine::emit_normals(hipStream_t s) {
+    if (!have_grid_ || probe_only_) throw InputError("engine: emit_normals needs a slab's emitted vertices");
+    normals_.reserve((size_t)std::max<int64_t>(cap_v_, 1) * 3 * sizeof(float));
+    unsigned long long* prob = d_normal_problems();
+    IMPLI_HIP(hipMemsetAsync(prob, 0, sizeof(unsigned long long), s));
+    // every vertex the slab emitted (counter words [2] - [5], read on the device: no host round
+    // trip), the grid sized by the vertex buffer's capacity, which the emission never writes past
+    (void)vertex_normals(verts_.as<float>(), cap_v_, counters_.as<uint32_t>(), normals_.as<float>(), prob, s);
+}
+
+void Engine::download_normals(float* out, const SlabCounts& c, hipStream_t s, uint64_t* problems) {
+    if (!normals_.p || normals_.bytes < (size_t)c.n_verts() * 12) throw InputError("engine: no normals emitted for this mesh");
+    if (c.n_verts()) IMPLI_HIP(hipMemcpyAsync(out, normals_.p, (size_t)c.n_verts() * 12, hipMemcpyDeviceToHost, s));
+    hproblems_.reserve(sizeof(unsigned long long));
+    IMPLI_HIP(hipMemcpyAsync(hproblems_.p, d_normal_problems(), sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    IMPLI_HIP(hipStreamSynchronize(s));
+    if (problems) *problems = normal_problems_host();
+}
+
+bool Engine::normals_to_host(const float* d_pts, int64_t n, float* h_out, hipStream_t s) {
+    hproblems_.reserve(sizeof(unsigned long long));
+    unsigned long long* prob = d_normal_problems();
+    IMPLI_HIP(hipMemsetAsync(prob, 0, sizeof(unsigned long long), s));
+    bool jit = false;
+    if (n > 0) {
+        normals_.reserve((size_t)n * 12);
+        jit = vertex_normals(d_pts, n, nullptr, normals_.as<float>(), prob, s);
+        IMPLI_HIP(hipMemcpyAsync(h_out, normals_.p, (size_t)n * 12, hipMemcpyDeviceToHost, s));
+    }
+    IMPLI_HIP(hipMemcpyAsync(hproblems_.p, prob, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    return jit;
 }
 
 }  // namespace impli

@@ -126,8 +126,11 @@ public:
     // the emission kernels run, `host(nv, nf, &verts, &faces)` then sizes the host result, the
     // vertices' copy runs on copy_stream beside the face pass and the faces' copy follows it on
     // stream (blocking until both have landed)
+    // normals_host (optional): the mesh's per-vertex normals as well -- it sizes the host array for
+    // nv vertices; the normals kernel follows the face pass on stream, beside the vertices' copy
     SlabCounts marching_cubes_to_host(hipStream_t stream, hipStream_t copy_stream,
-                                      const std::function<void(int64_t, int64_t, float**, int32_t**)>& host);
+                                      const std::function<void(int64_t, int64_t, float**, int32_t**)>& host,
+                                      const std::function<float*(int64_t)>* normals_host = nullptr);
 
     // this object's state for the merged launches of an object stream (kernels.hpp ObjArgs); the
     // pruned path after one eval_field (its unit marks), valid until the buffers grow
@@ -137,6 +140,27 @@ public:
 
     // direct evaluation at device points
     void eval_points(const float* d_xyz, int64_t n, float* d_f, float* d_grad, hipStream_t stream);
+    // per-vertex normals (mcc2.cpp:852-871: -g / |g|, or -42 g where |g| <= 1e-4) at n device points,
+    // asynchronous on `stream`: the object's point module when loaded, else the interpreter kernel.
+    // *d_problems (zeroed by the caller) gains the -42 rows.  d_counters (nullable): a counter block
+    // whose emitted vertex count bounds the pass instead of n (n then sizes the grid).  Returns
+    // whether the point module ran.
+    bool vertex_normals(const float* d_pts, int64_t n, const uint32_t* d_counters, float* d_normals,
+                        unsigned long long* d_problems, hipStream_t stream);
+    // the normals of this slab's emitted vertices (after emit / emit_verts, stream-ordered: the count
+    // is read on the device), into a buffer of the engine's; d_normals() is valid after the call
+    void emit_normals(hipStream_t stream);
+    float* d_normals() const { return normals_.as<float>(); }
+    // [0] the -42 rows of the last emit_normals / normals pass (device, unsigned long long)
+    unsigned long long* d_normal_problems();
+    // blocking copy of the slab's normals (c.n_verts() rows) and of their -42 count
+    void download_normals(float* out, const SlabCounts& c, hipStream_t stream, uint64_t* problems = nullptr);
+    // the normals of n device points (host-known count) straight to host memory, all enqueued on
+    // `stream` without a synchronisation: count reset, kernel, the copy of the normals into h_out
+    // and of the -42 count into pinned memory (normal_problems_host() once the stream has drained).
+    // Returns whether the point module ran.
+    bool normals_to_host(const float* d_pts, int64_t n, float* h_out, hipStream_t stream);
+    uint64_t normal_problems_host() const { return hproblems_.p ? *hproblems_.as<unsigned long long>() : 0; }
 
     const GridDesc& grid() const { return grid_; }
     float* d_verts() const { return verts_.as<float>(); }
@@ -220,6 +244,8 @@ private:
     hipEvent_t ev_counts_ = nullptr, ev_verts_ = nullptr;   // marching_cubes_to_host
     DevBuf prog_, rabbit_, cases_;
     DevBuf offsets_, cmodes_, ccls_, clist_, modes_, cls_, fill_, blist_, field_, signs_, scan_blk_, unit_cnt_, unit_part_, unit_cmask_, ulist_, upart_, umark_, counters_, lmodes_, claimed_, vid_, records_, verts_, faces_;
+    DevBuf normals_, nproblems_;   // the normals passes' output (allocated on first use) and their -42 count
+    HostBuf hproblems_;            // ... and that count's pinned landing zone
     int64_t cap_v_ = 0, cap_f_ = 0, cap_rec_ = 0;
     bool timing_ = false;
     hipEvent_t ev_[11] = {};   // 0-8 phase boundaries, 9 after the coarse pass, 10 after refine

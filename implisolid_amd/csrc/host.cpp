@@ -116,6 +116,10 @@ MCSettings parse_mc_settings(const char* text) {
     s.subdiv = read_bool("subdiv.enabled", true, "subdiv.enable");
     s.post_subdiv_noise = d.get_float("debug.post_subdiv_noise", 0.01f);
     s.overall_repeats = d.get_int("overall_repeats", 1);
+    {   // additive key, read as the reference reads its ints (true / false are no ints: the default)
+        const int v = d.get_int("normals.enabled", -1);
+        s.normals = v != -1 && v != 0;
+    }
     s.ignore_root_matrix = d.get_bool("ignore_root_matrix", false);
     if (s.qem && !s.projection) why += "  err7 (qem needs projection)";
     if (s.resolution > 65535) why += "  resolution exceeds the reference's dim_t";

@@ -20,6 +20,7 @@ struct MCSettings {
     bool projection = false;
     bool subdiv = true;
     float post_subdiv_noise = 0.01f;
+    bool normals = false;   // additive: "normals.enabled", per-vertex normals with the mesh (no reference key)
 };
 
 // Errors the reference reports with abort() / clog.  The C ABI decides what to do with them

@@ -655,7 +655,8 @@ void TreeJit::build(Slot* slot) {
                      hipModuleGetFunction(&pk.early2, slot->mod, "impli_pt_project_early2") == hipSuccess &&
                      hipModuleGetFunction(&pk.late, slot->mod, "impli_pt_project_late") == hipSuccess &&
                      hipModuleGetFunction(&pk.normals, slot->mod, "impli_pt_normals_at") == hipSuccess &&
-                     hipModuleGetFunction(&pk.points, slot->mod, "impli_pt_points") == hipSuccess;
+                     hipModuleGetFunction(&pk.points, slot->mod, "impli_pt_points") == hipSuccess &&
+                     hipModuleGetFunction(&pk.vnormals, slot->mod, "impli_pt_vertex_normals") == hipSuccess;
             return ok;
         };
         bool ok = load(code);
@@ -1117,7 +1118,10 @@ std::string TreeJit::point_source(const Program& p, bool bake) {
       << "    impli::ob::normals_at_body(JitPt{M, tab}, P, rng, G, pend, mode);\n}\n"
       << "extern \"C\" __global__ __launch_bounds__(256) void impli_pt_points(const float* __restrict__ M, const float* __restrict__ tab,\n"
       << "    const float* xyz, int64_t n, float* f, float* grad) {\n"
-      << "    impli::ob::points_body(JitPt{M, tab}, xyz, n, f, grad);\n}\n";
+      << "    impli::ob::points_body(JitPt{M, tab}, xyz, n, f, grad);\n}\n"
+      << "extern \"C\" __global__ __launch_bounds__(256)" << occ_fg << " void impli_pt_vertex_normals(const float* __restrict__ M, const float* __restrict__ tab,\n"
+      << "    const float* P, int64_t n, const uint32_t* counters, float* N, unsigned long long* problems) {\n"
+      << "    impli::ob::vertex_normals_body(JitPt{M, tab}, P, impli::ob::counted_points(counters, n), N, problems);\n}\n";
     return s.str();
 }
 

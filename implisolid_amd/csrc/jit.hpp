@@ -47,7 +47,8 @@ public:
     };
     struct PointKernels {                 // the point module (ob02_device.hpp bodies)
         hipFunction_t cnormals = nullptr, prep = nullptr, early = nullptr, early2 = nullptr, late = nullptr,
-                      normals = nullptr, points = nullptr;   // early2: the early search with 2 lanes per face
+                      normals = nullptr, points = nullptr,   // early2: the early search with 2 lanes per face
+                      vnormals = nullptr;                    // the mesh's per-vertex normals
     };
     enum Kind { kBricks = 0, kPoints = 1 };
     // One compiled module (one source on one device).  `ready` is set (release) once `k` holds the

@@ -45,6 +45,11 @@ void launch_eval_bricks_interp(const Program* d_prog, int depth, const float* d_
 void launch_signs_from_field(const GridDesc& g, const float* d_field, uint64_t* d_signs, hipStream_t s);
 void launch_eval_points(const Program* d_prog, int depth, const float* d_rabbit, const float* d_xyz, int64_t n,
                         float* d_f, float* d_grad /* nullable: values only */, hipStream_t s);
+// per-vertex normals -g / |g| at n points (ob02.hip k_vertex_normals, the interpreter form of
+// ob02_device.hpp vertex_normals_body); d_counters (nullable): a slab's counter block, whose emitted
+// vertex count then bounds the pass (n: the capacity the grid covers); *d_problems += the -42 rows
+void launch_vertex_normals(const Program* d_prog, int depth, const float* d_rabbit, const float* d_pts, int64_t n,
+                           const uint32_t* d_counters, float* d_normals, unsigned long long* d_problems, hipStream_t s);
 // diagnostics: glibc sinf (0) / atanf (1) / atan2f (2) restatements on device operands
 void launch_libm_probe(int which, const float* d_a, const float* d_b, int64_t n, float* d_out, hipStream_t s);
 void launch_cos_probe(const double* d_a, int64_t n, double* d_out, hipStream_t s);

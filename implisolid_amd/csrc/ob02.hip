@@ -618,6 +618,13 @@ __global__ __launch_bounds__(256) void k_normals_at(const Program* __restrict__ 
                                                     float* __restrict__ G, const uint32_t* __restrict__ pend, int mode) {
     normals_at_body(InterpPt<D>{prog, tab}, P, rng, G, pend, mode);
 }
+template <int D>
+__global__ __launch_bounds__(256) void k_vertex_normals(const Program* __restrict__ prog, const float* __restrict__ tab,
+                                                        const float* __restrict__ P, int64_t n,
+                                                        const uint32_t* __restrict__ counters, float* __restrict__ N,
+                                                        unsigned long long* __restrict__ problems) {
+    vertex_normals_body(InterpPt<D>{prog, tab}, P, counted_points(counters, n), N, problems);
+}
 
 // ---- step 1 ----------------------------------------------------------------------------------
 __device__ __forceinline__ float kij(int64_t i, int64_t j, const float* __restrict__ C, const float* __restrict__ N);
@@ -1965,6 +1972,13 @@ void pert_draw_ahead() {
 
 }  // namespace
 
+void launch_vertex_normals(const Program* d_prog, int depth, const float* d_rabbit, const float* d_pts, int64_t n,
+                           const uint32_t* d_counters, float* d_normals, unsigned long long* d_problems, hipStream_t s) {
+    if (n <= 0) return;
+    DEPTH_LAUNCH(depth, k_vertex_normals, blocks_for(n), 256, s, d_prog, d_rabbit, d_pts, n, d_counters, d_normals,
+                 d_problems);
+}
+
 // The perturbation table of a face count on one device, shared by every Ob02 of the process
 // (the shards of one process, the builds of one engine): drawn once on a host thread, copied once
 // into pinned memory and uploaded once, on the stream of the Ob02 that first needs it; `ready`
@@ -2832,6 +2846,10 @@ void Ob02::subdivide(float amplitude) {   // my_subdiv_ (centroids_projection.cp
         whole_ranges();
     }
     add_rand_noise(amplitude);
+}
+
+void Ob02::normals_to_host(float* h_out) {
+    if (E.normals_to_host(verts_.as<float>(), nv, h_out, s)) ++jit_launches_;
 }
 
 void Ob02::fetch(float* verts, int32_t* faces) {

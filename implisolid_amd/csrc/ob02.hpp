@@ -73,6 +73,9 @@ public:
     void subdivide(float amplitude);
     int64_t n_verts() const { return nv; }
     int64_t n_faces() const { return nf; }
+    // the per-vertex normals of the current vertices (mcc2.cpp:852-871) straight to host memory,
+    // enqueued on the loop's stream behind its last step (Engine::normals_to_host; no synchronisation)
+    void normals_to_host(float* h_out);
     // blocking copy of the current mesh to host
     void fetch(float* verts, int32_t* faces);
     // host copies of the point sets stored since load_mesh (blocking)

@@ -6,6 +6,7 @@
 //   project_*_body         set_centers_on_surface cp:421-1214 + bisection bisection.hpp:117-459
 //   normals_at_body        the QEM normals at the projected centroids (qem.hpp:256-316)
 //   points_body            direct evaluation (mcc2.cpp:815-911)
+//   vertex_normals_body    the mesh's per-vertex normals (mcc2.cpp:852-871)
 #pragma once
 #include "ifunc_device.hpp"
 
@@ -629,6 +630,38 @@ __device__ __forceinline__ void points_body(const Ev& ev, const float* __restric
     } else {
         f[i] = ev.f(x, y, z);
     }
+}
+
+// per-vertex surface normals (mcc2.cpp:852-871, calculate_implicit_gradients with
+// normalize_and_invert): N = g * factor, factor = -1 / |g| where |g| > 0.0001, else -42; one lane per
+// point.  The reference compares the float norm with the double 0.0001 and divides in double before
+// rounding to float: norm > 0.0001f decides the same for every float, and -1.0f / norm (IEEE
+// division) is that quotient (tests/test_cpu_normals.py checks both).  A NaN norm fails the
+// comparison, so a non-finite gradient takes the -42 branch and stays non-finite.  The -42 rows are
+// counted per wave (ballot) with one atomic per wave that has any.
+template <class Ev>
+__device__ __forceinline__ void vertex_normals_body(const Ev& ev, const float* __restrict__ P, int64_t n,
+                                                    float* __restrict__ N, unsigned long long* __restrict__ problems) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    bool bad = false;
+    if (i < n) {
+        V3 g;
+        (void)ev.fg(P[3 * i], P[3 * i + 1], P[3 * i + 2], g);
+        const float norm = norm2f(g.x, g.y, g.z);
+        bad = !(norm > 0.0001f);
+        const float factor = bad ? -42.0f : -1.0f / norm;
+        N[3 * i] = g.x * factor; N[3 * i + 1] = g.y * factor; N[3 * i + 2] = g.z * factor;
+    }
+    const uint64_t m = (uint64_t)__ballot(bad);
+    if (m && (threadIdx.x & 63) == 0) atomicAdd(problems, (unsigned long long)__popcll(m));
+}
+
+// the number of points of a pass whose count lives on the device: a slab's emitted vertices
+// (counter words [2] - [5], mc_types.hpp), at most the `cap` the grid was sized for
+__device__ __forceinline__ int64_t counted_points(const uint32_t* __restrict__ counters, int64_t cap) {
+    if (!counters) return cap;
+    const int64_t c = (int64_t)(counters[2] - counters[5]);
+    return c < cap ? c : cap;
 }
 
 }  // namespace ob

@@ -51,6 +51,30 @@ void finish_geometry(void);
 void* get_f_ptr(void);
 /* mcc2.cpp:97 / :515-519  library-owned float32 xyz */
 void* get_v_ptr(void);
+/* Additive: per-vertex surface normals with the mesh, from the same build.  The mc_settings key
+   "normals": {"enabled": 1} (an int, read like projection.enabled: true / false are not ints and
+   leave the default 0; the reference ignores the key) makes build_geometry evaluate the implicit
+   gradient at the final vertices -- after the last step of the OB02 loop, or at the marching-cubes
+   vertices when nothing refines them -- and apply what calculate_implicit_gradients(true) applies,
+   mcc2.cpp:852-871: norm = sqrt(x x + y y + z z); n = g * (norm > 0.0001 ? -1 / norm : -42).  This
+   replaces the reference front end's second round trip (implisolid_main.js:335-368 and :583-622:
+   set_object, set_x with fewer than 50000 points, calculate_implicit_gradients, get_gradients_ptr;
+   its author's note at :551 asks for "the normals in the same request").  Names as the reference
+   names get_v_*:
+     get_n_size  the vertex count if the last build computed normals, else 0
+     get_n_ptr   library-owned float32 xyz per vertex, valid like get_v_ptr's until the next build;
+                 NULL when the size is 0
+     get_n       copy 3*vcount floats
+   A build without the key exposes nothing, also directly after one that had normals.  Intermediate
+   meshes carry no normals: inside a progress callback get_n_size() is 0; the final mesh has them.
+   With implisolid_set_devices each slab's device computes the normals of the vertices it emitted
+   (after a refinement: the device the loop ran on).  The object stream (implisolid_batch_*) ignores
+   the key.  implisolid_normals_stats: out = [normals computed, rows that took the -42 branch] of the
+   last build; 0, or -1 with implisolid_last_error(). */
+int get_n_size(void);
+void* get_n_ptr(void);
+void get_n(float* n_out, int vcount);
+int implisolid_normals_stats(int64_t out[2]);
 
 /* ---- direct evaluation API ------------------------------------------------------------------ */
 /* mcc2.cpp:106 / :726-741  returns 1, or 0 if an object is already set */
@@ -140,6 +164,11 @@ void implisolid_ob02_profile(int on);
 int implisolid_last_build_stats(double out[13]);
 /* evaluate n >= 0 points (no 50k limit) of the current set_object(); grad may be NULL */
 int implisolid_eval_points(const float* xyz, int64_t n, float* f_out, float* grad_out);
+/* Additive: the normals of n >= 0 points of the current set_object() (no 50k limit), by the kernel
+   build_geometry's "normals" key runs: out receives 3n floats, -g / |g| per mcc2.cpp:852-871 (-42 g
+   where |g| <= 0.0001, or is not a number); *problems (may be NULL) the number of such rows.
+   calculate_implicit_gradients keeps its own host loop.  0, or -1 with implisolid_last_error(). */
+int implisolid_eval_normals(const float* xyz, int64_t n, float* out, int64_t* problems);
 /* Additive, diagnostics: the device restatements of glibc 2.35 sinf (which 0: out = sinf(a)),
    atanf (1) and atan2f (2: out = atan2f(a, b)) that the screw family calls (screw.hpp:20-36,
    std::sin / std::atan2 on floats), on n host operands; 0 or -1 with implisolid_last_error() */
@@ -216,6 +245,13 @@ int implisolid_slab_copy_counts(implisolid_slab* s, uint32_t* d_dst, void* strea
 int implisolid_slab_set_offsets(implisolid_slab* s, uint32_t voff, uint32_t foff);
 /* blocking copy of the slab's emitted vertices (3*V floats) and faces (3*F ints, global ids) */
 int implisolid_slab_download(implisolid_slab* s, float* verts, int32_t* faces, void* stream);   /* R, res, cz0, cz1, cz_emit, fz0, fz1, depth */
+/* Additive: the normals (mcc2.cpp:852-871, as get_n_ptr's) of the vertices the slab emitted, the rows
+   implisolid_slab_download returns.  emit_normals is stream-ordered after emit / emit_verts (the
+   vertex count is read on the device); slab_normals is the device array (valid after emit_normals,
+   until the slab's buffers grow); download_normals blocks and copies 3*V floats. */
+int implisolid_slab_emit_normals(implisolid_slab* s, void* stream);
+float* implisolid_slab_normals(implisolid_slab* s);
+int implisolid_slab_download_normals(implisolid_slab* s, float* out, void* stream);
 float* implisolid_slab_verts(implisolid_slab* s);     /* device pointers */
 int32_t* implisolid_slab_faces(implisolid_slab* s);
 float* implisolid_slab_field(implisolid_slab* s);
@@ -282,6 +318,7 @@ int implisolid_slab_brick_stats(implisolid_slab* s, int64_t out[3]);
  *     into `stream`.
  * run is async on `stream`; counts and download block.  info = {objects, streams, graphs (1/0),
  * merged (1/0)} and the JIT compile seconds. */
+/* The mc settings' "normals" key is ignored here: an object stream computes no normals. */
 typedef struct implisolid_batch implisolid_batch;
 implisolid_batch* implisolid_batch_create(const char* const* shapes, int n, const char* mc_json, int n_streams);
 int implisolid_batch_run(implisolid_batch* b, void* stream);
