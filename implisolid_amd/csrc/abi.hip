@@ -179,8 +179,8 @@ std::vector<std::unique_ptr<SlabEngine>> g_slab_engines;
 // and the slabs' meshes copied into the host result at their offsets -- byte-identical to one GPU.
 // normals (optional): each slab engine also computes the normals of the vertices it emitted, on its
 // device, concatenated like the vertices; *problems = their -42 rows
-void multi_device_mc(const Program& prog, const MCSettings& st, PinnedVec<float>& verts, PinnedVec<int32_t>& faces,
-                     PinnedVec<float>* normals = nullptr, int64_t* problems = nullptr) {
+void multi_device_mc(const Program& prog, const ObjectTables& tabs, const MCSettings& st, PinnedVec<float>& verts,
+                     PinnedVec<int32_t>& faces, PinnedVec<float>* normals = nullptr, int64_t* problems = nullptr) {
     DeviceGuard guard;
     const int n = (int)g_devices.size();
     while ((int)g_slab_engines.size() < n) {
@@ -197,15 +197,16 @@ void multi_device_mc(const Program& prog, const MCSettings& st, PinnedVec<float>
     std::string key((const char*)&prog, sizeof(Program));
     key.append((const char*)&st.resolution, sizeof st.resolution).append((const char*)st.box, sizeof st.box);
     key.append((const char*)&n, sizeof n);
+    key.append((const char*)tabs.data.data(), tabs.data.size() * sizeof(float));   // sdf_3d tables: part of the object
     if (key != cut_key) {
         IMPLI_HIP(hipSetDevice(g_devices[0]));
-        cuts = balance_cuts(prog, st.resolution, st.box, n, g_slab_engines[0]->stream);
+        cuts = balance_cuts(prog, st.resolution, st.box, n, g_slab_engines[0]->stream, &tabs);
         cut_key = key;
     }
     for (int r = 0; r < n; ++r) {   // eval + count, all devices in flight
         SlabEngine& se = *g_slab_engines[(size_t)r];
         IMPLI_HIP(hipSetDevice(se.device));
-        se.engine->set_object(prog);
+        se.engine->set_object(prog, nullptr, &tabs);   // every device builds its own table arena
         se.engine->set_slab(st.resolution, st.box, SlabRange{cuts[(size_t)r], cuts[(size_t)r + 1], 0});
         se.engine->eval_field(se.stream);
         se.engine->count(se.stream);
@@ -253,10 +254,11 @@ void grand_algorithm(const char* shape_json, const MCSettings& st, const CallSpe
         report("build_geometry() called in a bad state.", false);
         return;
     }
-    Program prog = compile_mp5(shape_json, st.ignore_root_matrix);
+    ObjectTables tabs;
+    Program prog = compile_mp5(shape_json, st.ignore_root_matrix, &tabs);
     Engine& E = engine();
     hipStream_t s = abi_stream();
-    E.set_object(prog);
+    E.set_object(prog, nullptr, &tabs);
     // the last build's normals go with its mesh; this build's appear when it ends (normals_done)
     g_state.normals.resize(0);
     g_state.normals_ready = false;
@@ -278,7 +280,7 @@ void grand_algorithm(const char* shape_json, const MCSettings& st, const CallSpe
         // the MC mesh's normals come from the slabs' devices; a refined mesh's from the loop's (below)
         const bool slab_normals = st.normals && !refine;
         int64_t problems = 0;
-        multi_device_mc(prog, st, g_state.verts, g_state.faces, slab_normals ? &g_state.normals : nullptr, &problems);
+        multi_device_mc(prog, tabs, st, g_state.verts, g_state.faces, slab_normals ? &g_state.normals : nullptr, &problems);
         nv = (int64_t)g_state.verts.size() / 3;
         nf = (int64_t)g_state.faces.size() / 3;
         if (!refine) {
@@ -548,8 +550,9 @@ int set_object(const char* shape_json, bool ignore_root_matrix) {
         return 0;
     }
     try {
-        Program p = compile_mp5(shape_json, ignore_root_matrix);
-        engine().set_object(p);
+        ObjectTables tabs;
+        Program p = compile_mp5(shape_json, ignore_root_matrix, &tabs);
+        engine().set_object(p, nullptr, &tabs);
     } catch (const InputError& e) {
         report(e.what(), true);
         return 0;
@@ -765,9 +768,12 @@ int implisolid_debug_intervals(const char* shape_json, int ignore_root_matrix, i
     if (n == 0) return 0;
     TreeJit::Slot* slot = nullptr;
     try {
-        const Program p = compile_mp5(shape_json, ignore_root_matrix != 0);
+        ObjectTables tabs;
+        const Program p = compile_mp5(shape_json, ignore_root_matrix != 0, &tabs);
         Engine& E = engine();
         hipStream_t s = abi_stream();
+        TableArena arena;   // the probed shape's own sdf_3d tables (the engine's rabbit section first either way)
+        const float* d_tab = arena.set(tabs, E.d_rabbit());
         hipFunction_t fn = nullptr;
         if (variant) {   // the shape module (1) or the object's baked module (2), compiled before the launch
             TreeJit& J = TreeJit::instance();
@@ -790,7 +796,7 @@ int implisolid_debug_intervals(const char* shape_json, int ignore_root_matrix, i
         uint64_t* d_mo = dm.as<uint64_t>() + n;
         IMPLI_HIP(hipMemcpyAsync(db.p, boxes, (size_t)n * 24, hipMemcpyHostToDevice, s));
         if (modes_in) IMPLI_HIP(hipMemcpyAsync(d_mi, modes_in, (size_t)n * 8, hipMemcpyHostToDevice, s));
-        launch_iv_probe(dp.get(), p.max_depth, E.d_rabbit(), E.tab_range(), db.as<float>(), d_mi, n, dout.as<float>(), d_mo, s,
+        launch_iv_probe(dp.get(), p.max_depth, d_tab, E.tab_range(), db.as<float>(), d_mi, n, dout.as<float>(), d_mo, s,
                         fn);
         IMPLI_HIP(hipGetLastError());
         IMPLI_HIP(hipMemcpyAsync(iv_out, dout.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
@@ -818,9 +824,12 @@ int implisolid_debug_eval_modes(const char* shape_json, int ignore_root_matrix, 
     }
     if (n == 0) return 0;
     try {
-        const Program p = compile_mp5(shape_json, ignore_root_matrix != 0);
+        ObjectTables tabs;
+        const Program p = compile_mp5(shape_json, ignore_root_matrix != 0, &tabs);
         Engine& E = engine();
         hipStream_t s = abi_stream();
+        TableArena arena;
+        const float* d_tab = arena.set(tabs, E.d_rabbit());
         ProbeProgram dp(p);
         DevBuf& dx = E.scratch(0);
         DevBuf& dm = E.scratch(1);
@@ -830,7 +839,7 @@ int implisolid_debug_eval_modes(const char* shape_json, int ignore_root_matrix, 
         df.reserve((size_t)n * 4);
         IMPLI_HIP(hipMemcpyAsync(dx.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, s));
         IMPLI_HIP(hipMemcpyAsync(dm.p, modes, (size_t)n * 8, hipMemcpyHostToDevice, s));
-        launch_eval_modes_probe(dp.get(), p.max_depth, E.d_rabbit(), dx.as<float>(), dm.as<uint64_t>(), n, df.as<float>(), s);
+        launch_eval_modes_probe(dp.get(), p.max_depth, d_tab, dx.as<float>(), dm.as<uint64_t>(), n, df.as<float>(), s);
         IMPLI_HIP(hipGetLastError());
         IMPLI_HIP(hipMemcpyAsync(f_out, df.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
         IMPLI_HIP(hipStreamSynchronize(s));
@@ -928,7 +937,8 @@ void about(void) {
 static int64_t jit_compile_kind(const char* shape_json, int kind, char* source_out, int64_t capacity, double* seconds) {
     g_last_error.clear();
     try {
-        const Program p = compile_mp5(shape_json, false);
+        ObjectTables tabs;   // the source reads the tables as data: only the program matters here
+        const Program p = compile_mp5(shape_json, false, &tabs);
         // (bake mode 1, "always": the value-baked source of this object)
         const std::string src = kind == TreeJit::kPoints ? TreeJit::point_source(p)
                                                          : TreeJit::kernel_source(p, TreeJit::instance().bake() == TreeJit::kBakeAlways);
@@ -958,7 +968,8 @@ int64_t implisolid_jit_compile_points(const char* shape_json, char* source_out, 
 int implisolid_program_info(const char* shape_json, int ignore_root_matrix, int32_t info[4], float* mats_out) {
     g_last_error.clear();
     try {
-        const Program p = compile_mp5(shape_json, ignore_root_matrix != 0);
+        ObjectTables tabs;
+        const Program p = compile_mp5(shape_json, ignore_root_matrix != 0, &tabs);
         info[0] = p.n_instr;
         info[1] = p.max_depth;
         info[2] = p.n_mats;
@@ -980,9 +991,10 @@ implisolid_slab* implisolid_slab_create_range(const char* shape_json, const char
     g_last_error.clear();
     try {
         MCSettings st = parse_mc_settings(mc_json);
-        Program p = compile_mp5(shape_json, st.ignore_root_matrix);
+        ObjectTables tabs;
+        Program p = compile_mp5(shape_json, st.ignore_root_matrix, &tabs);
         auto* s = new implisolid_slab();
-        s->engine.set_object(p);
+        s->engine.set_object(p, nullptr, &tabs);
         s->engine.set_slab(st.resolution, st.box, SlabRange{z0, z1, 0});
         return s;
     } catch (const std::exception& e) {
@@ -995,8 +1007,9 @@ int implisolid_slab_balance(const char* shape_json, const char* mc_json, int nra
     g_last_error.clear();
     try {
         const MCSettings st = parse_mc_settings(mc_json);
-        const Program p = compile_mp5(shape_json, st.ignore_root_matrix);
-        const std::vector<int> c = balance_cuts(p, st.resolution, st.box, nranks, nullptr);
+        ObjectTables tabs;
+        const Program p = compile_mp5(shape_json, st.ignore_root_matrix, &tabs);
+        const std::vector<int> c = balance_cuts(p, st.resolution, st.box, nranks, nullptr, &tabs);
         for (size_t k = 0; k < c.size(); ++k) cuts[k] = c[k];
     } catch (const std::exception& e) {
         report(e.what(), false);
@@ -1042,9 +1055,10 @@ implisolid_slab* implisolid_slab_create(const char* shape_json, const char* mc_j
     g_last_error.clear();
     try {
         MCSettings st = parse_mc_settings(mc_json);
-        Program p = compile_mp5(shape_json, st.ignore_root_matrix);
+        ObjectTables tabs;
+        Program p = compile_mp5(shape_json, st.ignore_root_matrix, &tabs);
         auto* s = new implisolid_slab();
-        s->engine.set_object(p);
+        s->engine.set_object(p, nullptr, &tabs);
         s->engine.set_grid(st.resolution, st.box, rank, nranks);
         return s;
     } catch (const std::exception& e) {
@@ -1665,10 +1679,11 @@ implisolid_ob02* implisolid_ob02_create(const char* shape_json, const char* mc_j
     auto* h = new implisolid_ob02();
     try {
         h->st = parse_mc_settings(mc_json);
-        const Program p = compile_mp5(shape_json, h->st.ignore_root_matrix);
+        ObjectTables tabs;
+        const Program p = compile_mp5(shape_json, h->st.ignore_root_matrix, &tabs);
         IMPLI_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
         h->engine.reset(new Engine());
-        h->engine->set_object(p);
+        h->engine->set_object(p, nullptr, &tabs);
         h->ob.reset(new Ob02(*h->engine, h->stream));
         h->ob->capture_pointsets = false;
     } catch (const std::exception& e) {

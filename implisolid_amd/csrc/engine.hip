@@ -245,6 +245,9 @@ Engine::Engine(hipStream_t setup, std::vector<ZeroRange>* resets) : resets_(rese
             t.rabbit_bytes = all.size() * sizeof(float);
             t.cases = c;
         }
+        static_assert(kArenaRabbitFloats == 3 * dev::kRabbitPadded, "the arena's rabbit section is the shared table");
+        shared_rabbit_ = t.rabbit;
+        shared_rabbit_bytes_ = t.rabbit_bytes;
         rabbit_.attach(t.rabbit, t.rabbit_bytes);
         cases_.attach(t.cases, sizeof(CaseInfo) * 256);
         tab_range_ = g_tab_range;
@@ -313,6 +316,7 @@ Engine::~Engine() {
                      &records_, &verts_, &faces_, &normals_, &nproblems_};
     for (auto* b : all) b->release();
     for (auto& b : scratch_) b.release();
+    arena_.release();
     // the buffers went to the pool (no hipFree and its implicit synchronisation): the modules'
     // last launches must be done before release_jit may unload them
     if (jit_slot_ || bake_slot_ || pt_slot_ || pt_bake_slot_) (void)hipDeviceSynchronize();
@@ -344,9 +348,31 @@ int program_vdepth(const Program& p) {
     return best;
 }
 
-void Engine::set_object(const Program& prog, const Program* d_prog) {
+const float* TableArena::set(const ObjectTables& t, const float* d_shared_rabbit) {
+    if (t.empty()) {
+        buf_.release();
+        return d_shared_rabbit;
+    }
+    buf_.reserve(t.arena_floats * sizeof(float));
+    float* a = buf_.as<float>();
+    IMPLI_HIP(hipMemcpy(a, d_shared_rabbit, (size_t)kArenaRabbitFloats * sizeof(float), hipMemcpyDeviceToDevice));
+    for (const SdfTable& T : t.nodes) {
+        if ((size_t)T.tab_off + T.padded > t.arena_floats || T.data_off + T.padded > t.data.size())
+            throw InputError("sdf_3d: table layout out of range");
+        IMPLI_HIP(hipMemcpy(a + T.tab_off, t.data.data() + T.data_off, (size_t)T.padded * sizeof(float), hipMemcpyHostToDevice));
+        launch_sdf3d_pyramid(a, T.tab_off, (int)T.sx, (int)T.sy, (int)T.sz, T.level0, (int)T.n_levels, T.lvl_off, nullptr);
+    }
+    IMPLI_HIP(hipGetLastError());
+    // the engine's kernels run on caller streams, which the null stream does not order against
+    IMPLI_HIP(hipDeviceSynchronize());
+    return a;
+}
+
+void Engine::set_object(const Program& prog, const Program* d_prog, const ObjectTables* tables) {
+    static const ObjectTables no_tables;
+    const ObjectTables& T = tables ? *tables : no_tables;
     // the same object again (repeated builds): keep its modules and its eval count
-    if (have_object_ && !d_prog && std::memcmp(&prog, &prog_host_, sizeof(Program)) == 0) return;
+    if (have_object_ && !d_prog && std::memcmp(&prog, &prog_host_, sizeof(Program)) == 0 && T.same(tables_host_)) return;
     // the engine's kernels run on caller streams (often non-blocking): nothing in flight may still
     // read the program being replaced (a fresh engine has launched nothing)
     if (have_object_ || have_grid_) IMPLI_HIP(hipDeviceSynchronize());
@@ -361,6 +387,11 @@ void Engine::set_object(const Program& prog, const Program* d_prog) {
     vdepth_ = program_vdepth(prog);
     n_csg_ = prog.n_csg;
     prog_host_ = prog;
+    if (!T.empty() || !tables_host_.empty()) {
+        const float* tab = arena_.set(T, static_cast<const float*>(shared_rabbit_));
+        rabbit_.attach(const_cast<float*>(tab), T.empty() ? shared_rabbit_bytes_ : arena_.bytes());
+        tables_host_ = T;
+    }
     release_jit();
     TreeJit::instance().trim();   // the device is synchronised here: a safe point to unload modules
     evals_ = 0;
@@ -599,10 +630,11 @@ std::vector<int> cuts_from_layer_work(const std::vector<int64_t>& listed, int64_
     return cuts;
 }
 
-std::vector<int> balance_cuts(const Program& prog, int R, const float box[6], int nranks, hipStream_t s) {
+std::vector<int> balance_cuts(const Program& prog, int R, const float box[6], int nranks, hipStream_t s,
+                              const ObjectTables* tables) {
     if (nranks == 1) return {1, R + 3};
     Engine probe;
-    probe.set_object(prog);
+    probe.set_object(prog, nullptr, tables);
     probe.set_slab(R, box, SlabRange{1, R + 3, 0}, true);
     probe.interval_pass(s);
     const BrickGrid bg = brick_grid(probe.grid());

@@ -64,12 +64,29 @@ struct SlabCounts {
 // share of the bricks the pruned eval lists (field values + marching cubes scale with them) plus a
 // small per-brick term for the interval / fill passes over every brick.  Runs the interval pass of
 // the whole grid once on the current device (deterministic: every rank computes the same cuts).
-std::vector<int> balance_cuts(const Program& prog, int R, const float box[6], int nranks, hipStream_t stream);
+std::vector<int> balance_cuts(const Program& prog, int R, const float box[6], int nranks, hipStream_t stream,
+                              const ObjectTables* tables = nullptr);
 // the same from per-stored-layer listed-brick counts of the whole grid (host-only, tested on CPU)
 std::vector<int> cuts_from_layer_work(const std::vector<int64_t>& listed_per_layer, int64_t bricks_per_layer, int R,
                                       int nranks);
 
 struct ZeroRange { void* p; size_t n; };
+
+// The `tab` pointer every kernel receives.  An object without sdf_3d nodes reads the per-device
+// shared rabbit table; one with such nodes gets an arena of its own on its device (host.hpp
+// ObjectTables): a copy of the rabbit section at the same offsets, then each node's zero-padded
+// table and its min / max pyramid, which k_sdf3d_level0 / k_sdf3d_level build on the device.
+class TableArena {
+public:
+    ~TableArena() { buf_.release(); }
+    // on the current device; blocking (the arena is complete when it returns).  Returns the shared
+    // table when t is empty.
+    const float* set(const ObjectTables& t, const float* d_shared_rabbit);
+    size_t bytes() const { return buf_.bytes; }
+    void release() { buf_.release(); }
+private:
+    DevBuf buf_;
+};
 
 class Engine {
 public:
@@ -86,7 +103,9 @@ public:
     // probe_only: allocate only what the interval pass needs (interval_pass, listed_per_layer).
     // d_prog: the program already on the device (an object stream uploads all its programs at once;
     // the engine reads it there, it must outlive the engine's use)
-    void set_object(const Program& prog, const Program* d_prog = nullptr);
+    // tables: the object's sdf_3d tables (compile_mp5); the engine keeps a copy and builds the
+    // object's table arena on its device.  The same program with other table contents is another object.
+    void set_object(const Program& prog, const Program* d_prog = nullptr, const ObjectTables* tables = nullptr);
     void set_grid(int R, const float box[6], int rank, int nranks);
     // setup: a fresh engine's buffer resets go on this stream, without device synchronisations
     // (an object stream sets up its engines back to back; every later launch of theirs is on it)
@@ -215,6 +234,10 @@ private:
     int vdepth_ = 1;
     int n_csg_ = 0;
     Program prog_host_{};
+    ObjectTables tables_host_;             // the object's sdf_3d tables ("same object" includes their contents)
+    TableArena arena_;                     // ... and their device arena (rabbit_ points into it then)
+    void* shared_rabbit_ = nullptr;        // the per-device shared table objects without sdf_3d read
+    size_t shared_rabbit_bytes_ = 0;
     TreeJit::Slot* jit_slot_ = nullptr;   // the object's module (null: JIT off); may still compile
     bool jit_requested_ = false;
     TreeJit::Slot* bake_slot_ = nullptr;  // its baked module (TreeJit bake modes), preferred once loaded

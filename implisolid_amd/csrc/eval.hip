@@ -115,6 +115,7 @@ __device__ __forceinline__ void prim_f2(int t, const float* __restrict__ tab, co
         case NT_METABALLS: a = meta_f(prm, x0, y0, z0); b = meta_f(prm, x1, y1, z1); return;
         case NT_EXTRUSION: a = extr_f(prm, x0, y0); b = extr_f(prm, x1, y1); return;
         case NT_SCREW_TBB: a = tbb_f(prm, x0, y0, z0); b = tbb_f(prm, x1, y1, z1); return;
+        case NT_SDF3D: a = sdf3d_f(tab, prm, x0, y0, z0); b = sdf3d_f(tab, prm, x1, y1, z1); return;
         default: a = dm_f(x0, y0, z0); b = dm_f(x1, y1, z1); return;
     }
 }
@@ -791,6 +792,57 @@ void launch_iv_probe(const Program* d_prog, int depth, const float* d_rabbit, fl
     else if (depth <= 8) k_iv_probe<8><<<blocks, 256, 0, s>>>(d_prog, d_rabbit, tab_range, d_boxes, d_modes_in, n, d_iv, d_modes_out);
     else if (depth <= 12) k_iv_probe<12><<<blocks, 256, 0, s>>>(d_prog, d_rabbit, tab_range, d_boxes, d_modes_in, n, d_iv, d_modes_out);
     else k_iv_probe<16><<<blocks, 256, 0, s>>>(d_prog, d_rabbit, tab_range, d_boxes, d_modes_in, n, d_iv, d_modes_out);
+}
+
+// ---- the min / max pyramid of an sdf_3d table (ifunc_interval.hpp sdf3d_iv) ---------------------
+// level 0: {min, max} over the eight reads b + {0, 1} + {0, sx} + {0, sx sy} of every flat index
+// b < n (cube_iv's block table); the table is zero-padded past the last read (b + 1 + sx + sx sy)
+__global__ __launch_bounds__(256) void k_sdf3d_level0(const float* __restrict__ tab, int sx, int sxy, uint32_t n,
+                                                       float2* __restrict__ out) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= n) return;
+    float lo = INFINITY, hi = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const float v = tab[b + (k & 1) + ((k & 2) ? sx : 0) + ((k & 4) ? sxy : 0)];
+        lo = v < lo ? v : lo;
+        hi = v > hi ? v : hi;
+    }
+    out[b] = float2{lo, hi};
+}
+// level L + 1 from level L: entry (X, Y, Z) of the dense (ox, oy, oz) grid combines the entries
+// (2X + {0, 1}, 2Y + {0, 1}, 2Z + {0, 1}) of the input that lie inside its (ix, iy, iz) grid; the
+// input is addressed x + y isx + z isxy (level 0: the table's flat strides, else its own dense ones)
+__global__ __launch_bounds__(256) void k_sdf3d_level(const float2* __restrict__ in, int ix, int iy, int iz, int isx,
+                                                      int isxy, int ox, int oy, int oz, float2* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (uint32_t)(ox * oy * oz)) return;
+    const int X = (int)(i % (uint32_t)ox), Y = (int)((i / (uint32_t)ox) % (uint32_t)oy), Z = (int)(i / (uint32_t)(ox * oy));
+    float lo = INFINITY, hi = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int x = 2 * X + (k & 1), y = 2 * Y + ((k >> 1) & 1), z = 2 * Z + (k >> 2);
+        if (x < ix && y < iy && z < iz) {
+            const float2 m = in[x + y * isx + z * isxy];
+            lo = m.x < lo ? m.x : lo;
+            hi = m.y > hi ? m.y : hi;
+        }
+    }
+    out[i] = float2{lo, hi};
+}
+
+void launch_sdf3d_pyramid(float* d_arena, uint32_t tab_off, int sx, int sy, int sz, uint32_t level0, int n_levels,
+                          const uint32_t* lvl_off, hipStream_t s) {
+    float2* l0 = reinterpret_cast<float2*>(d_arena + lvl_off[0]);
+    k_sdf3d_level0<<<(level0 + 255) / 256, 256, 0, s>>>(d_arena + tab_off, sx, sx * sy, level0, l0);
+    int ix = sx + 1, iy = sy + 1, iz = sz + 1, isx = sx, isxy = sx * sy;   // level 0: the cells 0 .. size per axis
+    for (int L = 1; L < n_levels; ++L) {
+        const int ox = (sx >> L) + 1, oy = (sy >> L) + 1, oz = (sz >> L) + 1;
+        const uint32_t n = (uint32_t)ox * oy * oz;
+        k_sdf3d_level<<<(n + 255) / 256, 256, 0, s>>>(reinterpret_cast<const float2*>(d_arena + lvl_off[L - 1]), ix, iy, iz,
+                                                       isx, isxy, ox, oy, oz, reinterpret_cast<float2*>(d_arena + lvl_off[L]));
+        ix = ox; iy = oy; iz = oz; isx = ox; isxy = ox * oy;
+    }
 }
 
 // diagnostics: the pruned point interpreter with a caller-given modes word per point

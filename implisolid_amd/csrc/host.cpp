@@ -133,6 +133,7 @@ namespace {
 struct Builder {
     Program p{};
     int depth = 0, max_depth = 0;
+    ObjectTables* tables = nullptr;   // receives the sdf_3d tables (null: such nodes are refused)
 
     int add_matrix(const float m[12]) {
         if (p.n_mats >= kMaxProgram) throw InputError("MP5 tree too large");
@@ -297,6 +298,88 @@ struct Builder {
         return 1 + 3 * size;
     }
 
+    // sdf_3d (object_factory.hpp:352-395, sdf_3d.hpp:73-102): sizes, grid_size, origin and the "sdf"
+    // array, flat index x + y size_x + z size_x size_y as in cube.hpp.  Validates the node, appends
+    // its zero-padded table to `tables` and lays out its arena section (host.hpp ObjectTables).
+    void sdf3d_params(const Json& d, float prm[kSdfParams]) {
+        (void)d.get_int("id", 0);   // read, otherwise unused
+        int size[3];
+        const char* size_keys[3] = {"size_x", "size_y", "size_z"};
+        for (int k = 0; k < 3; ++k) {
+            if (!d.find(size_keys[k])->as_int(&size[k]))
+                throw InputError(std::string("sdf_3d: \"") + size_keys[k] + "\" must be an integer");
+            if (size[k] < kSdfMinSize || size[k] > kSdfMaxSize)
+                throw InputError(std::string("sdf_3d: \"") + size_keys[k] + "\" must be in [2, 512]");
+        }
+        const int64_t N = (int64_t)size[0] * size[1] * size[2];
+        if (N > kSdfMaxEntries) throw InputError("sdf_3d: size_x * size_y * size_z exceeds 2^22 entries");
+        float gs, org[3];
+        if (!d.get_float("grid_size", &gs) || !std::isfinite(gs) || !(gs > 0.f))
+            throw InputError("sdf_3d: \"grid_size\" must be a finite number > 0");
+        const char* org_keys[3] = {"origin_x", "origin_y", "origin_z"};
+        for (int k = 0; k < 3; ++k)
+            if (!d.get_float(org_keys[k], &org[k]) || !std::isfinite(org[k]))
+                throw InputError(std::string("sdf_3d: \"") + org_keys[k] + "\" must be a finite number");
+        // the largest cell index the point function computes, (int)((X - o) / gs) at the box's far
+        // face X = o + gs size (monotone in X), in the device's float operations: it must stay at
+        // size, the last index the padding covers (a grid_size far below the origin's rounding
+        // step would pass it)
+        for (int k = 0; k < 3; ++k) {
+            const float far = org[k] + gs * (float)size[k];
+            const float cell = (far - org[k]) / gs;
+            if (!std::isfinite(far) || !(cell < (float)(size[k] + 1)))
+                throw InputError(std::string("sdf_3d: \"grid_size\" is too small against \"") + org_keys[k] +
+                                 "\" (the table box does not resolve in float)");
+        }
+        const Json* sdf = d.find("sdf");
+        if (sdf->kind != Json::Array) throw InputError("sdf_3d: \"sdf\" must be an array");
+        if ((int64_t)sdf->items.size() != N)
+            throw InputError("sdf_3d: \"sdf\" holds " + std::to_string(sdf->items.size()) + " values, size_x * size_y * size_z is " +
+                             std::to_string(N));
+        if ((int)tables->nodes.size() >= kSdfMaxNodes) throw InputError("sdf_3d: more than 8 sdf_3d nodes in one object");
+
+        SdfTable T{};
+        T.sx = (uint32_t)size[0]; T.sy = (uint32_t)size[1]; T.sz = (uint32_t)size[2];
+        const uint32_t sxy = T.sx * T.sy;
+        T.level0 = T.sx + T.sy * T.sx + T.sz * sxy + 1;          // flat indices of the cells 0 .. size per axis
+        T.padded = (T.level0 + 1 + T.sx + sxy + 1) & ~1u;         // + the eight reads' reach, kept even (float2 alignment)
+        T.data_off = tables->data.size();
+        tables->data.resize(T.data_off + T.padded, 0.f);
+        float* tab = tables->data.data() + T.data_off;
+        float vmin = 0.f, vmax = 0.f;                             // the padding's zeros are readable
+        for (int64_t i = 0; i < N; ++i) {
+            float v;
+            if (!sdf->items[(size_t)i].second.as_float(&v) || !std::isfinite(v))
+                throw InputError("sdf_3d: \"sdf\"[" + std::to_string(i) + "] is not a finite number");
+            tab[i] = v;
+            vmin = v < vmin ? v : vmin;
+            vmax = v > vmax ? v : vmax;
+        }
+        uint32_t smax = std::max(T.sx, std::max(T.sy, T.sz)), top = 0;
+        while ((smax >> top) > 1) ++top;
+        T.n_levels = top + 1;
+        size_t off = tables->nodes.empty() ? (size_t)kArenaRabbitFloats : tables->arena_floats;
+        T.tab_off = (uint32_t)off;
+        off += T.padded;
+        for (uint32_t L = 0; L < T.n_levels; ++L) {
+            T.lvl_off[L] = (uint32_t)off;
+            const size_t entries = L == 0 ? (size_t)T.level0
+                                          : (size_t)((T.sx >> L) + 1) * ((T.sy >> L) + 1) * ((T.sz >> L) + 1);
+            off += 2 * entries;
+        }
+        tables->arena_floats = off;
+        tables->nodes.push_back(T);
+
+        auto bits = [](uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; };
+        std::memset(prm, 0, sizeof(float) * kSdfParams);
+        prm[SDF_SX] = (float)T.sx; prm[SDF_SY] = (float)T.sy; prm[SDF_SZ] = (float)T.sz;
+        prm[SDF_GS] = gs; prm[SDF_OX] = org[0]; prm[SDF_OY] = org[1]; prm[SDF_OZ] = org[2];
+        prm[SDF_VMIN] = vmin; prm[SDF_VMAX] = vmax;
+        prm[SDF_TAB] = bits(T.tab_off);
+        prm[SDF_LEVELS] = (float)T.n_levels;
+        for (uint32_t L = 0; L < T.n_levels; ++L) prm[SDF_LVL0 + L] = bits(T.lvl_off[L]);
+    }
+
     static void vec3(const Json& d, const char* key, float out[3]) {
         const Json* a = d.find(key);
         if (!a || a->kind != Json::Array || a->items.size() < 3) throw InputError(std::string("half_plane: bad \"") + key + "\"");
@@ -442,6 +525,24 @@ struct Builder {
             csg(NT_DIFFERENCE, m, [&] { leaf(NT_EXTRUSION, eye, prm, n); }, [&] { leaf(NT_LID, eye); });
             return;
         }
+        if (t == "sdf_3d") {           // :352-395, sdf_3d.hpp:73-102: the table is read from the node
+            // a node without the table fields is the reference's by-id form (the table fetched by
+            // JavaScript): outside the implemented families, as before
+            std::string missing;
+            for (const char* k : {"size_x", "size_y", "size_z", "grid_size", "origin_x", "origin_y", "origin_z", "sdf"})
+                if (!d.find(k)) missing += std::string(missing.empty() ? "" : ", ") + "\"" + k + "\"";
+            if (!missing.empty())
+                throw InputError("MP5 type \"sdf_3d\" is outside the implemented node families: the node carries no " +
+                                 missing + " (a table fetched by id is not supported)");
+            // (object streams pass no table receiver: their programs travel without table arenas)
+            if (!tables) throw InputError("MP5 type \"sdf_3d\" is not supported in an object stream (implisolid_batch_create)");
+            matrix12(d, m);
+            if (ignore) std::memcpy(m, eye, sizeof m);
+            float prm[kSdfParams];
+            sdf3d_params(d, prm);
+            leaf(NT_SDF3D, m, prm, kSdfParams);
+            return;
+        }
         static const char* unsupported[] = {"sdf_3d", "rawjscode"};
         for (auto* u : unsupported)
             if (t == u) throw InputError("MP5 type \"" + t + "\" is outside the implemented node families");
@@ -461,8 +562,19 @@ struct Builder {
 
 }  // namespace
 
-Program compile_mp5(const Json& shape, bool ignore_root_matrix) {
+bool ObjectTables::same(const ObjectTables& o) const {
+    if (nodes.size() != o.nodes.size() || arena_floats != o.arena_floats || data.size() != o.data.size()) return false;
+    for (size_t i = 0; i < nodes.size(); ++i) {
+        const SdfTable &a = nodes[i], &b = o.nodes[i];
+        if (a.sx != b.sx || a.sy != b.sy || a.sz != b.sz || a.tab_off != b.tab_off || a.data_off != b.data_off) return false;
+    }
+    return data.empty() || std::memcmp(data.data(), o.data.data(), data.size() * sizeof(float)) == 0;
+}
+
+Program compile_mp5(const Json& shape, bool ignore_root_matrix, ObjectTables* tables) {
     Builder b;
+    if (tables) *tables = ObjectTables{};
+    b.tables = tables;
     b.node(shape, ignore_root_matrix);
     b.p.max_depth = b.max_depth + 1;
     for (int i = 0; i < b.p.n_instr; ++i) {   // XFORM patterns (program.hpp XformPattern)
@@ -484,14 +596,14 @@ Program compile_mp5(const Json& shape, bool ignore_root_matrix) {
     return b.p;
 }
 
-Program compile_mp5(const char* shape_json, bool ignore_root_matrix) {
+Program compile_mp5(const char* shape_json, bool ignore_root_matrix, ObjectTables* tables) {
     Json d;
     try {
         d = Json::parse(shape_json);
     } catch (const JsonError& e) {
         throw InputError(e.what());
     }
-    return compile_mp5(d, ignore_root_matrix);
+    return compile_mp5(d, ignore_root_matrix, tables);
 }
 
 // the largest resolution the settings parser accepts (the reference's dim_t, polygoniser_settings.hpp)

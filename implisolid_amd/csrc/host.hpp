@@ -33,10 +33,37 @@ struct InputError : std::runtime_error {
 // reference sets needs_abort.
 MCSettings parse_mc_settings(const char* json_text);
 
+// The caller-supplied SDF tables of an object's sdf_3d nodes (sdf_3d.hpp:73-102: read from the node
+// itself).  They travel beside the Program, whose NT_SDF3D parameter rows (program.hpp SdfParam)
+// hold each table's place in the object's device table arena:
+//   [0, kArenaRabbitFloats)   the rabbit section, as every object without sdf_3d reads it
+//   per node                  the table, zero-padded to `padded` floats, then its min / max pyramid
+//                             (float2 entries; built on the device, engine.hip TableArena)
+// Level 0 has one entry per flat index b < level0 = sx + sy sx + sz sx sy + 1 (cube_iv's block
+// table: min / max of the eight reads from b); level L >= 1 is a dense (s >> L) + 1 grid per axis
+// whose entry combines 2 x 2 x 2 entries of level L - 1.
+struct SdfTable {
+    uint32_t sx, sy, sz;
+    uint32_t padded;                  // floats of the zero-padded table: every index a read can reach
+    uint32_t level0;                  // entries of level 0
+    uint32_t n_levels;
+    uint32_t tab_off;                 // arena offsets, in floats
+    uint32_t lvl_off[kSdfMaxLevels];
+    size_t data_off;                  // the padded table's start in ObjectTables::data
+};
+struct ObjectTables {
+    std::vector<SdfTable> nodes;
+    std::vector<float> data;          // the nodes' padded tables, one after the other
+    size_t arena_floats = 0;          // the whole arena, rabbit section included
+    bool empty() const { return nodes.empty(); }
+    bool same(const ObjectTables& o) const;   // layout and table contents, bit for bit
+};
+
 // object_factory (object_factory.hpp:56-758) -> node program.  Throws InputError for unknown or
-// unsupported node types (the reference abort()s on unknown ones, :731-734).
-Program compile_mp5(const char* shape_json, bool ignore_root_matrix);
-Program compile_mp5(const Json& shape, bool ignore_root_matrix);
+// unsupported node types (the reference abort()s on unknown ones, :731-734).  tables receives the
+// object's sdf_3d tables; a caller that passes none cannot take a shape with such a node (InputError).
+Program compile_mp5(const char* shape_json, bool ignore_root_matrix, ObjectTables* tables = nullptr);
+Program compile_mp5(const Json& shape, bool ignore_root_matrix, ObjectTables* tables = nullptr);
 
 // Z-slab decomposition of the cell layers 1 .. res-3 (res = R + 5) over nranks: rank r owns
 // layers [z0, z1) and recomputes `halo` (0 or 1) layer below z0 (owner rule).

@@ -113,6 +113,70 @@ __device__ __forceinline__ float cube_f(const float* __restrict__ tab, float X, 
     }
     return -res;
 }
+// ---- sdf_3d = a caller-supplied SDF table (sdf_3d.hpp:73-102 reads it from the node; the
+//      reference hands the evaluation to JavaScript).  The value is cube_f's operations in its
+//      order with the node's sizes, grid size, origin and table (prm: program.hpp SdfParam; the
+//      table at arena offset SDF_TAB, zero-padded over every index a read can reach -- the host
+//      checks that the cell index stays <= size per axis, host.cpp sdf3d_params).
+struct SdfCell {   // the cell's eight reads and fractions, shared by the value and the gradient
+    float r000, r100, r010, r110, r001, r101, r011, r111, xd, yd, zd, gs;
+    bool out;
+};
+__device__ __forceinline__ SdfCell sdf3d_cell(const float* __restrict__ arena, const float* __restrict__ prm, float X,
+                                              float Y, float Z) {
+    const int sx = (int)prm[SDF_SX], sy = (int)prm[SDF_SY], sz = (int)prm[SDF_SZ];
+    const float gs = prm[SDF_GS], ox = prm[SDF_OX], oy = prm[SDF_OY], oz = prm[SDF_OZ];
+    const float* __restrict__ tab = arena + __float_as_uint(prm[SDF_TAB]);
+    SdfCell c;
+    c.gs = gs;
+    c.out = (ox + gs * (float)sx < X || X < ox) || (oy + gs * (float)sy < Y || Y < oy) ||
+            (oz + gs * (float)sz < Z || Z < oz);
+    c.r000 = c.r100 = c.r010 = c.r110 = c.r001 = c.r101 = c.r011 = c.r111 = 0.f;
+    c.xd = c.yd = c.zd = 0.f;
+    if (!c.out) {
+        const int xg = (int)((X - ox) / gs), yg = (int)((Y - oy) / gs), zg = (int)((Z - oz) / gs);
+        const float xl = ox + (float)xg * gs, yl = oy + (float)yg * gs, zl = oz + (float)zg * gs;
+        c.xd = (X - xl) / gs; c.yd = (Y - yl) / gs; c.zd = (Z - zl) / gs;
+        const int b = xg + yg * sx + zg * sx * sy;
+        c.r000 = tab[b]; c.r100 = tab[b + 1]; c.r010 = tab[b + sx]; c.r110 = tab[b + 1 + sx];
+        c.r001 = tab[b + sx * sy]; c.r101 = tab[b + 1 + sx * sy]; c.r011 = tab[b + sx + sx * sy];
+        c.r111 = tab[b + 1 + sx + sx * sy];
+    }
+    return c;
+}
+__device__ __forceinline__ float sdf3d_f(const float* __restrict__ arena, const float* __restrict__ prm, float X, float Y,
+                                         float Z) {
+    const SdfCell c = sdf3d_cell(arena, prm, X, Y, Z);
+    float res = 10000.f;
+    if (!c.out) {
+        const float c00 = c.r000 * (1.f - c.xd) + c.r100 * c.xd;
+        const float c01 = c.r001 * (1.f - c.xd) + c.r101 * c.xd;
+        const float c10 = c.r010 * (1.f - c.xd) + c.r110 * c.xd;
+        const float c11 = c.r011 * (1.f - c.xd) + c.r111 * c.xd;
+        const float c0 = c00 * (1.f - c.yd) + c10 * c.yd;
+        const float c1 = c01 * (1.f - c.yd) + c11 * c.yd;
+        res = c0 * (1.f - c.zd) + c1 * c.zd;
+    }
+    return -res;
+}
+// The reference's sdf_3d::eval_gradient is empty (its output stays unwritten): defined here as the
+// analytic gradient of the value inside the cell, (0, 0, 0) outside the table box
+__device__ __forceinline__ V3 sdf3d_g(const float* __restrict__ arena, const float* __restrict__ prm, float X, float Y,
+                                      float Z) {
+    const SdfCell c = sdf3d_cell(arena, prm, X, Y, Z);
+    if (c.out) return V3{0.f, 0.f, 0.f};
+    const float c00 = c.r000 * (1.f - c.xd) + c.r100 * c.xd;
+    const float c01 = c.r001 * (1.f - c.xd) + c.r101 * c.xd;
+    const float c10 = c.r010 * (1.f - c.xd) + c.r110 * c.xd;
+    const float c11 = c.r011 * (1.f - c.xd) + c.r111 * c.xd;
+    const float c0 = c00 * (1.f - c.yd) + c10 * c.yd;
+    const float c1 = c01 * (1.f - c.yd) + c11 * c.yd;
+    const float e0 = (c.r100 - c.r000) * (1.f - c.yd) + (c.r110 - c.r010) * c.yd;
+    const float e1 = (c.r101 - c.r001) * (1.f - c.yd) + (c.r111 - c.r011) * c.yd;
+    return V3{-((e0 * (1.f - c.zd) + e1 * c.zd) / c.gs), -(((c10 - c00) * (1.f - c.zd) + (c11 - c01) * c.zd) / c.gs),
+              -((c1 - c0) / c.gs)};
+}
+
 // cube.hpp:273-315 -- the old six-plane gradient (does not match the rabbit field, F3)
 // The chosen face's normal is carried through the unrolled loop (constant indices only): indexing
 // the table with the winning face made it a private array, which the compiler kept in registers in
@@ -643,10 +707,12 @@ __device__ __forceinline__ float prim_f(int t, const float* __restrict__ tab, co
         case NT_METABALLS: return meta_f(prm, x, y, z);
         case NT_EXTRUSION: return extr_f(prm, x, y);
         case NT_SCREW_TBB: return tbb_f(prm, x, y, z);
+        case NT_SDF3D: return sdf3d_f(tab, prm, x, y, z);
         default: return dm_f(x, y, z);
     }
 }
-__device__ __forceinline__ V3 prim_g(int t, const float* __restrict__ prm, float x, float y, float z) {
+__device__ __forceinline__ V3 prim_g(int t, const float* __restrict__ tab, const float* __restrict__ prm, float x, float y,
+                                     float z) {
     switch (t) {
         case NT_ELLIPSOID: return egg_g(x, y, z);
         case NT_CUBE: return cube_g(x, y, z);
@@ -661,6 +727,7 @@ __device__ __forceinline__ V3 prim_g(int t, const float* __restrict__ prm, float
         case NT_METABALLS: return meta_g(prm, x, y, z);
         case NT_EXTRUSION: return extr_g(prm, x, y);
         case NT_SCREW_TBB: return tbb_g(prm, x, y, z);
+        case NT_SDF3D: return sdf3d_g(tab, prm, x, y, z);
         default: return dm_g(x, y, z);
     }
 }
@@ -718,7 +785,7 @@ __device__ __forceinline__ float eval_fg(const Program* __restrict__ prog, const
             px[sp] = q.x; py[sp] = q.y; pz[sp] = q.z;
         } else if (I.op == OP_PRIM) {
             const float f = prim_f(I.type, tab, prog->mats[I.prm], px[sp], py[sp], pz[sp]);
-            V3 g = prim_g(I.type, prog->mats[I.prm], px[sp], py[sp], pz[sp]);
+            V3 g = prim_g(I.type, tab, prog->mats[I.prm], px[sp], py[sp], pz[sp]);
             g = grad_xform(prog->mats[I.mat], g);
             vf[vp] = f; gx[vp] = g.x; gy[vp] = g.y; gz[vp] = g.z;
             ++vp;

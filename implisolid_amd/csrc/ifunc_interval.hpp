@@ -164,6 +164,49 @@ __device__ __forceinline__ Iv cube_iv(const float* __restrict__ tab, float2 tab_
     return r;
 }
 
+// sdf_3d (sdf3d_f): cube_iv with the node's table, the range taken from the table's min / max
+// pyramid (host.hpp ObjectTables, built on the device by k_sdf3d_level0 / k_sdf3d_level): for the
+// cells x0..x1 (y, z alike) the smallest level L with (x1 >> L) - (x0 >> L) <= 1 on all three axes,
+// whose at most 2 x 2 x 2 entries cover every cell of the box -- eight loads at any box size.  The
+// top level is at most 2 x 2 x 2 entries, so the search ends there at the latest.
+__device__ __forceinline__ Iv sdf3d_iv(const float* __restrict__ arena, const float* __restrict__ prm, Box p) {
+    const int sx = (int)prm[SDF_SX], sy = (int)prm[SDF_SY], sz = (int)prm[SDF_SZ];
+    const float gs = prm[SDF_GS], ox = prm[SDF_OX], oy = prm[SDF_OY], oz = prm[SDF_OZ];
+    const float xm = ox + gs * (float)sx, ym = oy + gs * (float)sy, zm = oz + gs * (float)sz;
+    const bool all_in = p.x.lo >= ox && p.x.hi <= xm && p.y.lo >= oy && p.y.hi <= ym && p.z.lo >= oz && p.z.hi <= zm;
+    const bool none_in = p.x.lo > xm || p.x.hi < ox || p.y.lo > ym || p.y.hi < oy || p.z.lo > zm || p.z.hi < oz;
+    const Iv outside{-10000.f, -10000.f};
+    if (none_in) return outside;
+    // in-table points: xg = (int)((X - ox) / gs) is monotone in X and at most sx (checked on the host)
+    const int x0 = (int)((fmax2(p.x.lo, ox) - ox) / gs), x1 = (int)((fmin2(p.x.hi, xm) - ox) / gs);
+    const int y0 = (int)((fmax2(p.y.lo, oy) - oy) / gs), y1 = (int)((fmin2(p.y.hi, ym) - oy) / gs);
+    const int z0 = (int)((fmax2(p.z.lo, oz) - oz) / gs), z1 = (int)((fmin2(p.z.hi, zm) - oz) / gs);
+    float vmin, vmax;
+    if (!(p.x.lo <= p.x.hi) || !(p.y.lo <= p.y.hi) || !(p.z.lo <= p.z.hi)) {
+        vmin = prm[SDF_VMIN]; vmax = prm[SDF_VMAX];
+    } else {
+        const int top = (int)prm[SDF_LEVELS] - 1;
+        int L = 0;
+        while (L < top && (((x1 >> L) - (x0 >> L)) > 1 || ((y1 >> L) - (y0 >> L)) > 1 || ((z1 >> L) - (z0 >> L)) > 1)) ++L;
+        // level 0 is indexed by the table's flat index, the levels above are dense grids
+        const int nx = L ? (sx >> L) + 1 : sx, nxy = L ? nx * ((sy >> L) + 1) : sx * sy;
+        const float2* mm = reinterpret_cast<const float2*>(arena + __float_as_uint(prm[SDF_LVL0 + L]));
+        vmin = INFINITY; vmax = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int x = ((k & 1) ? x1 : x0) >> L, y = ((k & 2) ? y1 : y0) >> L, z = ((k & 4) ? z1 : z0) >> L;
+            const float2 m = mm[x + y * nx + z * nxy];
+            vmin = fmin2(vmin, m.x);
+            vmax = fmax2(vmax, m.y);
+        }
+    }
+    // trilinear weights are in [0, 1] up to a few ulps; cover the extrapolation generously
+    const float s = (fabsf(vmin) + fabsf(vmax)) * 1e-4f + 1e-6f;
+    Iv r{-(vmax + s), -(vmin - s)};
+    if (!all_in) r = hull(r, outside);
+    return r;
+}
+
 __device__ __forceinline__ Iv cyl_iv(Box p) {
     const float w0 = 0.f, w1 = 0.f, w2 = 1.f, X = 0.f, Y = 0.f, Zc = -0.5f;
     const Iv t0 = add(add(mulc(sub(p.x, ivc(X)), w0), mulc(sub(p.y, ivc(Y)), w1)), mulc(sub(p.z, ivc(Zc)), w2));
@@ -324,6 +367,7 @@ __device__ __forceinline__ Iv prim_iv(int t, const float* __restrict__ tab, floa
         case NT_METABALLS: r = meta_iv(prm, p); break;
         case NT_EXTRUSION: r = extr_iv(prm, p); break;
         case NT_SCREW_TBB: r = tbb_iv(prm, p); break;
+        case NT_SDF3D: r = sdf3d_iv(tab, prm, p); break;
         default: r = dm_iv(p); break;
     }
     return settle(r);

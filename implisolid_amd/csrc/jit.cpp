@@ -101,6 +101,7 @@ const char* prim_call(int t) {
         case NT_TETRA: return "tet_f(P, ";
         case NT_METABALLS: return "meta_f(P, ";
         case NT_SCREW_TBB: return "tbb_f(P, ";
+        case NT_SDF3D: return "sdf3d_f(tab, P, ";
         default: throw std::runtime_error("jit: unknown primitive");
     }
 }
@@ -311,6 +312,7 @@ const char* prim_iv_call(int t) {
         case NT_METABALLS: return "meta_iv(P, ";
         case NT_EXTRUSION: return "extr_iv(P, ";
         case NT_SCREW_TBB: return "tbb_iv(P, ";
+        case NT_SDF3D: return "sdf3d_iv(tab, P, ";
         default: throw std::runtime_error("jit: unknown primitive");
     }
 }
@@ -378,6 +380,7 @@ const char* prim_g_call(int t) {
         case NT_TETRA: return "tet_g(P, ";
         case NT_METABALLS: return "meta_g(P, ";
         case NT_SCREW_TBB: return "tbb_g(P, ";
+        case NT_SDF3D: return "sdf3d_g(tab, P, ";
         default: throw std::runtime_error("jit: unknown primitive");
     }
 }

@@ -61,6 +61,11 @@ void launch_iv_probe(const Program* d_prog, int depth, const float* d_rabbit, fl
 void launch_eval_modes_probe(const Program* d_prog, int depth, const float* d_rabbit, const float* d_xyz,
                              const uint64_t* d_modes, int64_t n, float* d_f, hipStream_t s);
 
+// the min / max pyramid of one sdf_3d table inside an object's table arena (host.hpp SdfTable: the
+// padded table at tab_off, level L at lvl_off[L]); one launch per level, in order on s
+void launch_sdf3d_pyramid(float* d_arena, uint32_t tab_off, int sx, int sy, int sz, uint32_t level0, int n_levels,
+                          const uint32_t* lvl_off, hipStream_t s);
+
 // K2 (count per group) and K2b (group bases + flat list of non-empty units)
 void launch_mc_count(const CaseInfo* d_cases, const GridDesc& g, const MCBuffers& b, hipStream_t s);
 void launch_mc_scan(const GridDesc& g, const MCBuffers& b, hipStream_t s);

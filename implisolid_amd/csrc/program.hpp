@@ -42,7 +42,28 @@ enum NodeType : int32_t {
     NT_EXTRUSION = 15,    // extrusion.hpp + convex_polygon.hpp, params {n, (nx, ny, n0) x n}
     NT_SCREW_TBB = 16,    // inf_top_bot_bound.hpp over the screw ("screw_gradient_wrong"), params
                           // {twist, r0, delta} then (next row) the node's inverse matrix
+    NT_SDF3D = 17,        // sdf_3d.hpp: a caller-supplied SDF table sampled like the rabbit (cube.hpp),
+                          // params SdfParam below; the table lives in the object's table arena
 };
+
+// NT_SDF3D parameter rows (two consecutive rows of mats[], read as one float array).  Offsets are
+// in floats from the start of the object's table arena and are stored as bit patterns (an arena
+// of several 2^22-entry tables passes 2^24, where floats stop holding every integer).
+enum SdfParam : int32_t {
+    SDF_SX = 0, SDF_SY = 1, SDF_SZ = 2,      // sizes, as floats (<= 512: exact)
+    SDF_GS = 3, SDF_OX = 4, SDF_OY = 5, SDF_OZ = 6,
+    SDF_VMIN = 7, SDF_VMAX = 8,              // range of every value a read can return (0 of the padding included)
+    SDF_TAB = 9,                             // bits: offset of the zero-padded table
+    SDF_LEVELS = 10,                         // number of min/max pyramid levels, as a float
+    SDF_LVL0 = 11,                           // bits: offsets of level 0 .. kSdfMaxLevels-1 (float2 {min, max} entries)
+};
+constexpr int kSdfMaxLevels = 10;            // sizes <= 512: the level-9 grid is at most 2 x 2 x 2
+constexpr int kSdfParams = SDF_LVL0 + kSdfMaxLevels;
+constexpr int kSdfMaxNodes = 8;              // sdf_3d nodes per object
+constexpr int kSdfMinSize = 2, kSdfMaxSize = 512, kSdfMaxEntries = 1 << 22;
+// the arena's first section: the rabbit table, its padding and its block min / max table, at the
+// offsets cube_f / cube_iv read (ifunc_device.hpp kRabbitPadded: 3 * 10240 floats)
+constexpr int kArenaRabbitFloats = 3 * 10240;
 
 enum OpCode : int32_t {
     OP_XFORM = 0,

@@ -90,6 +90,32 @@ def extrusion(size=6, scale=1.0, t=(0, 0, 0)):
     return {"type": "extrusion", "matrix": st(scale, *t), "size": size}
 
 
+def sdf3d_node(table, grid_size, origin, matrix, id=0, sizes=None):
+    """An MP5 "sdf_3d" node that carries its SDF table (object_factory.hpp:352-395): sampled
+    trilinearly like the rabbit, positive values outside.  table: a [z][y][x] nested sequence or
+    array (its shape gives the sizes), or a flat sequence in x + y size_x + z size_x size_y order
+    together with sizes = (size_x, size_y, size_z).  origin: the table box's lower corner; its
+    upper corner is origin + grid_size * size per axis."""
+    shape = getattr(table, "shape", None)
+    if sizes is None:
+        if shape is None:   # nested lists
+            shape = (len(table), len(table[0]), len(table[0][0]))
+            flat = [float(v) for plane in table for row in plane for v in row]
+        else:
+            if len(shape) != 3:
+                raise ValueError("sdf3d_node: a flat table needs sizes = (size_x, size_y, size_z)")
+            flat = [float(v) for v in table.reshape(-1)]
+        sz, sy, sx = (int(s) for s in shape)
+    else:
+        sx, sy, sz = (int(s) for s in sizes)
+        flat = [float(v) for v in (table.reshape(-1) if shape is not None else table)]
+    if len(flat) != sx * sy * sz:
+        raise ValueError("sdf3d_node: the table holds %d values, the sizes ask for %d" % (len(flat), sx * sy * sz))
+    return {"type": "sdf_3d", "id": int(id), "matrix": [float(v) for v in matrix],
+            "size_x": sx, "size_y": sy, "size_z": sz, "grid_size": float(grid_size),
+            "origin_x": float(origin[0]), "origin_y": float(origin[1]), "origin_z": float(origin[2]), "sdf": flat}
+
+
 def random_leaf(rng, box=1.0, types=LEAF_TYPES):
     while True:
         t = rng.choice(types)

@@ -6,6 +6,12 @@
  * declarations :88-134, definitions as cited).  Signatures, argument meaning, ownership and error
  * behaviour are the reference's; the work runs on the GPU (HIP, gfx950).
  *
+ * MP5 node families: the reference factory's primitives and CSG nodes, and "sdf_3d" with its table
+ * in the node (size_x/y/z in [2, 512], at most 2^22 entries, grid_size, origin_x/y/z, "sdf"; at most
+ * 8 per object): sampled trilinearly like the rabbit ("icube"), reads past the table return 0, the
+ * gradient is the analytic in-cell gradient.  Rejected: "rawjscode", an "sdf_3d" without its table
+ * fields, and any "sdf_3d" in implisolid_batch_create.
+ *
  * Thread-safety: like the reference, one global geometry slot and one direct-eval slot; not
  * reentrant.  build_geometry returns after the result is host resident.
  */
