@@ -49,6 +49,7 @@ ABI_SYMBOLS = [
     "implisolid_ob02_unpack", "implisolid_ob02_halo",
     "get_n_size", "get_n_ptr", "get_n", "implisolid_normals_stats", "implisolid_eval_normals",
     "implisolid_slab_emit_normals", "implisolid_slab_normals", "implisolid_slab_download_normals",
+    "implisolid_batch_has_normals", "implisolid_batch_download_normals",
 ]
 
 # implisolid_progress_callback (include/implisolid.h): verts, n_verts, faces, n_faces,
@@ -182,6 +183,8 @@ def lib():
         "implisolid_slab_emit_normals": ([c_void_p, c_void_p], c_int),
         "implisolid_slab_normals": ([c_void_p], c_void_p),
         "implisolid_slab_download_normals": ([c_void_p, fp, c_void_p], c_int),
+        "implisolid_batch_has_normals": ([c_void_p], c_int),
+        "implisolid_batch_download_normals": ([c_void_p, c_int, fp, ctypes.POINTER(ctypes.c_int64)], c_int),
     }
     for name, (args, res) in sig.items():
         try:
@@ -957,13 +960,15 @@ class Batch:
     """A stream of objects polygonised with one mc-settings dict (BASELINE config 5).  n_streams=0:
     merged launches (every stage once for all objects, interpreter kernels); n_streams >= 1: one
     hipGraph per object (JIT tree kernels) replayed over that many streams.  run() is async on
-    `stream`; counts()/download() block."""
+    `stream`; counts()/download() block.  With "normals": {"enabled": 1} in the settings (or
+    normals=True, which merges the key into a copy of them) every run() also computes each object's
+    per-vertex normals on the device, behind its face pass: normals(i), download(i, normals=True)."""
 
-    def __init__(self, shapes, mc_settings, n_streams=4):
+    def __init__(self, shapes, mc_settings, n_streams=4, normals=False):
         L = lib()
         enc = [_s(sh) for sh in shapes]
         arr = (ctypes.c_char_p * len(enc))(*enc)
-        self.h = L.implisolid_batch_create(arr, len(enc), _s(mc_settings), int(n_streams))
+        self.h = L.implisolid_batch_create(arr, len(enc), _s(_with_normals(mc_settings, normals)), int(n_streams))
         if not self.h:
             raise ImplisolidError(last_error() or "implisolid_batch_create failed")
         info = (ctypes.c_int32 * 4)()
@@ -971,6 +976,9 @@ class Batch:
         L.implisolid_batch_info(self.h, info, ctypes.byref(secs))
         self.n, self.n_streams, self.graphs, self.jit_seconds = int(info[0]), int(info[1]), bool(info[2]), secs.value
         self.merged = bool(info[3])
+        # (an older experimental build, IMPLISOLID_LIB, has no such entry: its streams compute none)
+        has = getattr(L, "implisolid_batch_has_normals", None)
+        self.has_normals = bool(has(self.h)) if has else False
 
     def run(self, stream=None):
         if lib().implisolid_batch_run(self.h, stream) != 0:
@@ -982,14 +990,30 @@ class Batch:
             raise ImplisolidError(last_error())
         return int(out[0]), int(out[1]), bool(out[2])
 
-    def download(self, i):
+    def download(self, i, normals=False):
+        """(verts, faces) of object i's last run; with normals=True (verts, faces, normals)."""
         nv, nf, of = self.counts(i)
         v = np.empty((nv, 3), np.float32)
         f = np.empty((nf, 3), np.int32)
         if lib().implisolid_batch_download(self.h, int(i), v.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
                                            f.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))) != 0:
             raise ImplisolidError(last_error())
-        return v, f
+        return (v, f, self.normals(i)) if normals else (v, f)
+
+    def normals(self, i, return_problems=False):
+        """Object i's per-vertex normals of the last run, float32 [nv, 3], the rows of download(i)'s
+        vertices (rows with |g| <= 1e-4 or a non-finite g are -42 g); with return_problems: (normals,
+        the number of such rows).  Raises for a batch created without the "normals" key."""
+        if not self.has_normals:   # (the library says why; no vertex count is read for nothing)
+            lib().implisolid_batch_download_normals(self.h, int(i), None, None)
+            raise ImplisolidError(last_error() or "the batch computes no normals")
+        nv = self.counts(i)[0]
+        out = np.empty((nv, 3), np.float32)
+        bad = ctypes.c_int64(0)
+        if lib().implisolid_batch_download_normals(self.h, int(i), out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                                   ctypes.byref(bad)) != 0:
+            raise ImplisolidError(last_error())
+        return (out, int(bad.value)) if return_problems else out
 
     def close(self):
         if self.h:

@@ -1274,6 +1274,10 @@ struct implisolid_batch {
     DevBuf resets;                       // merged: the fresh engines' buffer resets (ZeroPiece list)
     std::vector<std::unique_ptr<Engine>> engines;
     bool merged = false;                 // one launch per stage for all objects (ObjArgs rows)
+    // the mc settings' "normals" key: every run() also computes each object's per-vertex normals,
+    // behind its face pass (merged: one launch_batch_vertex_normals per group into the engines'
+    // buffers, ObjArgs::normals; per object: Engine::emit_normals).  Off: nothing below exists.
+    bool normals = false;
     DevBuf objs;                         // merged: ObjArgs[n] on the device, shallow objects first
     int depth = 0;
     // merged: objects of tree depth <= kBatchShallowDepth (rows [0, n_shallow)) run the interval and
@@ -1362,6 +1366,7 @@ implisolid_batch* implisolid_batch_create(const char* const* shapes, int n, cons
         // n_streams <= 0: merged launches (the interpreter kernels, every stage once for all
         // objects); otherwise one hipGraph per object (JIT tree kernels when enabled) over streams
         b->merged = n_streams <= 0 && Engine::pruning() > 0;
+        b->normals = st.normals;
         if (b->merged) {
             // the merged kernels keep the objects' list prefix in LDS (kMaxBatchObjects entries) and
             // index every object's refine items with one 32-bit flat index
@@ -1419,7 +1424,7 @@ implisolid_batch* implisolid_batch_create(const char* const* shapes, int n, cons
                 E.set_object(progs[(size_t)i], b->progs.as<Program>() + i);
                 if (timing) ph[1] += tick(tp);
                 E.set_slab(st.resolution, st.box, whole, false, s0);
-                E.arm_merged();
+                E.arm_merged(b->normals);
                 E.detach_resets();
                 if (timing) ph[2] += tick(tp);
             }
@@ -1445,7 +1450,11 @@ implisolid_batch* implisolid_batch_create(const char* const* shapes, int n, cons
                 if (timing) ph[1] += tick(tp);
                 E.set_grid(st.resolution, st.box, 0, 1);
                 if (timing) ph[2] += tick(tp);
+                // the normals' buffer reserved (grown with the vertices by the warm run) and the point
+                // module requested here, before any capture: the captured sequence is launches only
+                if (b->normals) E.stream_normals();
                 E.marching_cubes(s0);
+                if (b->normals) E.emit_normals(s0);
                 if (timing) ph[3] += tick(tp);
             }
         }
@@ -1506,6 +1515,16 @@ implisolid_batch* implisolid_batch_create(const char* const* shapes, int n, cons
                 if (!grew) break;
                 IMPLI_HIP(hipMemcpyAsync(b->objs.p, rows.data(), rows.size() * sizeof(ObjArgs), hipMemcpyHostToDevice, s0));
             }
+            if (b->normals) {   // the normals pass indexes every object's vertices (in whole waves) with 32 bits
+                uint64_t waves = 0;
+                for (int r = 0; r < n; ++r) {
+                    const uint32_t* h = hc.as<uint32_t>() + (size_t)r * kCounterWords;
+                    waves += ((uint64_t)(h[2] - h[5]) + 63) / 64;
+                }
+                if (waves * 64 >= (1ull << 32) - (1ull << 24))
+                    throw InputError("implisolid_batch_create: the objects' vertices exceed the merged normals pass's 32-bit "
+                                     "index; use fewer objects or n_streams >= 1");
+            }
             if (timing) {
                 ph[3] += tick(tp);
                 size_t pool1[4];
@@ -1530,6 +1549,7 @@ implisolid_batch* implisolid_batch_create(const char* const* shapes, int n, cons
                 b->engines[(size_t)i]->eval_field(s0);
                 b->engines[(size_t)i]->count(s0);
                 b->engines[(size_t)i]->emit(nullptr, s0);
+                if (b->normals) b->engines[(size_t)i]->emit_normals(s0);   // the same chain: no branch
             } catch (const std::exception&) {
                 ok = false;
             }
@@ -1577,6 +1597,7 @@ static void batch_merged_enqueue(implisolid_batch* b, hipStream_t s) {
         const ObjArgs* rows = b->objs.as<ObjArgs>() + gr.row0;
         launch_batch_eval(rows, gr.n, gr.depth, gr.vdepth, E0.d_rabbit(), E0.tab_range(), E0.grid(), fill, q);
         launch_batch_mc(rows, gr.n, E0.d_cases(), E0.grid(), q);
+        if (b->normals) launch_batch_vertex_normals(rows, gr.n, gr.depth, E0.d_rabbit(), q);
     }
     for (int k = 1; k < ng; ++k) {
         IMPLI_HIP(hipEventRecord(b->events[(size_t)k], b->streams[(size_t)k - 1]));
@@ -1603,6 +1624,7 @@ int implisolid_batch_run(implisolid_batch* b, void* stream) {
                 b->engines[i]->eval_field(q);
                 b->engines[i]->count(q);
                 b->engines[i]->emit(nullptr, q);
+                if (b->normals) b->engines[i]->emit_normals(q);
             }
         }
         for (int k = 0; k < ns; ++k) {
@@ -1652,6 +1674,30 @@ int implisolid_batch_download(implisolid_batch* b, int i, float* verts, int32_t*
         const SlabCounts c = E.read_counts(b->streams[0], &of);
         if (of) throw HipError("batch object overflowed its output capacity");
         E.download(verts, faces, c, b->streams[0]);
+    } catch (const std::exception& e) {
+        report(e.what(), false);
+        return -1;
+    }
+    return 0;
+}
+
+int implisolid_batch_has_normals(implisolid_batch* b) { return b && b->normals ? 1 : 0; }
+
+int implisolid_batch_download_normals(implisolid_batch* b, int i, float* normals_out, int64_t* problems) {
+    try {
+        if (i < 0 || i >= (int)b->engines.size()) throw InputError("implisolid_batch_download_normals: bad index");
+        if (!b->normals)
+            throw InputError("implisolid_batch_download_normals: the batch computes no normals (its mc settings lack "
+                             "\"normals\": {\"enabled\": 1})");
+        for (auto q : b->streams) IMPLI_HIP(hipStreamSynchronize(q));
+        if (b->merged) IMPLI_HIP(hipDeviceSynchronize());
+        bool of = false;
+        Engine& E = *b->engines[(size_t)i];
+        const SlabCounts c = E.read_counts(b->streams[0], &of);
+        if (of) throw HipError("batch object overflowed its output capacity");
+        uint64_t bad = 0;
+        E.download_normals(normals_out, c, b->streams[0], &bad);
+        if (problems) *problems = (int64_t)bad;
     } catch (const std::exception& e) {
         report(e.what(), false);
         return -1;
@@ -1818,7 +1864,13 @@ void implisolid_batch_destroy(implisolid_batch* b) {
         for (auto e : b->events) g_batch_events[d].push_back(e);
         for (auto q : b->streams) g_batch_streams[d].push_back(q);
     }
+    // the engines own their buffers, the normals' included (Engine::~Engine); the batch's own blocks
+    // have no destructor: released here, the programs after the engines that read them
+    b->engines.clear();
     b->objs.release();
+    b->progs.release();
+    b->counts.release();
+    b->resets.release();
     delete b;
 }
 

@@ -12,16 +12,13 @@ namespace impli {
 // thread (refine) or wave (eval) finds the object of its item by binary search.
 constexpr int kMaxBatchObjects = 1024;
 // align: each object's range rounded up to a multiple of it (64: every wave holds one object)
-__device__ __forceinline__ uint32_t batch_prefix(const ObjArgs* __restrict__ objs, int n, int word, uint32_t mult,
-                                                 uint32_t cap, uint32_t* s_pre, uint32_t align = 1u) {
+// batch_prefix_counts: the prefix of counts the caller loaded, c[k] that of object 4 t + k (256
+// threads, up to 4 objects each; entries past n are ignored)
+__device__ __forceinline__ uint32_t batch_prefix_counts(const uint32_t (&c)[4], int n, uint32_t mult, uint32_t cap,
+                                                        uint32_t* s_pre, uint32_t align) {
     __shared__ uint32_t s_part[4];
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;   // 256 threads, up to 4 objects each
-    uint32_t v[4], c[4] = {0u, 0u, 0u, 0u}, sum = 0;
-    if (n > 0) {   // uniform; the four loads unconditional (a clamped index), so they issue together
-                   // instead of one round trip per guarded load
-#pragma unroll
-        for (int k = 0; k < 4; ++k) c[k] = objs[4 * t + k < n ? 4 * t + k : n - 1].counters[word];
-    }
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    uint32_t v[4], sum = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int o = 4 * t + k;
@@ -45,6 +42,18 @@ __device__ __forceinline__ uint32_t batch_prefix(const ObjArgs* __restrict__ obj
     }
     __syncthreads();
     return s_pre[n];
+}
+// ... of one word of every object's counter block
+__device__ __forceinline__ uint32_t batch_prefix(const ObjArgs* __restrict__ objs, int n, int word, uint32_t mult,
+                                                 uint32_t cap, uint32_t* s_pre, uint32_t align = 1u) {
+    const int t = threadIdx.x;
+    uint32_t c[4] = {0u, 0u, 0u, 0u};
+    if (n > 0) {   // uniform; the four loads unconditional (a clamped index), so they issue together
+                   // instead of one round trip per guarded load
+#pragma unroll
+        for (int k = 0; k < 4; ++k) c[k] = objs[4 * t + k < n ? 4 * t + k : n - 1].counters[word];
+    }
+    return batch_prefix_counts(c, n, mult, cap, s_pre, align);
 }
 __device__ __forceinline__ int batch_object_of(const uint32_t* s_pre, int n, uint32_t i) {   // last o: pre[o] <= i
     int lo = 0, hi = n - 1;

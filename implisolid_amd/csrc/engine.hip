@@ -404,10 +404,17 @@ void Engine::set_grid(int R, const float box[6], int rank, int nranks) {
     set_slab(R, box, slab_partition(R, rank, nranks));   // one halo layer below (owner rule)
 }
 
-void Engine::arm_merged() {
+void Engine::arm_merged(bool normals) {
     if (!have_grid_ || !have_object_ || probe_only_) throw InputError("engine: arm_merged needs an object and a grid");
     if (mark_id_ == 0) mark_id_ = 1;   // the unit marks were reset to 0 with the grid
     marks_valid_ = true;
+    if (normals) stream_normals();
+}
+
+void Engine::stream_normals() {
+    if (!have_grid_ || probe_only_) throw InputError("engine: stream_normals needs a grid");
+    stream_normals_ = true;
+    normals_.reserve((size_t)std::max<int64_t>(cap_v_, 1) * 3 * sizeof(float));
 }
 
 void Engine::set_slab(int R, const float box[6], const SlabRange& sr_in, bool probe_only, hipStream_t setup) {
@@ -497,6 +504,8 @@ bool Engine::ensure_capacity(const SlabCounts& c) {
     grow(verts_, cap_v_, (int64_t)c.n_verts() + 1, 3 * sizeof(float));
     grow(faces_, cap_f_, (int64_t)c.n_faces() + 1, 3 * sizeof(int32_t));
     grow(records_, cap_rec_, (int64_t)c.act_total + 1, sizeof(uint4));
+    // an object stream's normals: one row per vertex the buffer holds (obj_args hands both out)
+    if (stream_normals_) normals_.reserve((size_t)std::max<int64_t>(cap_v_, 1) * 3 * sizeof(float));
     return grew;
 }
 
@@ -837,6 +846,8 @@ ObjArgs Engine::obj_args() const {
     o.claimed = claimed_.as<uint32_t>();
     o.mc = buffers();
     o.mc.offsets = offsets_.as<uint32_t>();
+    o.normals = stream_normals_ ? normals_.as<float>() : nullptr;
+    o.nproblems = stream_normals_ ? const_cast<Engine*>(this)->d_normal_problems() : nullptr;
     return o;
 }
 
@@ -873,6 +884,8 @@ bool Engine::vertex_normals(const float* d_pts, int64_t n, const uint32_t* d_cou
 }
 
 unsigned long long* Engine::d_normal_problems() {
+    // an object stream's passes count in the counter block, which each pass's eval clears
+    if (stream_normals_) return reinterpret_cast<unsigned long long*>(counters_.as<uint32_t>() + kNormalProblemsWord);
     nproblems_.reserve(sizeof(unsigned long long));
     return nproblems_.as<unsigned long long>();
 }
@@ -881,7 +894,8 @@ void Engine::emit_normals(hipStream_t s) {
     if (!have_grid_ || probe_only_) throw InputError("engine: emit_normals needs a slab's emitted vertices");
     normals_.reserve((size_t)std::max<int64_t>(cap_v_, 1) * 3 * sizeof(float));
     unsigned long long* prob = d_normal_problems();
-    IMPLI_HIP(hipMemsetAsync(prob, 0, sizeof(unsigned long long), s));
+    // (an object stream's count lives in the counter block: this pass's eval_field cleared it)
+    if (!stream_normals_) IMPLI_HIP(hipMemsetAsync(prob, 0, sizeof(unsigned long long), s));
     // every vertex the slab emitted (counter words [2] - [5], read on the device: no host round
     // trip), the grid sized by the vertex buffer's capacity, which the emission never writes past
     (void)vertex_normals(verts_.as<float>(), cap_v_, counters_.as<uint32_t>(), normals_.as<float>(), prob, s);

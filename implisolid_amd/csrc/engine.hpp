@@ -111,8 +111,14 @@ public:
     // (an object stream sets up its engines back to back; every later launch of theirs is on it)
     void set_slab(int R, const float box[6], const SlabRange& sr, bool probe_only = false, hipStream_t setup = nullptr);
     // an object stream's merged launches without a warm eval of this engine: the merged fill writes
-    // its unit marks (id 1) from the first pass on
-    void arm_merged();
+    // its unit marks (id 1) from the first pass on.  normals: stream_normals() as well
+    void arm_merged(bool normals = false);
+    // an object stream that computes per-vertex normals in every pass (merged:
+    // launch_batch_vertex_normals; per object: emit_normals): the normals' buffer is reserved here and
+    // grows with the vertex buffer (ensure_capacity), and the -42 rows are counted in the counter
+    // block (kNormalProblemsWord), which every pass's eval clears with its other words -- the passes,
+    // captured or not, are kernel launches only
+    void stream_normals();
     void detach_resets() { resets_ = nullptr; }
     // the pruned eval's interval and fill passes alone (no field values), then per stored sample
     // layer of the slab: the number of bricks listed for evaluation (blocking)
@@ -268,6 +274,7 @@ private:
     DevBuf prog_, rabbit_, cases_;
     DevBuf offsets_, cmodes_, ccls_, clist_, modes_, cls_, fill_, blist_, field_, signs_, scan_blk_, unit_cnt_, unit_part_, unit_cmask_, ulist_, upart_, umark_, counters_, lmodes_, claimed_, vid_, records_, verts_, faces_;
     DevBuf normals_, nproblems_;   // the normals passes' output (allocated on first use) and their -42 count
+    bool stream_normals_ = false;  // arm_merged(true): normals_ is kept sized like verts_
     HostBuf hproblems_;            // ... and that count's pinned landing zone
     int64_t cap_v_ = 0, cap_f_ = 0, cap_rec_ = 0;
     bool timing_ = false;

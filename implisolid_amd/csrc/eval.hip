@@ -27,6 +27,7 @@
 #include "kernels.hpp"
 #include "jit.hpp"
 #include "batch_device.hpp"
+#include "ob02_device.hpp"
 
 namespace impli {
 
@@ -51,13 +52,7 @@ __global__ __launch_bounds__(256) void k_eval_field(const Program* __restrict__ 
     field[w * (kBX * kBY) + lane] = f;   // eval_shape: field (zero) += value
 }
 
-// A program pointer loaded from memory (ObjArgs::prog of a merged object stream) is generic: loads
-// through it are flat vector loads, so every instruction fetch of the interpreter was a memory round
-// trip and its fields and stack indices VGPR values.  The program is read-only during a launch, so
-// the merged kernels read it through the constant address space (scalar loads, uniform indices).
-typedef const __attribute__((address_space(4))) Program* ProgC;
-__device__ __forceinline__ ProgC prog_const(const Program* p) { return (ProgC)p; }
-
+// (the merged kernels read an object's program through ProgC, ifunc_device.hpp)
 template <int D, class ProgP = const Program*>
 struct InterpIv {   // the interval interpreter (ifunc_interval.hpp eval_iv)
     ProgP prog;
@@ -504,6 +499,44 @@ __global__ __launch_bounds__(256) void k_eval_claimed_b(const ObjArgs* __restric
     }
 }
 
+// The object stream's per-vertex normals: ob02.hip k_vertex_normals' pass (ob02_device.hpp
+// vertex_normal_at, the rule of mcc2.cpp:852-871) over the vertices every object of a merged pass
+// emitted, in one launch behind the face pass.  One flat index over the objects' emitted counts,
+// each rounded up to whole waves, so a wave's object -- its program (read through ProgC: scalar
+// instruction fetches), buffers and problem count -- is uniform; an object that emitted nothing has
+// no wave.  A lane past its object's count evaluates the object's vertex 0 (its load is issued
+// unconditionally, like the others') and stores nothing.  The -42 rows go to the object's own count
+// (ObjArgs::nproblems, a word pair of its counter block: the pass's coarse kernel cleared it).
+__device__ __forceinline__ uint32_t batch_emitted(const ObjArgs& o) {
+    return (uint32_t)ob::counted_points(o.counters, o.mc.cap_v);
+}
+template <int D>
+__global__ __launch_bounds__(256) void k_batch_vertex_normals(const ObjArgs* __restrict__ objs, int n,
+                                                              const float* __restrict__ tab) {
+    __shared__ uint32_t s_pre[kMaxBatchObjects + 4];
+    uint32_t c[4] = {0u, 0u, 0u, 0u};
+    if (n > 0) {   // uniform; clamped indices: the loads issue together (batch_prefix)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) c[k] = batch_emitted(objs[4 * (int)threadIdx.x + k < n ? 4 * (int)threadIdx.x + k : n - 1]);
+    }
+    const uint32_t total = batch_prefix_counts(c, n, 1u, 0xffffffffu, s_pre, 64u);
+    for (uint32_t i0 = blockIdx.x * 256 + (threadIdx.x & ~63u); i0 < total; i0 += gridDim.x * 256) {
+        const int k = __builtin_amdgcn_readfirstlane(batch_object_of(s_pre, n, i0));
+        const ObjArgs& o = objs[k];
+        const uint32_t i = i0 + (threadIdx.x & 63u) - s_pre[k];
+        const bool live = i < batch_emitted(o);
+        const float* __restrict__ p = o.mc.verts + 3 * (size_t)(live ? i : 0u);
+        const float x = p[0], y = p[1], z = p[2];
+        ob::V3 nrm;
+        const bool bad = ob::vertex_normal_at(ob::InterpPt<D, ProgC>{prog_const(o.prog), tab}, x, y, z, nrm);
+        if (live) {
+            float* __restrict__ q = o.normals + 3 * (size_t)i;
+            q[0] = nrm.x; q[1] = nrm.y; q[2] = nrm.z;
+        }
+        ob::count_normal_problems(bad && live, o.nproblems);
+    }
+}
+
 // sign bitmap of a fully evaluated field (unpruned path), in storage order: one wave per brick
 // layer reads its 256 contiguous bytes (the PMC fetch calibration, tools/pmc_traffic.py) and writes
 // the layer's kBY sign pieces, as the pruned eval does
@@ -727,6 +760,18 @@ void launch_batch_eval(const ObjArgs* d_objs, int n, int depth, int vdepth, cons
         IMPLI_BATCH_EVAL(16, 1, 16);
     }
 #undef IMPLI_BATCH_EVAL
+}
+
+// (a fixed grid like the other flat merged kernels': the counts live on the device)
+constexpr unsigned kBatchNormalsBlocks = 2048;
+
+void launch_batch_vertex_normals(const ObjArgs* d_objs, int n, int depth, const float* d_rabbit, hipStream_t s) {
+    if (n <= 0) return;
+    if (n > kMaxBatchObjects) throw std::runtime_error("merged object stream: more than 1024 objects per launch");
+    if (depth > 16) throw std::runtime_error("merged normals: a program's stacks exceed the kernel's (depth " + std::to_string(depth) + ")");
+    if (depth <= kBatchShallowDepth) k_batch_vertex_normals<kBatchShallowDepth><<<kBatchNormalsBlocks, 256, 0, s>>>(d_objs, n, d_rabbit);
+    else if (depth <= 12) k_batch_vertex_normals<12><<<kBatchNormalsBlocks, 256, 0, s>>>(d_objs, n, d_rabbit);
+    else k_batch_vertex_normals<16><<<kBatchNormalsBlocks, 256, 0, s>>>(d_objs, n, d_rabbit);
 }
 
 void launch_eval_points(const Program* d_prog, int depth, const float* d_rabbit, const float* d_xyz, int64_t n,

@@ -46,6 +46,11 @@ static_assert(kBX * kBY == 64 && (kBX == 8 || kBX == 16 || kBX == 32), "a brick 
 constexpr int kBrickListWord = 12, kCoarseListWord = 13, kOverflowWord = 16, kCounterWords = 32;
 // [15]: the merged object-stream eval's claimed candidates (eval_listed_deferred)
 constexpr int kClaimedWord = 15;
+// [20, 22): an object stream's merged normals pass counts its -42 rows here (one 64-bit count,
+// cleared with the block by the pass's coarse kernel; kernels.hpp ObjArgs::nproblems)
+constexpr int kNormalProblemsWord = 20;
+static_assert(kNormalProblemsWord % 2 == 0 && kNormalProblemsWord >= kOverflowWord + 4 && kNormalProblemsWord + 2 <= kCounterWords,
+              "the normals' problem count: an aligned word pair past the overflow flags");
 enum BrickClass : uint8_t { kBrickMixed = 0, kBrickPos = 1, kBrickNeg = 2, kBrickNoFill = 4 };
 // fill[b] (written by the pruned eval) = class | fill class << 4 | flags.  Fill class kBrickPos /
 // kBrickNeg: the brick's sign pieces are constant (no cell corner in it needs its exact value unless

@@ -769,24 +769,48 @@ __device__ __forceinline__ float eval_f(const Program* __restrict__ prog, const 
     return vf[0];
 }
 
-// joint (f, grad): every node's gradient is M^-T * (selected child gradient)
-template <int D>
-__device__ __forceinline__ float eval_fg(const Program* __restrict__ prog, const float* __restrict__ tab, float x,
+// A program pointer loaded from memory (ObjArgs::prog of a merged object stream) is generic: loads
+// through it are flat vector loads, so every instruction fetch of the interpreter was a memory round
+// trip and its fields and stack indices VGPR values.  The program is read-only during a launch, so
+// the merged kernels read it through the constant address space (scalar loads, uniform indices).
+typedef const __attribute__((address_space(4))) Program* ProgC;
+__device__ __forceinline__ ProgC prog_const(const Program* p) { return (ProgC)p; }
+
+// one instruction through any program pointer (field by field: an Instr in another address space
+// does not bind to the copy constructor's reference)
+template <class ProgP>
+__device__ __forceinline__ Instr instr_at(ProgP prog, int pc) {
+    const auto& s = prog->instr[pc];
+    Instr I;
+    I.op = s.op; I.type = s.type; I.mat = s.mat; I.csg = s.csg;
+    I.skip_csg = s.skip_csg; I.skip_child = s.skip_child; I.skip_to = s.skip_to; I.prm = s.prm;
+    return I;
+}
+
+// a matrix / parameter row as a generic pointer (after inlining, the address space is inferred
+// back from the cast, so constant-space rows are still read with scalar loads)
+template <class ProgP>
+__device__ __forceinline__ const float* mat_row(ProgP prog, int i) { return (const float*)prog->mats[i]; }
+
+// joint (f, grad): every node's gradient is M^-T * (selected child gradient).  ProgP: const
+// Program*, or ProgC where the pointer was loaded from memory (the object stream's normals)
+template <int D, class ProgP = const Program*>
+__device__ __forceinline__ float eval_fg(ProgP __restrict__ prog, const float* __restrict__ tab, float x,
                                          float y, float z, V3& g_out) {
     float px[D], py[D], pz[D], vf[D], gx[D], gy[D], gz[D];
     int sp = 0, vp = 0;
     px[0] = x; py[0] = y; pz[0] = z;
     const int n = prog->n_instr;
     for (int pc = 0; pc < n; ++pc) {
-        const Instr I = prog->instr[pc];
+        const Instr I = instr_at(prog, pc);
         if (I.op == OP_XFORM) {
-            const V3 q = xform(prog->mats[I.mat], px[sp], py[sp], pz[sp]);
+            const V3 q = xform(mat_row(prog, I.mat), px[sp], py[sp], pz[sp]);
             ++sp;
             px[sp] = q.x; py[sp] = q.y; pz[sp] = q.z;
         } else if (I.op == OP_PRIM) {
-            const float f = prim_f(I.type, tab, prog->mats[I.prm], px[sp], py[sp], pz[sp]);
-            V3 g = prim_g(I.type, tab, prog->mats[I.prm], px[sp], py[sp], pz[sp]);
-            g = grad_xform(prog->mats[I.mat], g);
+            const float f = prim_f(I.type, tab, mat_row(prog, I.prm), px[sp], py[sp], pz[sp]);
+            V3 g = prim_g(I.type, tab, mat_row(prog, I.prm), px[sp], py[sp], pz[sp]);
+            g = grad_xform(mat_row(prog, I.mat), g);
             vf[vp] = f; gx[vp] = g.x; gy[vp] = g.y; gz[vp] = g.z;
             ++vp;
             --sp;
@@ -799,7 +823,7 @@ __device__ __forceinline__ float eval_fg(const Program* __restrict__ prog, const
             const float f = (I.type == NT_UNION) ? ((f1 > f2) ? f1 : f2)
                           : (I.type == NT_INTERSECTION) ? ((f1 > f2) ? f2 : f1)
                                                        : ((f1 < -f2) ? f1 : -f2);
-            const V3 g = grad_xform(prog->mats[I.mat], first ? g1 : g2);
+            const V3 g = grad_xform(mat_row(prog, I.mat), first ? g1 : g2);
             vf[vp - 1] = f; gx[vp - 1] = g.x; gy[vp - 1] = g.y; gz[vp - 1] = g.z;
             --sp;
         }

@@ -404,24 +404,9 @@ __device__ __forceinline__ uint32_t mode_of(uint64_t modes, int csg);
 // skipped and their decision kept.  The stacks are kept as separate scalar arrays (structure of
 // arrays) so that the uniform-index accesses stay in VGPRs (arrays of Iv structs were demoted to
 // scratch).
-// one instruction through any program pointer (field by field: an Instr in another address space
-// does not bind to the copy constructor's reference)
-template <class ProgP>
-__device__ __forceinline__ Instr instr_at(ProgP prog, int pc) {
-    const auto& s = prog->instr[pc];
-    Instr I;
-    I.op = s.op; I.type = s.type; I.mat = s.mat; I.csg = s.csg;
-    I.skip_csg = s.skip_csg; I.skip_child = s.skip_child; I.skip_to = s.skip_to; I.prm = s.prm;
-    return I;
-}
-
-// a matrix / parameter row as a generic pointer (after inlining, the address space is inferred
-// back from the cast, so constant-space rows are still read with scalar loads)
-template <class ProgP>
-__device__ __forceinline__ const float* mat_row(ProgP prog, int i) { return (const float*)prog->mats[i]; }
-
 // ProgP: the program pointer -- const Program*, or a constant-address-space pointer when it was
-// loaded from memory (merged object streams: scalar loads of the instructions, eval.hip ProgC)
+// loaded from memory (merged object streams: scalar loads of the instructions, ifunc_device.hpp
+// ProgC, instr_at, mat_row)
 template <int D, class ProgP>
 __device__ __forceinline__ Iv eval_iv(ProgP __restrict__ prog, const float* __restrict__ tab,
                                       float2 tab_range, Box p0, uint64_t modes_in, uint64_t& modes) {

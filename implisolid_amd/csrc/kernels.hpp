@@ -94,6 +94,10 @@ struct ObjArgs {
     uint32_t* counters;
     uint32_t* claimed;   // the merged eval's claimed candidates, appended at counters[kClaimedWord]
     MCBuffers mc;
+    // a stream that computes normals (launch_batch_vertex_normals), else null: 3 floats per vertex,
+    // sized like mc.verts, and the object's count of -42 rows (counters + kNormalProblemsWord)
+    float* normals;
+    unsigned long long* nproblems;
 };
 // eval (interval passes, fill, listed bricks) and MC (count, scan, vertices, faces) of n objects;
 // blocks per object are capped for the grid-stride kernels (small grids: most blocks would idle)
@@ -115,5 +119,9 @@ constexpr int kBatchShallowDepth = 9;
 // 0.545 for one (profiles/r04x_*): concurrent merged kernels contend more than they overlap.
 constexpr int kBatchGroups = 1;
 void launch_batch_mc(const ObjArgs* d_objs, int n, const CaseInfo* d_cases, const GridDesc& g, hipStream_t s);
+// the normals (launch_vertex_normals' rule) of the vertices every one of the n objects emitted, into
+// rows[k].normals, the -42 rows counted in *rows[k].nproblems: one launch behind launch_batch_mc;
+// depth: the deepest program's (the stack classes of launch_batch_eval)
+void launch_batch_vertex_normals(const ObjArgs* rows, int n, int depth, const float* d_rabbit, hipStream_t s);
 
 }  // namespace impli

@@ -20,10 +20,11 @@ constexpr int kBisectCap = 200;                      // the reference has no cap
 
 __device__ __forceinline__ float norm2f(float x, float y, float z) { return sqrtf(x * x + y * y + z * z); }
 
-// the node-program interpreter (ifunc_device.hpp, stack capacity D) as an evaluator
-template <int D>
+// the node-program interpreter (ifunc_device.hpp, stack capacity D) as an evaluator.  ProgP: const
+// Program*, or dev::ProgC for a pointer loaded from memory (the object stream's normals; fg only)
+template <int D, class ProgP = const Program*>
 struct InterpPt {
-    const Program* prog;
+    ProgP prog;
     const float* tab;
     __device__ __forceinline__ float f(float x, float y, float z) const { return dev::eval_f<D>(prog, tab, x, y, z); }
     __device__ __forceinline__ float fg(float x, float y, float z, V3& g) const {
@@ -639,21 +640,35 @@ __device__ __forceinline__ void points_body(const Ev& ev, const float* __restric
 // division) is that quotient (tests/test_cpu_normals.py checks both).  A NaN norm fails the
 // comparison, so a non-finite gradient takes the -42 branch and stays non-finite.  The -42 rows are
 // counted per wave (ballot) with one atomic per wave that has any.
+// vertex_normal_at: the rule at one point (the normal, and whether it took the -42 branch);
+// count_normal_problems: the wave's count (every lane of the wave calls it).  Both passes are these
+// two: vertex_normals_body over one object's points, and the object stream's merged pass over every
+// object's vertices (eval.hip k_batch_vertex_normals).
+template <class Ev>
+__device__ __forceinline__ bool vertex_normal_at(const Ev& ev, float x, float y, float z, V3& nrm) {
+    V3 g;
+    (void)ev.fg(x, y, z, g);
+    const float norm = norm2f(g.x, g.y, g.z);
+    const bool bad = !(norm > 0.0001f);
+    const float factor = bad ? -42.0f : -1.0f / norm;
+    nrm = V3{g.x * factor, g.y * factor, g.z * factor};
+    return bad;
+}
+__device__ __forceinline__ void count_normal_problems(bool bad, unsigned long long* __restrict__ problems) {
+    const uint64_t m = (uint64_t)__ballot(bad);
+    if (m && (threadIdx.x & 63) == 0) atomicAdd(problems, (unsigned long long)__popcll(m));
+}
 template <class Ev>
 __device__ __forceinline__ void vertex_normals_body(const Ev& ev, const float* __restrict__ P, int64_t n,
                                                     float* __restrict__ N, unsigned long long* __restrict__ problems) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     bool bad = false;
     if (i < n) {
-        V3 g;
-        (void)ev.fg(P[3 * i], P[3 * i + 1], P[3 * i + 2], g);
-        const float norm = norm2f(g.x, g.y, g.z);
-        bad = !(norm > 0.0001f);
-        const float factor = bad ? -42.0f : -1.0f / norm;
-        N[3 * i] = g.x * factor; N[3 * i + 1] = g.y * factor; N[3 * i + 2] = g.z * factor;
+        V3 nrm;
+        bad = vertex_normal_at(ev, P[3 * i], P[3 * i + 1], P[3 * i + 2], nrm);
+        N[3 * i] = nrm.x; N[3 * i + 1] = nrm.y; N[3 * i + 2] = nrm.z;
     }
-    const uint64_t m = (uint64_t)__ballot(bad);
-    if (m && (threadIdx.x & 63) == 0) atomicAdd(problems, (unsigned long long)__popcll(m));
+    count_normal_problems(bad, problems);
 }
 
 // the number of points of a pass whose count lives on the device: a slab's emitted vertices

@@ -74,8 +74,8 @@ void* get_v_ptr(void);
    A build without the key exposes nothing, also directly after one that had normals.  Intermediate
    meshes carry no normals: inside a progress callback get_n_size() is 0; the final mesh has them.
    With implisolid_set_devices each slab's device computes the normals of the vertices it emitted
-   (after a refinement: the device the loop ran on).  The object stream (implisolid_batch_*) ignores
-   the key.  implisolid_normals_stats: out = [normals computed, rows that took the -42 branch] of the
+   (after a refinement: the device the loop ran on).  The object stream (implisolid_batch_*) honours
+   the key too: implisolid_batch_download_normals.  implisolid_normals_stats: out = [normals computed, rows that took the -42 branch] of the
    last build; 0, or -1 with implisolid_last_error(). */
 int get_n_size(void);
 void* get_n_ptr(void);
@@ -324,13 +324,25 @@ int implisolid_slab_brick_stats(implisolid_slab* s, int64_t out[3]);
  *     into `stream`.
  * run is async on `stream`; counts and download block.  info = {objects, streams, graphs (1/0),
  * merged (1/0)} and the JIT compile seconds. */
-/* The mc settings' "normals" key is ignored here: an object stream computes no normals. */
+/* With the mc settings' "normals": {"enabled": 1} (read as build_geometry reads it) every run() also
+ * computes each object's per-vertex normals (mcc2.cpp:852-871, as get_n_ptr's), stream-ordered behind
+ * its face pass with no host round trip: merged, one more launch per depth class for all objects;
+ * per object, one more kernel at the end of its graph (or of its direct launches).  Without the key
+ * run() enqueues what it always did and no normals buffer exists.
+ *   has_normals       1 if the batch was created with the key, else 0
+ *   download_normals  blocking, synchronises like download: copies 3 * n_verts floats, the rows of
+ *                     download's vertices; *problems (may be NULL) = that object's rows that took the
+ *                     -42 branch in the last run.  -1 with implisolid_last_error() for a bad index and
+ *                     for a batch created without the key (no normals exist: an error, not an empty
+ *                     result). */
 typedef struct implisolid_batch implisolid_batch;
 implisolid_batch* implisolid_batch_create(const char* const* shapes, int n, const char* mc_json, int n_streams);
 int implisolid_batch_run(implisolid_batch* b, void* stream);
 int implisolid_batch_info(implisolid_batch* b, int32_t out[4], double* jit_seconds);
 int implisolid_batch_counts(implisolid_batch* b, int i, uint32_t out[3]);
 int implisolid_batch_download(implisolid_batch* b, int i, float* verts, int32_t* faces);
+int implisolid_batch_has_normals(implisolid_batch* b);
+int implisolid_batch_download_normals(implisolid_batch* b, int i, float* normals_out, int64_t* problems);
 void implisolid_batch_destroy(implisolid_batch* b);
 
 /* The OB02 loop (polygonizer steps 1-3, polygonizer_algorithm_ob02.hpp:74-157) on one Z-slab shard of
