@@ -50,6 +50,8 @@ ABI_SYMBOLS = [
     "get_n_size", "get_n_ptr", "get_n", "implisolid_normals_stats", "implisolid_eval_normals",
     "implisolid_slab_emit_normals", "implisolid_slab_normals", "implisolid_slab_download_normals",
     "implisolid_batch_has_normals", "implisolid_batch_download_normals",
+    "implisolid_bounds", "implisolid_bounds_edges", "implisolid_fit_box", "implisolid_parse_fit_box",
+    "implisolid_last_fit_box", "implisolid_debug_bounds_ms",
 ]
 
 # implisolid_progress_callback (include/implisolid.h): verts, n_verts, faces, n_faces,
@@ -185,6 +187,12 @@ def lib():
         "implisolid_slab_download_normals": ([c_void_p, fp, c_void_p], c_int),
         "implisolid_batch_has_normals": ([c_void_p], c_int),
         "implisolid_batch_download_normals": ([c_void_p, c_int, fp, ctypes.POINTER(ctypes.c_int64)], c_int),
+        "implisolid_bounds": ([c_char_p, c_int, fp, c_int, fp, ctypes.POINTER(ctypes.c_int64)], c_int),
+        "implisolid_bounds_edges": ([fp, c_int, fp], c_int),
+        "implisolid_fit_box": ([fp, fp, c_int, c_int, fp], c_int),
+        "implisolid_parse_fit_box": ([c_char_p, ip], c_int),
+        "implisolid_last_fit_box": ([fp], c_int),
+        "implisolid_debug_bounds_ms": ([c_int], ctypes.c_double),
     }
     for name, (args, res) in sig.items():
         try:
@@ -642,6 +650,74 @@ def debug_intervals(shape, boxes, variant=0, modes_in=None, ignore_root_matrix=F
     if rc != 0:
         raise ImplisolidError(last_error())
     return iv, mo
+
+
+def _box6(box, what):
+    b = np.ascontiguousarray(box, np.float32).reshape(-1)
+    if b.size != 6:
+        raise ValueError("%s: a box is six floats {xmin, xmax, ymin, ymax, zmin, zmax}" % what)
+    return b
+
+
+def bounds(shape, search_box, depth, ignore_root_matrix=False):
+    """The axis-aligned bounds of the solid inside search_box {xmin, xmax, ymin, ymax, zmin, zmax},
+    from the interval evaluator on a 2^depth-cell edge table (depth in [3, 10]; include/implisolid.h
+    implisolid_bounds).  Returns (found, box float32[6], stats): found False means the solid is
+    empty in the search box (box == search_box); stats = [boxes bounded, boxes skipped as inside the
+    running bounds, longest list, reruns after a list overflow]."""
+    fp = ctypes.POINTER(ctypes.c_float)
+    sb = _box6(search_box, "bounds")
+    out = np.empty(6, np.float32)
+    stats = (ctypes.c_int64 * 4)()
+    rc = lib().implisolid_bounds(_s(shape), int(bool(ignore_root_matrix)), sb.ctypes.data_as(fp), int(depth),
+                                 out.ctypes.data_as(fp), stats)
+    if rc < 0:
+        raise ImplisolidError(last_error())
+    return bool(rc), out, [int(v) for v in stats]
+
+
+def bounds_edges(search_box, depth):
+    """Host only: the edge table of bounds(), float32 [3, 2^depth + 1] (x, y, z rows)."""
+    fp = ctypes.POINTER(ctypes.c_float)
+    sb = _box6(search_box, "bounds_edges")
+    if not 3 <= int(depth) <= 10:
+        raise ImplisolidError("bounds_edges: depth must be in [3, 10]")
+    out = np.empty((3, (1 << int(depth)) + 1), np.float32)
+    if lib().implisolid_bounds_edges(sb.ctypes.data_as(fp), int(depth), out.ctypes.data_as(fp)) != 0:
+        raise ImplisolidError(last_error())
+    return out
+
+
+def fit_box(search_box, bounds_box, resolution, margin=2):
+    """Host only: the sampling box (float32[6]) that puts bounds_box on resolution - 2 margin cells
+    with margin cells around it, clipped to search_box (implisolid_fit_box)."""
+    fp = ctypes.POINTER(ctypes.c_float)
+    sb, bb = _box6(search_box, "fit_box"), _box6(bounds_box, "fit_box")
+    out = np.empty(6, np.float32)
+    if lib().implisolid_fit_box(sb.ctypes.data_as(fp), bb.ctypes.data_as(fp), int(resolution), int(margin),
+                                out.ctypes.data_as(fp)) != 0:
+        raise ImplisolidError(last_error())
+    return out
+
+
+def parse_fit_box(mc_settings):
+    """Host only: the "fit_box" settings key as a build reads it: dict(enabled, depth, margin)."""
+    out = (ctypes.c_int32 * 3)()
+    if lib().implisolid_parse_fit_box(_s(mc_settings), out) != 0:
+        raise ImplisolidError(last_error())
+    return {"enabled": int(out[0]), "depth": int(out[1]), "margin": int(out[2])}
+
+
+def last_fit_box():
+    """The box (float32[6]) the last build_geometry used if the "fit_box" key fitted it, else None."""
+    out = np.empty(6, np.float32)
+    return out if lib().implisolid_last_fit_box(out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))) == 1 else None
+
+
+def debug_bounds_ms(enable=True):
+    """Diagnostics: switch HIP-event timing of the bounds descent's level launches on or off; returns
+    the last timed descent's milliseconds (-1.0: none yet)."""
+    return float(lib().implisolid_debug_bounds_ms(int(bool(enable))))
 
 
 def debug_eval_modes(shape, pts, modes, ignore_root_matrix=False):

@@ -173,6 +173,7 @@ struct SlabEngine {           // one slab's engine and stream on its device, kep
     }
 };
 std::vector<std::unique_ptr<SlabEngine>> g_slab_engines;
+void ensure_slab_engines();
 
 // polygonize_step_0 on g_devices: balanced cuts (cached per object and grid), every slab evaluated
 // and counted on its device concurrently, vertex / face offsets from the counts (host), emission,
@@ -183,15 +184,7 @@ void multi_device_mc(const Program& prog, const ObjectTables& tabs, const MCSett
                      PinnedVec<int32_t>& faces, PinnedVec<float>* normals = nullptr, int64_t* problems = nullptr) {
     DeviceGuard guard;
     const int n = (int)g_devices.size();
-    while ((int)g_slab_engines.size() < n) {
-        const int d = g_devices[g_slab_engines.size()];
-        IMPLI_HIP(hipSetDevice(d));
-        std::unique_ptr<SlabEngine> se(new SlabEngine());
-        se->device = d;
-        IMPLI_HIP(hipStreamCreateWithFlags(&se->stream, hipStreamNonBlocking));
-        se->engine.reset(new Engine());
-        g_slab_engines.push_back(std::move(se));
-    }
+    ensure_slab_engines();
     static std::string cut_key;
     static std::vector<int> cuts;
     std::string key((const char*)&prog, sizeof(Program));
@@ -249,16 +242,151 @@ void multi_device_mc(const Program& prog, const ObjectTables& tabs, const MCSett
     }
 }
 
-void grand_algorithm(const char* shape_json, const MCSettings& st, const CallSpecs& cs) {   // mcc2.cpp:309-444
+// ---- bounds of the solid (implisolid_bounds, the "fit_box" settings key) ------------------------
+// The descent of eval.hip's k_bounds_level on the current device: E lends its scratch buffers (10:
+// state and edge table, 11-14: the two lists), d_prog / d_tab are the object's program and tables
+// there.  The only read-back is the state block, after the last level; a raised overflow flag voids
+// the run, the lists grow and the descent runs again.  Returns whether the solid has bounds in
+// `search` (else out = search); stats (nullable): boxes bounded, boxes skipped as inside the running
+// bounds, longest list, reruns after overflow.
+bool g_bounds_timing = false;   // implisolid_debug_bounds_ms: HIP events around the level launches
+double g_bounds_ms = -1.0;
+
+uint32_t bounds_list_capacity(int depth) {
+    // default: 8 N^2 boxes (a surface crossing the whole box lists about 6 N^2 at the last level)
+    uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(8ull << (2 * depth), 4096), 1ull << 21);
+    if (const char* e = std::getenv("IMPLISOLID_BOUNDS_LIST")) {   // read at each call (tests force the rerun path)
+        const long long v = std::atoll(e);
+        if (v > 0) cap = (uint64_t)v;
+    }
+    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(cap, 1), kBoundsMaxList);
+}
+
+bool compute_bounds(Engine& E, hipStream_t s, const Program* d_prog, int prog_depth, const float* d_tab,
+                    const float search[6], int depth, float out[6], int64_t stats[4]) {
+    const int N = 1 << depth;
+    std::vector<float> edges((size_t)3 * (N + 1));
+    bounds_edges(search, depth, edges.data());   // validates depth and box (InputError)
+    constexpr size_t kStateBytes = 256;
+    static_assert(sizeof(BoundsState) <= kStateBytes, "the edge table follows the state block");
+    DevBuf& dst = E.scratch(10);
+    dst.reserve(kStateBytes + edges.size() * sizeof(float));
+    BoundsState* d_state = dst.as<BoundsState>();
+    float* d_edges = reinterpret_cast<float*>(dst.as<char>() + kStateBytes);
+    IMPLI_HIP(hipMemcpyAsync(d_edges, edges.data(), edges.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    uint32_t cap = bounds_list_capacity(depth);
+    int64_t reruns = 0;
+    BoundsState h{};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    struct EvFree {
+        hipEvent_t* e;
+        ~EvFree() { for (int k = 0; k < 2; ++k) if (e[k]) (void)hipEventDestroy(e[k]); }
+    } ev_free{ev};
+    if (g_bounds_timing) for (auto& e : ev) IMPLI_HIP(hipEventCreate(&e));
+    for (;;) {
+        uint32_t* d_box[2];
+        uint64_t* d_modes[2];
+        for (int k = 0; k < 2; ++k) {
+            E.scratch(11 + k).reserve((size_t)cap * sizeof(uint32_t));
+            E.scratch(13 + k).reserve((size_t)cap * sizeof(uint64_t));
+            d_box[k] = E.scratch(11 + k).as<uint32_t>();
+            d_modes[k] = E.scratch(13 + k).as<uint64_t>();
+        }
+        if (ev[0]) IMPLI_HIP(hipEventRecord(ev[0], s));
+        launch_bounds_levels(d_prog, prog_depth, d_tab, E.tab_range(), d_edges, depth, d_box, d_modes, cap, d_state, s);
+        IMPLI_HIP(hipGetLastError());
+        if (ev[1]) IMPLI_HIP(hipEventRecord(ev[1], s));
+        IMPLI_HIP(hipMemcpyAsync(&h, d_state, sizeof h, hipMemcpyDeviceToHost, s));
+        IMPLI_HIP(hipStreamSynchronize(s));
+        if (!h.overflow) break;
+        if (cap >= kBoundsMaxList) throw HipError("bounds: list overflow at the largest capacity");
+        uint64_t want = 2ull * cap;   // the counts kept counting past the capacity: at least that many
+        for (int l = kBoundsMinDepth; l < depth; ++l) want = std::max<uint64_t>(want, h.count[l]);
+        cap = (uint32_t)std::min<uint64_t>(want, kBoundsMaxList);
+        ++reruns;
+    }
+    if (ev[0]) {
+        float ms = 0.f;
+        IMPLI_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        g_bounds_ms = ms;
+    }
+    const bool found = h.key[0] != 0xffffffffu;
+    for (int a = 0; a < 6; ++a) {
+        const uint32_t bits = bounds_key_bits(h.key[a]);
+        float f;
+        std::memcpy(&f, &bits, sizeof f);
+        out[a] = found ? f : search[a];
+    }
+    if (stats) {
+        stats[0] = (int64_t)h.evaluated;
+        stats[1] = (int64_t)h.skipped;
+        stats[2] = 0;
+        for (int l = kBoundsMinDepth; l < depth; ++l) stats[2] = std::max<int64_t>(stats[2], h.count[l]);
+        stats[3] = reruns;
+    }
+    return found;
+}
+
+float g_fit_box[6] = {};     // implisolid_last_fit_box: the box the last build used, if it was fitted
+bool g_fit_box_valid = false;
+// callers whose grid is fixed by their caller (a slab of the settings box) or shared by all objects
+// (an object stream) cannot honour the key: an enabled "fit_box" is an error there, not ignored
+void refuse_fit_box(const MCSettings& st, const char* who) {
+    if (st.fit_box)
+        throw InputError(std::string(who) + ": the mc settings enable \"fit_box\", which only build_geometry honours (the grid here "
+                         "is the caller's); fit the box first (implisolid_bounds, implisolid_fit_box) and pass it as \"box\"");
+}
+
+void ensure_slab_engines() {   // one engine and stream per entry of g_devices
+    while (g_slab_engines.size() < g_devices.size()) {
+        const int d = g_devices[g_slab_engines.size()];
+        IMPLI_HIP(hipSetDevice(d));
+        std::unique_ptr<SlabEngine> se(new SlabEngine());
+        se->device = d;
+        IMPLI_HIP(hipStreamCreateWithFlags(&se->stream, hipStreamNonBlocking));
+        se->engine.reset(new Engine());
+        g_slab_engines.push_back(std::move(se));
+    }
+}
+
+// "fit_box": st.box becomes the fitted box (host.hpp fit_box) of the solid's bounds inside it, found
+// on the build's device: the current one, or g_devices[0].  An empty solid keeps the box.
+void fit_settings_box(Engine& E, hipStream_t s, const Program& prog, const ObjectTables& tabs, MCSettings& st) {
+    float bounds[6], fitted[6];
+    bool found;
+    if (!g_devices.empty()) {
+        DeviceGuard guard;
+        ensure_slab_engines();
+        SlabEngine& se = *g_slab_engines[0];
+        IMPLI_HIP(hipSetDevice(se.device));
+        se.engine->set_object(prog, nullptr, &tabs);
+        found = compute_bounds(*se.engine, se.stream, se.engine->d_program(), prog.max_depth, se.engine->d_rabbit(), st.box,
+                               st.fit_depth, bounds, nullptr);
+    } else {
+        found = compute_bounds(E, s, E.d_program(), prog.max_depth, E.d_rabbit(), st.box, st.fit_depth, bounds, nullptr);
+    }
+    if (!found) return;
+    if (!fit_box(st.box, bounds, st.resolution, st.fit_margin, fitted)) throw InputError("fit_box: resolution - 2 margin must be >= 1");
+    for (int a = 0; a < 3; ++a)
+        if (!(fitted[2 * a] < fitted[2 * a + 1])) throw InputError("fit_box: the fitted box is empty");
+    std::memcpy(st.box, fitted, sizeof fitted);
+    std::memcpy(g_fit_box, fitted, sizeof fitted);
+    g_fit_box_valid = true;
+}
+
+void grand_algorithm(const char* shape_json, const MCSettings& st_given, const CallSpecs& cs) {   // mcc2.cpp:309-444
     if (g_state.active) {
         report("build_geometry() called in a bad state.", false);
         return;
     }
     ObjectTables tabs;
-    Program prog = compile_mp5(shape_json, st.ignore_root_matrix, &tabs);
+    Program prog = compile_mp5(shape_json, st_given.ignore_root_matrix, &tabs);
     Engine& E = engine();
     hipStream_t s = abi_stream();
     E.set_object(prog, nullptr, &tabs);
+    g_fit_box_valid = false;
+    MCSettings st = st_given;
+    if (st.fit_box) fit_settings_box(E, s, prog, tabs, st);
     // the last build's normals go with its mesh; this build's appear when it ends (normals_done)
     g_state.normals.resize(0);
     g_state.normals_ready = false;
@@ -853,6 +981,84 @@ int implisolid_debug_eval_modes(const char* shape_json, int ignore_root_matrix, 
     return 0;
 }
 
+int implisolid_bounds(const char* shape_json, int ignore_root_matrix, const float search[6], int depth, float out[6],
+                      int64_t stats[4]) {
+    g_last_error.clear();
+    if (!shape_json || !search || !out) {
+        report("implisolid_bounds: bad arguments", false);
+        return -1;
+    }
+    try {
+        // depth and box first: bad input is refused before anything reaches the device
+        if (depth < kBoundsMinDepth || depth > kBoundsMaxDepth) throw InputError("implisolid_bounds: depth must be in [3, 10]");
+        {
+            std::vector<float> probe((size_t)3 * ((1 << depth) + 1));
+            bounds_edges(search, depth, probe.data());
+        }
+        ObjectTables tabs;
+        const Program p = compile_mp5(shape_json, ignore_root_matrix != 0, &tabs);
+        Engine& E = engine();
+        hipStream_t s = abi_stream();
+        TableArena arena;   // the shape's own sdf_3d tables, as the interval probe builds them
+        const float* d_tab = arena.set(tabs, E.d_rabbit());
+        ProbeProgram dp(p);
+        return compute_bounds(E, s, dp.get(), p.max_depth, d_tab, search, depth, out, stats) ? 1 : 0;
+    } catch (const InputError& e) {
+        report(e.what(), true);
+        return -1;
+    } catch (const std::exception& e) {
+        (void)hipDeviceSynchronize();
+        report(e.what(), false);
+        return -1;
+    }
+}
+
+double implisolid_debug_bounds_ms(int enable) {
+    g_bounds_timing = enable != 0;
+    return g_bounds_ms;
+}
+
+int implisolid_bounds_edges(const float search[6], int depth, float* edges) {
+    g_last_error.clear();
+    try {
+        if (!search || !edges) throw InputError("implisolid_bounds_edges: bad arguments");
+        bounds_edges(search, depth, edges);
+    } catch (const std::exception& e) {
+        report(e.what(), false);
+        return -1;
+    }
+    return 0;
+}
+
+int implisolid_fit_box(const float search[6], const float bounds[6], int resolution, int margin, float out[6]) {
+    g_last_error.clear();
+    if (!search || !bounds || !out || !fit_box(search, bounds, resolution, margin, out)) {
+        report("implisolid_fit_box: resolution - 2 margin must be >= 1 (margin >= 0)", false);
+        return -1;
+    }
+    return 0;
+}
+
+int implisolid_parse_fit_box(const char* mc_json, int32_t out[3]) {
+    g_last_error.clear();
+    try {
+        const MCSettings s = parse_mc_settings(mc_json);
+        out[0] = s.fit_box ? 1 : 0;
+        out[1] = s.fit_depth;
+        out[2] = s.fit_margin;
+    } catch (const std::exception& e) {
+        report(e.what(), true);
+        return -1;
+    }
+    return 0;
+}
+
+int implisolid_last_fit_box(float out[6]) {
+    if (!g_fit_box_valid) return 0;
+    if (out) std::memcpy(out, g_fit_box, sizeof g_fit_box);
+    return 1;
+}
+
 void calculate_implicit_values(void) {
     if (!g_eval.has_x || !g_eval.has_object) {
         report("Error: You need to set_x() and set_object() first.", false);
@@ -991,6 +1197,7 @@ implisolid_slab* implisolid_slab_create_range(const char* shape_json, const char
     g_last_error.clear();
     try {
         MCSettings st = parse_mc_settings(mc_json);
+        refuse_fit_box(st, "implisolid_slab_create");
         ObjectTables tabs;
         Program p = compile_mp5(shape_json, st.ignore_root_matrix, &tabs);
         auto* s = new implisolid_slab();
@@ -1055,6 +1262,7 @@ implisolid_slab* implisolid_slab_create(const char* shape_json, const char* mc_j
     g_last_error.clear();
     try {
         MCSettings st = parse_mc_settings(mc_json);
+        refuse_fit_box(st, "implisolid_slab_create");
         ObjectTables tabs;
         Program p = compile_mp5(shape_json, st.ignore_root_matrix, &tabs);
         auto* s = new implisolid_slab();
@@ -1341,6 +1549,7 @@ implisolid_batch* implisolid_batch_create(const char* const* shapes, int n, cons
     try {
         if (n <= 0) throw InputError("implisolid_batch_create: no objects");
         const MCSettings st = parse_mc_settings(mc_json);
+        refuse_fit_box(st, "implisolid_batch_create");
         static const bool timing = std::getenv("IMPLISOLID_BATCH_TIMING") != nullptr;   // diagnostics
         auto t_start = std::chrono::steady_clock::now();
         size_t pool0[4] = {0, 0, 0, 0};

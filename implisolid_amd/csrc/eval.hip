@@ -839,6 +839,140 @@ void launch_iv_probe(const Program* d_prog, int depth, const float* d_rabbit, fl
     else k_iv_probe<16><<<blocks, 256, 0, s>>>(d_prog, d_rabbit, tab_range, d_boxes, d_modes_in, n, d_iv, d_modes_out);
 }
 
+// ---- bounds of the solid (implisolid_bounds) ---------------------------------------------------
+// One launch per level l = 3 .. depth of the search box's edge table (N = 2^depth cells per axis;
+// box i of level l spans edge[i << (depth - l)] .. edge[(i + 1) << (depth - l)]).  One thread per
+// box of the level: the 512 boxes of level 3 (modes word 0), else the eight children of every mixed
+// box the level above listed, bounded from the parent's modes word (as k_iv_probe with modes_in).
+// Outside boxes (hi < 0) are dropped, solid ones (lo >= 0) and the last level's mixed ones widen the
+// running bounds, the other mixed ones are listed for the next launch, which reads the list's length
+// on the device.  The bounds are min / max over contributions: order does not matter.
+//
+// A box wholly inside the running bounds is not bounded at all: whatever its descendants would
+// contribute lies inside it (the levels' boxes nest exactly: one edge table), hence inside bounds
+// that real contributions already set.  Only the work depends on when a wave sees the bounds grow.
+//
+// The list append costs one atomic per wave (ballot + prefix); an entry past the capacity is not
+// written and raises the overflow flag.  The bounds take an atomic only from a box that extends the
+// bounds the thread has just read (the skip test's loads).
+__device__ __forceinline__ uint32_t bounds_peek(const uint32_t* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ void k_bounds_init(BoundsState* __restrict__ st) {
+    const int t = threadIdx.x;
+    if (t < 12) st->count[t] = 0u;
+    if (t < 6) st->key[t] = (t & 1) ? 0u : 0xffffffffu;
+    if (t == 0) {
+        st->overflow = 0u;
+        st->pad = 0u;
+        st->evaluated = 0ull;
+        st->skipped = 0ull;
+    }
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_bounds_level(const Program* __restrict__ prog, const float* __restrict__ tab,
+                                                       float2 tab_range, const float* __restrict__ edges, int depth,
+                                                       int level, const uint32_t* __restrict__ pbox,
+                                                       const uint64_t* __restrict__ pmodes, uint32_t* __restrict__ obox,
+                                                       uint64_t* __restrict__ omodes, uint32_t cap,
+                                                       BoundsState* __restrict__ st) {
+    const int N = 1 << depth, sh = depth - level;
+    const bool top = level == kBoundsMinDepth;
+    // cap <= kBoundsMaxList = 2^27: eight children per listed parent stay below 2^32
+    const uint32_t total = top ? 512u : min(st->count[level - 1], cap) * 8u;
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t n_eval = 0, n_skip = 0;   // wave-uniform
+    // whole waves iterate (the append's ballot covers the wave)
+    for (uint32_t i0 = blockIdx.x * 256u + (threadIdx.x & ~63u); i0 < total; i0 += gridDim.x * 256u) {
+        const uint32_t i = i0 + lane;
+        const bool live = i < total;
+        const uint32_t j = live ? i : 0u;
+        uint32_t ix, iy, iz;
+        uint64_t m_in = 0;
+        if (top) {
+            ix = j & 7u; iy = (j >> 3) & 7u; iz = j >> 6;
+        } else {
+            const uint32_t p = pbox[j >> 3];
+            m_in = pmodes[j >> 3];
+            ix = 2u * (p & 1023u) + (j & 1u);
+            iy = 2u * ((p >> 10) & 1023u) + ((j >> 1) & 1u);
+            iz = 2u * (p >> 20) + ((j >> 2) & 1u);
+        }
+        // ix + 1 <= 2^level: the edge indices stay within [0, N]
+        const float* ey = edges + (N + 1);
+        const float* ez = ey + (N + 1);
+        const float x0 = edges[ix << sh], x1 = edges[(ix + 1u) << sh];
+        const float y0 = ey[iy << sh], y1 = ey[(iy + 1u) << sh];
+        const float z0 = ez[iz << sh], z1 = ez[(iz + 1u) << sh];
+        const uint32_t k[6] = {bounds_key(__float_as_uint(x0)), bounds_key(__float_as_uint(x1)),
+                               bounds_key(__float_as_uint(y0)), bounds_key(__float_as_uint(y1)),
+                               bounds_key(__float_as_uint(z0)), bounds_key(__float_as_uint(z1))};
+        uint32_t cur[6];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) cur[a] = bounds_peek(&st->key[a]);
+        const bool inside = live && k[0] >= cur[0] && k[1] <= cur[1] && k[2] >= cur[2] && k[3] <= cur[3] &&
+                            k[4] >= cur[4] && k[5] <= cur[5];
+        const bool run = live && !inside;
+        uint8_t c = kBrickNeg;
+        uint64_t m = 0;
+        if (run) c = sign_class(eval_iv<D>(prog, tab, tab_range, Box{Iv{x0, x1}, Iv{y0, y1}, Iv{z0, z1}}, m_in, m));
+        const bool mixed = run && c == kBrickMixed;
+        if (run && (c == kBrickPos || (mixed && level == depth))) {
+#pragma unroll
+            for (int a = 0; a < 6; a += 2) {
+                if (k[a] < cur[a]) atomicMin(&st->key[a], k[a]);
+                if (k[a + 1] > cur[a + 1]) atomicMax(&st->key[a + 1], k[a + 1]);
+            }
+        }
+        const bool push = mixed && level < depth;
+        const uint64_t pm = __ballot(push);
+        if (pm) {
+            uint32_t base = 0;
+            if (lane == 0) base = atomicAdd(&st->count[level], (uint32_t)__popcll((unsigned long long)pm));
+            base = (uint32_t)__shfl((int)base, 0, 64);
+            const uint32_t at = base + (uint32_t)__popcll((unsigned long long)(pm & ((1ull << lane) - 1ull)));
+            if (push) {
+                if (at < cap) {
+                    obox[at] = ix | (iy << 10) | (iz << 20);
+                    omodes[at] = m;
+                } else {
+                    st->overflow = 1u;
+                }
+            }
+        }
+        n_eval += (uint32_t)__popcll((unsigned long long)__ballot(run));
+        n_skip += (uint32_t)__popcll((unsigned long long)__ballot(inside));
+    }
+    if (lane == 0) {
+        if (n_eval) atomicAdd(&st->evaluated, (unsigned long long)n_eval);
+        if (n_skip) atomicAdd(&st->skipped, (unsigned long long)n_skip);
+    }
+}
+
+void launch_bounds_levels(const Program* d_prog, int prog_depth, const float* d_rabbit, float2 tab_range,
+                          const float* d_edges, int depth, uint32_t* const d_box[2], uint64_t* const d_modes[2],
+                          uint32_t cap, BoundsState* d_state, hipStream_t s) {
+    if (depth < kBoundsMinDepth || depth > kBoundsMaxDepth) throw std::runtime_error("bounds: depth must be in [3, 10]");
+    if (cap < 1u || cap > kBoundsMaxList) throw std::runtime_error("bounds: list capacity out of range");
+    const int D = eval_depth(prog_depth);
+    k_bounds_init<<<1, 64, 0, s>>>(d_state);
+    for (int l = kBoundsMinDepth; l <= depth; ++l) {
+        // the level holds at most 8^l boxes, and at most eight per listed parent
+        const uint64_t most = l == kBoundsMinDepth ? 512ull : std::min<uint64_t>(1ull << (3 * l), 8ull * cap);
+        const unsigned blocks = (unsigned)std::min<uint64_t>((most + 255) / 256, 1024);
+        const uint32_t* pb = d_box[(l - 1) & 1];
+        const uint64_t* pmo = d_modes[(l - 1) & 1];
+        uint32_t* ob = d_box[l & 1];
+        uint64_t* om = d_modes[l & 1];
+        if (D <= 4) k_bounds_level<4><<<blocks, 256, 0, s>>>(d_prog, d_rabbit, tab_range, d_edges, depth, l, pb, pmo, ob, om, cap, d_state);
+        else if (D <= 8) k_bounds_level<8><<<blocks, 256, 0, s>>>(d_prog, d_rabbit, tab_range, d_edges, depth, l, pb, pmo, ob, om, cap, d_state);
+        else if (D <= 12) k_bounds_level<12><<<blocks, 256, 0, s>>>(d_prog, d_rabbit, tab_range, d_edges, depth, l, pb, pmo, ob, om, cap, d_state);
+        else k_bounds_level<16><<<blocks, 256, 0, s>>>(d_prog, d_rabbit, tab_range, d_edges, depth, l, pb, pmo, ob, om, cap, d_state);
+    }
+}
+
 // ---- the min / max pyramid of an sdf_3d table (ifunc_interval.hpp sdf3d_iv) ---------------------
 // level 0: {min, max} over the eight reads b + {0, 1} + {0, sx} + {0, sx sy} of every flat index
 // b < n (cube_iv's block table); the table is zero-padded past the last read (b + 1 + sx + sx sy)

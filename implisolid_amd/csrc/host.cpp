@@ -120,11 +120,56 @@ MCSettings parse_mc_settings(const char* text) {
         const int v = d.get_int("normals.enabled", -1);
         s.normals = v != -1 && v != 0;
     }
+    {   // additive key, ints like "normals.enabled"
+        const int v = d.get_int("fit_box.enabled", -1);
+        s.fit_box = v != -1 && v != 0;
+        int dflt = kBoundsMinDepth;   // ceil(log2(resolution)), clamped
+        while (dflt < kBoundsMaxDepth && (1 << dflt) < s.resolution) ++dflt;
+        s.fit_depth = d.get_int("fit_box.depth", dflt);
+        s.fit_margin = d.get_int("fit_box.margin", 2);
+        if (s.fit_box) {
+            if (s.fit_depth < kBoundsMinDepth || s.fit_depth > kBoundsMaxDepth) why += "  fit_box.depth must be in [3, 10]";
+            if (s.fit_margin < 0 || (int64_t)s.resolution - 2 * (int64_t)s.fit_margin < 1)
+                why += "  fit_box.margin must leave resolution - 2 margin >= 1";
+        }
+    }
     s.ignore_root_matrix = d.get_bool("ignore_root_matrix", false);
     if (s.qem && !s.projection) why += "  err7 (qem needs projection)";
     if (s.resolution > 65535) why += "  resolution exceeds the reference's dim_t";
     if (!why.empty()) throw InputError("Aborting because of a problem in mc_settings_from_json. Abort reasons: " + why);
     return s;
+}
+
+// ---------------------------------------------------------------------------------------------
+void bounds_edges(const float search[6], int depth, float* edges) {
+    if (depth < kBoundsMinDepth || depth > kBoundsMaxDepth) throw InputError("bounds: depth must be in [3, 10]");
+    const int N = 1 << depth;
+    for (int a = 0; a < 3; ++a) {
+        const float lo = search[2 * a], hi = search[2 * a + 1];
+        const float width = hi - lo;
+        if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo < hi) || !std::isfinite(width))
+            throw InputError("bounds: the search box must be finite with min < max on every axis");
+        const float step = width / (float)N;
+        float* e = edges + (size_t)a * (N + 1);
+        for (int k = 0; k < N; ++k) {
+            const float off = (float)k * step;   // rounded on its own (-ffp-contract=off)
+            e[k] = lo + off;
+        }
+        e[N] = hi;
+    }
+}
+
+bool fit_box(const float search[6], const float bounds[6], int resolution, int margin, float out[6]) {
+    if (margin < 0 || (int64_t)resolution - 2 * (int64_t)margin < 1) return false;
+    const double cells = (double)(resolution - 2 * margin), m = (double)margin;
+    for (int a = 0; a < 3; ++a) {
+        const double b0 = bounds[2 * a], b1 = bounds[2 * a + 1], s0 = search[2 * a], s1 = search[2 * a + 1];
+        const double w = (b1 - b0) / cells;
+        const double lo = std::max(s0, b0 - m * w), hi = std::min(s1, b1 + m * w);
+        out[2 * a] = (float)lo;
+        out[2 * a + 1] = (float)hi;
+    }
+    return true;
 }
 
 // ---------------------------------------------------------------------------------------------

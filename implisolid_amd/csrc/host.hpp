@@ -21,6 +21,11 @@ struct MCSettings {
     bool subdiv = true;
     float post_subdiv_noise = 0.01f;
     bool normals = false;   // additive: "normals.enabled", per-vertex normals with the mesh (no reference key)
+    // additive: "fit_box": {"enabled", "depth", "margin"} -- build_geometry fits its sampling box to
+    // the solid's interval bounds inside `box` (bounds_edges / fit_box below; no reference key)
+    bool fit_box = false;
+    int fit_depth = 3;      // levels of the bounds descent; default ceil(log2(resolution)) in [3, 10]
+    int fit_margin = 2;     // cells of the fitted grid between the bounds and the box wall
 };
 
 // Errors the reference reports with abort() / clog.  The C ABI decides what to do with them
@@ -32,6 +37,18 @@ struct InputError : std::runtime_error {
 // parse_mc_properties_json (polygoniser_settings.hpp:147-305).  Throws InputError where the
 // reference sets needs_abort.
 MCSettings parse_mc_settings(const char* json_text);
+
+// The edge table of the bounds descent (implisolid_bounds): N = 2^depth cells per axis of the search
+// box {xmin, xmax, ymin, ymax, zmin, zmax}; per axis edge[k] = lo + (float)k * ((hi - lo) / (float)N)
+// for k < N, each operation rounded to float on its own, and edge[N] = hi.  edges: 3 (N + 1) floats,
+// x then y then z.  Throws InputError for a depth outside [3, 10] or a box that is not finite with
+// lo < hi on every axis.
+constexpr int kBoundsMinDepth = 3, kBoundsMaxDepth = 10;
+void bounds_edges(const float search[6], int depth, float* edges);
+// The sampling box for `bounds` inside the settings box `search`: per axis, in double,
+// w = (b1 - b0) / (resolution - 2 margin), lo = max(s0, b0 - margin w), hi = min(s1, b1 + margin w),
+// rounded to float.  False if resolution - 2 margin < 1 or margin < 0.
+bool fit_box(const float search[6], const float bounds[6], int resolution, int margin, float out[6]);
 
 // The caller-supplied SDF tables of an object's sdf_3d nodes (sdf_3d.hpp:73-102: read from the node
 // itself).  They travel beside the Program, whose NT_SDF3D parameter rows (program.hpp SdfParam)

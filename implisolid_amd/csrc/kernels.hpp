@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "grid.hpp"
+#include "host.hpp"
 #include "mc_types.hpp"
 #include "program.hpp"
 
@@ -60,6 +61,32 @@ void launch_iv_probe(const Program* d_prog, int depth, const float* d_rabbit, fl
                      hipStream_t s, hipFunction_t jit_fn = nullptr);
 void launch_eval_modes_probe(const Program* d_prog, int depth, const float* d_rabbit, const float* d_xyz,
                              const uint64_t* d_modes, int64_t n, float* d_f, hipStream_t s);
+
+// The bounds descent (implisolid_bounds; DESIGN "Bounds of the solid"): levels 3 .. depth of the
+// search box's 2^depth-cell edge table, one launch per level on s, no host synchronisation between
+// them.  The device state: count[l] = mixed boxes listed at level l (the next launch's items are
+// read from it), the running bounds as order-preserving keys of the edge floats {min x, max x, min
+// y, max y, min z, max z} (no contribution: min keys all ones), an overflow flag (a list was full:
+// the result is void, rerun with longer lists) and the work counters.
+struct BoundsState {
+    uint32_t count[12];
+    uint32_t key[6];
+    uint32_t overflow, pad;
+    unsigned long long evaluated, skipped;
+};
+constexpr uint32_t kBoundsMaxList = 1u << 27;   // boxes of level 9: the longest list any descent needs
+// order-preserving key of a float (no NaN): a < b  <=>  key(a) < key(b)
+__host__ __device__ inline uint32_t bounds_key(uint32_t float_bits) {
+    return (float_bits & 0x80000000u) ? ~float_bits : (float_bits | 0x80000000u);
+}
+__host__ __device__ inline uint32_t bounds_key_bits(uint32_t key) {
+    return (key & 0x80000000u) ? (key ^ 0x80000000u) : ~key;
+}
+// d_edges: 3 (2^depth + 1) floats (host.hpp bounds_edges); d_box / d_modes: the two alternating
+// lists of `cap` entries each (box index x | y << 10 | z << 20 at its level, its modes word)
+void launch_bounds_levels(const Program* d_prog, int prog_depth, const float* d_rabbit, float2 tab_range,
+                          const float* d_edges, int depth, uint32_t* const d_box[2], uint64_t* const d_modes[2],
+                          uint32_t cap, BoundsState* d_state, hipStream_t s);
 
 // the min / max pyramid of one sdf_3d table inside an object's table arena (host.hpp SdfTable: the
 // padded table at tab_off, level L at lvl_off[L]); one launch per level, in order on s

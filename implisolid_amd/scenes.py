@@ -20,8 +20,9 @@ def st(scale, tx, ty, tz):
 
 
 def mc_settings(resolution, box=1.0, *, vresampl_iters=0, vresampl_c=1.0, projection=0, qem=0,
-                overall_repeats=1, subdiv=0, post_subdiv_noise=0):
-    return {
+                overall_repeats=1, subdiv=0, post_subdiv_noise=0, fit_box=None):
+    """fit_box: None (no key), True / 1 (the defaults), or a dict with "depth" and / or "margin"."""
+    d = {
         "box": {"xmin": -box, "xmax": box, "ymin": -box, "ymax": box, "zmin": -box, "zmax": box},
         "resolution": resolution,
         "vresampl": {"iters": vresampl_iters, "c": vresampl_c},
@@ -31,6 +32,10 @@ def mc_settings(resolution, box=1.0, *, vresampl_iters=0, vresampl_c=1.0, projec
         "overall_repeats": overall_repeats,
         "debug": {"post_subdiv_noise": post_subdiv_noise},
     }
+    if fit_box is not None:
+        d["fit_box"] = dict({"enabled": 1}, **{k: int(v) for k, v in fit_box.items()}) if isinstance(fit_box, dict) \
+            else {"enabled": int(bool(fit_box))}
+    return d
 
 
 # configuration 1: single sphere (iellipsoid r = 0.5), box +-0.6, 32^3, MC only

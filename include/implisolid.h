@@ -202,6 +202,56 @@ int implisolid_debug_intervals(const char* shape_json, int ignore_root_matrix, i
 int implisolid_debug_eval_modes(const char* shape_json, int ignore_root_matrix, const float* xyz, const uint64_t* modes,
                                 int64_t n, float* f_out);
 
+/* Additive: the axis-aligned bounds of the solid inside a search box, from the interval evaluator (no
+ * reference counterpart: the front end guesses boxes from node matrices, boundingbox_utils.js:63-196).
+ *   search  {xmin, xmax, ymin, ymax, zmin, zmax}, the order implisolid_parse_settings returns a box
+ *   depth   in [3, 10]: the box is cut into N = 2^depth cells per axis by the edge table of
+ *           implisolid_bounds_edges; level l (3 .. depth) has 2^l boxes per axis, box i spanning
+ *           edge[i << (depth - l)] .. edge[(i + 1) << (depth - l)]
+ * The 512 boxes of level 3 are bounded with modes word 0, a child with its parent's returned modes
+ * word (implisolid_debug_intervals' modes_in).  A box whose bound is hi < 0 is dropped; one with
+ * lo >= 0 contributes its extent and is not cut further; any other (a NaN bound included) is cut
+ * into its eight children, or at level `depth` contributes its extent.  out = the per-axis min / max
+ * over the contributions: deterministic, never inside the solid's true extent, and at most the
+ * interval bounds' slack plus one cell of level `depth` outside it.  An unbounded primitive
+ * (half_plane, inf_screw, a lid) yields `search` on the axes where it is unbounded.
+ *   returns 1 and out = the bounds; 0 when the solid is empty in `search` (out = search); -1 with
+ *           implisolid_last_error() for a depth outside [3, 10], a box that is not finite with
+ *           min < max on every axis, or an unsupported node
+ *   stats   (may be NULL) [boxes bounded, boxes skipped because they lay inside the bounds found so
+ *           far (they cannot extend them; only the work depends on it), longest list of boxes cut at
+ *           one level, reruns after a list overflowed]
+ * One kernel launch per level on the library's stream, one read-back at the end.  The lists start at
+ * IMPLISOLID_BOUNDS_LIST boxes (environment, read at each call; default 8 N^2, at most 2^21) and
+ * grow when a level overflows them, after which the descent runs again. */
+int implisolid_bounds(const char* shape_json, int ignore_root_matrix, const float search[6], int depth, float out[6],
+                      int64_t stats[4]);
+/* host only (no GPU): the edge table, 3 (N + 1) floats, x then y then z.  Per axis
+ * edge[k] = lo + (float)k * ((hi - lo) / (float)N) for k < N, every operation rounded to float on its
+ * own (no fused multiply-add), and edge[N] = hi.  0, or -1 (depth, box) */
+int implisolid_bounds_edges(const float search[6], int depth, float* edges);
+/* host only: the sampling box that puts `bounds` on `resolution - 2 margin` cells with `margin` cells
+ * around them, clipped to the settings box `search`.  Per axis, in double:
+ * w = (b1 - b0) / (resolution - 2 margin), lo = max(s0, b0 - margin w), hi = min(s1, b1 + margin w),
+ * then rounded to float.  0, or -1 if resolution - 2 margin < 1 or margin < 0 */
+int implisolid_fit_box(const float search[6], const float bounds[6], int resolution, int margin, float out[6]);
+/* The mc-settings key "fit_box": {"enabled": 1, "depth": d, "margin": m} (ints, read as
+ * "projection.enabled" is; true / false are no ints and leave it off).  build_geometry and
+ * build_geometry_u then take the settings box as the search box: they find the bounds on the
+ * build's device (ids[0] under implisolid_set_devices), replace the box by implisolid_fit_box's
+ * and run unchanged on it (marching cubes, the OB02 loop, normals, progress callbacks).  The fitted
+ * box never leaves the settings box, which stays the caller's clip region; an empty solid keeps
+ * the box as given.  depth defaults to ceil(log2(resolution)) clamped to [3, 10], margin to 2.
+ * Without the key nothing changes.  implisolid_slab_create* and implisolid_batch_create refuse an
+ * enabled key (their grids are the caller's, or shared by all objects).
+ *   parse_fit_box  host only: out = {enabled, depth, margin} as a build would read them; 0 or -1
+ *   last_fit_box   1 and out = the box the last build used if it was fitted, else 0 */
+int implisolid_parse_fit_box(const char* mc_json, int32_t out[3]);
+int implisolid_last_fit_box(float out[6]);
+/* diagnostics: with enable != 0 the following implisolid_bounds calls (and fitted builds) time their
+ * level launches with HIP events; returns the last such figure in milliseconds (-1: none yet) */
+double implisolid_debug_bounds_ms(int enable);
+
 /* host-only: compile an MP5 tree to the node program; info = {n_instr, depth, n_mats, 0};
    mats_out receives n_mats inverse matrices (12 floats each, up to 256) */
 /* Additive, host only (no GPU): generate and hipRTC-compile the tree kernel for this shape.
