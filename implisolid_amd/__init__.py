@@ -52,6 +52,7 @@ ABI_SYMBOLS = [
     "implisolid_batch_has_normals", "implisolid_batch_download_normals",
     "implisolid_bounds", "implisolid_bounds_edges", "implisolid_fit_box", "implisolid_parse_fit_box",
     "implisolid_last_fit_box", "implisolid_debug_bounds_ms",
+    "implisolid_slice", "implisolid_slice_copy", "implisolid_slice_coords", "implisolid_slice_loops",
 ]
 
 # implisolid_progress_callback (include/implisolid.h): verts, n_verts, faces, n_faces,
@@ -193,6 +194,12 @@ def lib():
         "implisolid_parse_fit_box": ([c_char_p, ip], c_int),
         "implisolid_last_fit_box": ([fp], c_int),
         "implisolid_debug_bounds_ms": ([c_int], ctypes.c_double),
+        "implisolid_slice": ([c_char_p, c_int, fp, c_int, fp, c_int, ctypes.POINTER(ctypes.c_int64),
+                              ctypes.POINTER(ctypes.c_int64)], ctypes.c_int64),
+        "implisolid_slice_copy": ([fp, up], c_int),
+        "implisolid_slice_coords": ([fp, c_int, fp, fp], c_int),
+        "implisolid_slice_loops": ([up, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                                    ctypes.POINTER(ctypes.c_uint8)], ctypes.c_int64),
     }
     for name, (args, res) in sig.items():
         try:
@@ -697,6 +704,86 @@ def fit_box(search_box, bounds_box, resolution, margin=2):
     if lib().implisolid_fit_box(sb.ctypes.data_as(fp), bb.ctypes.data_as(fp), int(resolution), int(margin),
                                 out.ctypes.data_as(fp)) != 0:
         raise ImplisolidError(last_error())
+    return out
+
+
+def _rect4(rect, what):
+    r = np.ascontiguousarray(rect, np.float32).reshape(-1)
+    if r.size != 4:
+        raise ValueError("%s: a rect is four floats {xmin, xmax, ymin, ymax}" % what)
+    return r
+
+
+def slice_layers(shape, rect, resolution, z, ignore_root_matrix=False, return_stats=False):
+    """The solid's outlines on the planes z = z[l], by marching squares on the GPU over `resolution`
+    cells per axis of rect {xmin, xmax, ymin, ymax} (include/implisolid.h implisolid_slice).  Returns
+    (segments float32 (S, 2, 2) = {start, end} x {x, y}, directed with the solid on their left,
+    keys uint32 (S, 2) = {start, end} edge keys, layer_offsets int64 (L + 1,)), and with return_stats
+    also [(layer, tile) pairs, tiles evaluated, samples evaluated, chunks]."""
+    fp, up = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint32)
+    r = _rect4(rect, "slice_layers")
+    zz = np.ascontiguousarray(z, np.float32).reshape(-1)
+    offs = np.zeros(zz.size + 1, np.int64)
+    stats = (ctypes.c_int64 * 4)()
+    n = lib().implisolid_slice(_s(shape), int(bool(ignore_root_matrix)), r.ctypes.data_as(fp), int(resolution),
+                               zz.ctypes.data_as(fp), int(zz.size), offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), stats)
+    if n < 0:
+        raise ImplisolidError(last_error())
+    seg = np.empty((n, 2, 2), np.float32)
+    keys = np.empty((n, 2), np.uint32)
+    if lib().implisolid_slice_copy(seg.ctypes.data_as(fp), keys.ctypes.data_as(up)) != 0:
+        raise ImplisolidError(last_error())
+    if return_stats:
+        return seg, keys, offs, [int(v) for v in stats]
+    return seg, keys, offs
+
+
+def slice_coords(rect, resolution):
+    """Host only: the sample coordinates of slice_layers, (xs, ys) float32 (resolution + 1,) each."""
+    fp = ctypes.POINTER(ctypes.c_float)
+    r = _rect4(rect, "slice_coords")
+    if not 1 <= int(resolution) <= 4096:
+        raise ImplisolidError("slice_coords: resolution must be in [1, 4096]")
+    xs, ys = np.empty(int(resolution) + 1, np.float32), np.empty(int(resolution) + 1, np.float32)
+    if lib().implisolid_slice_coords(r.ctypes.data_as(fp), int(resolution), xs.ctypes.data_as(fp), ys.ctypes.data_as(fp)) != 0:
+        raise ImplisolidError(last_error())
+    return xs, ys
+
+
+def slice_loops(keys):
+    """Host only: one layer's keys uint32 (n, 2) chained into polylines (implisolid_slice_loops).
+    Returns (order int64 (n,), loop_offsets int64 (polylines + 1,), closed bool (polylines,)): polyline p
+    is the segments order[loop_offsets[p]:loop_offsets[p + 1]]; open chains first, then closed loops.
+    Raises if a key starts two segments or ends two."""
+    k = np.ascontiguousarray(keys, np.uint32).reshape(-1, 2)
+    n = k.shape[0]
+    ip64 = ctypes.POINTER(ctypes.c_int64)
+    order = np.zeros(n, np.int64)
+    offs = np.zeros(n + 1, np.int64)
+    closed = np.zeros(max(n, 1), np.uint8)
+    loops = lib().implisolid_slice_loops(k.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), n, order.ctypes.data_as(ip64),
+                                         offs.ctypes.data_as(ip64), closed.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
+    if loops < 0:
+        raise ImplisolidError(last_error())
+    return order, offs[:loops + 1].copy(), closed[:loops].astype(bool)
+
+
+def slice_polylines(shape, rect, resolution, z, ignore_root_matrix=False):
+    """slice_layers chained: per layer a list of (points float32 (n, 2), closed).  A closed loop lists
+    each vertex once (the last point joins the first); an open chain ends with its last segment's end."""
+    seg, keys, offs = slice_layers(shape, rect, resolution, z, ignore_root_matrix)
+    out = []
+    for l in range(len(offs) - 1):
+        s, k = seg[offs[l]:offs[l + 1]], keys[offs[l]:offs[l + 1]]
+        order, lo, closed = slice_loops(k)
+        lines = []
+        for p in range(len(closed)):
+            idx = order[lo[p]:lo[p + 1]]
+            pts = s[idx, 0]
+            if not closed[p]:
+                pts = np.concatenate([pts, s[idx[-1:], 1]])
+            lines.append((np.ascontiguousarray(pts), bool(closed[p])))
+        out.append(lines)
     return out
 
 

@@ -1039,6 +1039,203 @@ int implisolid_fit_box(const float search[6], const float bounds[6], int resolut
     return 0;
 }
 
+// ---- slices of the solid (implisolid_slice) ------------------------------------------------------
+// Layers go through slice.hip's passes in chunks of whole layers, at most kSliceMaxChunk (layer, tile)
+// items each: classify, a read-back of the list's length (it sizes the sample scratch and the march
+// and emit grids), march, scan, a read-back of the chunk's per-layer offsets and total (they size
+// the output), emit, and the copy into the host slot at the running offset.  E lends its scratch.
+namespace {
+struct SliceSlot {               // the last slice's result; n < 0: none
+    PinnedVec<float> xy;
+    PinnedVec<uint32_t> keys;
+    int64_t n = -1;
+};
+SliceSlot g_slice;
+
+uint32_t slice_chunk_layers(uint32_t tpl, int n_layers) {
+    uint64_t items = kSliceMaxChunk;
+    if (const char* e = std::getenv("IMPLISOLID_SLICE_CHUNK")) {   // read at each call (tests force several chunks)
+        const long long v = std::atoll(e);
+        if (v > 0) items = std::min<uint64_t>((uint64_t)v, kSliceMaxChunk);
+    }
+    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(items / tpl, 1), (uint64_t)n_layers);
+}
+
+int64_t slice_layers(Engine& E, hipStream_t s, const Program* d_prog, int prog_depth, const float* d_tab, int R,
+                     const std::vector<float>& xs, const std::vector<float>& ys, const float* z, int n_layers,
+                     int64_t* layer_offsets, int64_t stats[4]) {
+    SliceGrid g;
+    g.R = R;
+    g.ntx = (R + kSliceTile - 1) / kSliceTile;
+    g.tpl = (uint32_t)g.ntx * (uint32_t)g.ntx;
+    const uint32_t chunk_layers = slice_chunk_layers(g.tpl, n_layers);
+    const uint32_t cap = chunk_layers * g.tpl;   // items per chunk, <= kSliceMaxChunk (tpl <= 2^16)
+    const bool prune = Engine::pruning() >= 1;
+    constexpr size_t kStateBytes = 256;
+    static_assert(sizeof(SliceState) <= kStateBytes, "the coordinates follow the state block");
+    const size_t W = (size_t)R + 1;
+    // every reserve before any pointer is taken: a DevBuf that grows moves
+    E.scratch(10).reserve(kStateBytes + (2 * W + (size_t)n_layers) * sizeof(float));
+    E.scratch(11).reserve((size_t)cap * sizeof(uint32_t));                        // list
+    E.scratch(12).reserve((size_t)cap * sizeof(uint32_t));                        // counts
+    E.scratch(13).reserve((size_t)cap * sizeof(uint64_t));                        // the listed tiles' modes
+    E.scratch(14).reserve(((size_t)cap + 1 + cap / 4096 + 2) * sizeof(uint32_t)); // offsets, then the scan's sums
+    E.scratch(9).reserve(((size_t)chunk_layers + 1) * sizeof(uint32_t));          // per-layer offsets
+    SliceState* d_state = E.scratch(10).as<SliceState>();
+    float* d_xs = reinterpret_cast<float*>(E.scratch(10).as<char>() + kStateBytes);
+    float* d_ys = d_xs + W;
+    float* d_z = d_ys + W;
+    uint32_t* d_list = E.scratch(11).as<uint32_t>();
+    uint32_t* d_counts = E.scratch(12).as<uint32_t>();
+    uint64_t* d_lmodes = E.scratch(13).as<uint64_t>();
+    uint32_t* d_offsets = E.scratch(14).as<uint32_t>();
+    uint32_t* d_sums = d_offsets + cap + 1;
+    uint32_t* d_loff = E.scratch(9).as<uint32_t>();
+    IMPLI_HIP(hipMemcpyAsync(d_xs, xs.data(), W * sizeof(float), hipMemcpyHostToDevice, s));
+    IMPLI_HIP(hipMemcpyAsync(d_ys, ys.data(), W * sizeof(float), hipMemcpyHostToDevice, s));
+    IMPLI_HIP(hipMemcpyAsync(d_z, z, (size_t)n_layers * sizeof(float), hipMemcpyHostToDevice, s));
+    g_slice.xy.resize(0);
+    g_slice.keys.resize(0);
+    int64_t total = 0, listed = 0, samples = 0, chunks = 0;
+    std::vector<uint32_t> loff((size_t)chunk_layers + 1);
+    for (int l0 = 0; l0 < n_layers; l0 += (int)chunk_layers, ++chunks) {
+        const uint32_t nl = (uint32_t)std::min<int64_t>(chunk_layers, n_layers - l0);
+        const uint32_t n = nl * g.tpl;
+        const int64_t first = (int64_t)l0 * g.tpl;
+        IMPLI_HIP(hipMemsetAsync(d_state, 0, sizeof(SliceState), s));
+        IMPLI_HIP(hipMemsetAsync(d_counts, 0, (size_t)n * sizeof(uint32_t), s));
+        launch_slice_classify(d_prog, prog_depth, d_tab, E.tab_range(), d_xs, d_ys, d_z, g, first, n, prune, d_list, d_lmodes,
+                              d_state, s);
+        IMPLI_HIP(hipGetLastError());
+        SliceState h{};
+        IMPLI_HIP(hipMemcpyAsync(&h, d_state, sizeof h, hipMemcpyDeviceToHost, s));
+        IMPLI_HIP(hipStreamSynchronize(s));
+        if (h.n_listed > n) throw HipError("slice: the tile list overran its chunk");
+        listed += h.n_listed;
+        samples += (int64_t)h.samples;
+        uint32_t chunk_total = 0;
+        if (h.n_listed) {
+            E.scratch(15).reserve((size_t)h.n_listed * kSliceSamples * sizeof(float));
+            float* d_samples = E.scratch(15).as<float>();
+            launch_slice_march(d_prog, prog_depth, d_tab, d_xs, d_ys, d_z, g, first, h.n_listed, d_list, d_lmodes, d_samples,
+                               d_counts, s);
+            launch_scan_u32(d_counts, d_offsets, n, d_sums, false, s);
+            launch_slice_layer_offsets(d_offsets, g.tpl, nl, d_loff, s);
+            IMPLI_HIP(hipGetLastError());
+            IMPLI_HIP(hipMemcpyAsync(loff.data(), d_loff, ((size_t)nl + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            IMPLI_HIP(hipStreamSynchronize(s));
+            chunk_total = loff[nl];
+            if (total + (int64_t)chunk_total >= ((int64_t)1 << 31)) throw InputError("implisolid_slice: the slice reaches 2^31 segments");
+            if (chunk_total) {
+                E.scratch(0).reserve((size_t)chunk_total * 4 * sizeof(float));
+                E.scratch(1).reserve((size_t)chunk_total * 2 * sizeof(uint32_t));
+                launch_slice_emit(d_xs, d_ys, g, first, h.n_listed, d_list, d_samples, d_offsets, chunk_total,
+                                  E.scratch(0).as<float>(), E.scratch(1).as<uint32_t>(), s);
+                IMPLI_HIP(hipGetLastError());
+                g_slice.xy.resize((size_t)(total + chunk_total) * 4);
+                g_slice.keys.resize((size_t)(total + chunk_total) * 2);
+                IMPLI_HIP(hipMemcpyAsync(g_slice.xy.data() + 4 * total, E.scratch(0).p, (size_t)chunk_total * 4 * sizeof(float),
+                                         hipMemcpyDeviceToHost, s));
+                IMPLI_HIP(hipMemcpyAsync(g_slice.keys.data() + 2 * total, E.scratch(1).p,
+                                         (size_t)chunk_total * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+                IMPLI_HIP(hipStreamSynchronize(s));
+            }
+        } else {
+            std::fill(loff.begin(), loff.end(), 0u);
+        }
+        for (uint32_t k = 0; k < nl; ++k) layer_offsets[l0 + (int)k] = total + loff[k];
+        total += chunk_total;
+    }
+    layer_offsets[n_layers] = total;
+    if (stats) {
+        stats[0] = (int64_t)n_layers * g.tpl;
+        stats[1] = listed;
+        stats[2] = samples;
+        stats[3] = chunks;
+    }
+    return total;
+}
+}  // namespace
+
+int64_t implisolid_slice(const char* shape_json, int ignore_root_matrix, const float rect[4], int resolution, const float* z,
+                         int n_layers, int64_t* layer_offsets, int64_t stats[4]) {
+    g_last_error.clear();
+    g_slice.n = -1;   // whatever happens, the previous result is gone
+    if (!shape_json || !rect || !z || !layer_offsets) {
+        report("implisolid_slice: bad arguments", false);
+        return -1;
+    }
+    try {
+        // the request first: bad input is refused before anything reaches the device
+        if (n_layers < 1 || n_layers > kSliceMaxLayers) throw InputError("implisolid_slice: n_layers must be in [1, 65536]");
+        for (int l = 0; l < n_layers; ++l)
+            if (!std::isfinite(z[l])) throw InputError("implisolid_slice: every z must be finite");
+        if (resolution < 1 || resolution > kSliceMaxResolution) throw InputError("slice: resolution must be in [1, 4096]");
+        std::vector<float> xs((size_t)resolution + 1), ys((size_t)resolution + 1);
+        slice_coords(rect, resolution, xs.data(), ys.data());
+        ObjectTables tabs;
+        const Program p = compile_mp5(shape_json, ignore_root_matrix != 0, &tabs);
+        Engine& E = engine();
+        hipStream_t s = abi_stream();
+        TableArena arena;   // the shape's own sdf_3d tables, as implisolid_bounds builds them
+        const float* d_tab = arena.set(tabs, E.d_rabbit());
+        ProbeProgram dp(p);
+        g_slice.n = slice_layers(E, s, dp.get(), p.max_depth, d_tab, resolution, xs, ys, z, n_layers, layer_offsets, stats);
+        return g_slice.n;
+    } catch (const InputError& e) {
+        report(e.what(), true);
+        return -1;
+    } catch (const std::exception& e) {
+        (void)hipDeviceSynchronize();
+        report(e.what(), false);
+        return -1;
+    }
+}
+
+int implisolid_slice_copy(float* xy, uint32_t* keys) {
+    g_last_error.clear();
+    if (g_slice.n < 0 || (g_slice.n > 0 && (!xy || !keys))) {
+        report(g_slice.n < 0 ? "implisolid_slice_copy: no slice to copy (the last implisolid_slice failed, or none ran)"
+                             : "implisolid_slice_copy: bad arguments", false);
+        return -1;
+    }
+    if (g_slice.n > 0) {
+        std::memcpy(xy, g_slice.xy.data(), (size_t)g_slice.n * 4 * sizeof(float));
+        std::memcpy(keys, g_slice.keys.data(), (size_t)g_slice.n * 2 * sizeof(uint32_t));
+    }
+    return 0;
+}
+
+int implisolid_slice_coords(const float rect[4], int resolution, float* xs, float* ys) {
+    g_last_error.clear();
+    try {
+        if (!rect || !xs || !ys) throw InputError("implisolid_slice_coords: bad arguments");
+        slice_coords(rect, resolution, xs, ys);
+    } catch (const std::exception& e) {
+        report(e.what(), false);
+        return -1;
+    }
+    return 0;
+}
+
+int64_t implisolid_slice_loops(const uint32_t* keys, int64_t n_segments, int64_t* order, int64_t* loop_offsets,
+                               uint8_t* closed) {
+    g_last_error.clear();
+    if (n_segments < 0 || !loop_offsets || (n_segments > 0 && (!keys || !order || !closed))) {
+        report("implisolid_slice_loops: bad arguments", false);
+        return -1;
+    }
+    int64_t loops = -1;
+    try {
+        loops = slice_loops(keys, n_segments, order, loop_offsets, closed);
+    } catch (const std::exception& e) {
+        report(e.what(), false);
+        return -1;
+    }
+    if (loops < 0) report("implisolid_slice_loops: a key starts two segments or ends two", false);
+    return loops;
+}
+
 int implisolid_parse_fit_box(const char* mc_json, int32_t out[3]) {
     g_last_error.clear();
     try {

@@ -579,7 +579,7 @@ __global__ __launch_bounds__(256) void k_eval_points(const Program* __restrict__
 // accesses to v_cndmask select chains (8 compares + 8 selects per access); from 12 slots on it
 // uses VGPR index mode (s_set_gpr_idx_on + one v_mov), measured 1.7x faster on the config-4 tree.
 // IMPLISOLID_EVAL_DEPTH overrides the floor (experiments).
-static int eval_depth(int depth) {
+int eval_depth(int depth) {
     static int floor_d = [] {
         const char* s = std::getenv("IMPLISOLID_EVAL_DEPTH");
         return s ? std::atoi(s) : 12;

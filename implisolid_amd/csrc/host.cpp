@@ -173,6 +173,63 @@ bool fit_box(const float search[6], const float bounds[6], int resolution, int m
 }
 
 // ---------------------------------------------------------------------------------------------
+void slice_coords(const float rect[4], int resolution, float* xs, float* ys) {
+    if (resolution < 1 || resolution > kSliceMaxResolution) throw InputError("slice: resolution must be in [1, 4096]");
+    for (int a = 0; a < 2; ++a) {
+        const float lo = rect[2 * a], hi = rect[2 * a + 1];
+        const float width = hi - lo;
+        if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo < hi) || !std::isfinite(width))
+            throw InputError("slice: the rect must be finite with min < max on both axes");
+        const float step = width / (float)resolution;
+        float* e = a ? ys : xs;
+        for (int k = 0; k < resolution; ++k) {
+            const float off = (float)k * step;   // rounded on its own (-ffp-contract=off)
+            e[k] = lo + off;
+        }
+        e[resolution] = hi;
+    }
+}
+
+int64_t slice_loops(const uint32_t* keys, int64_t n, int64_t* order, int64_t* loop_offsets, uint8_t* closed) {
+    loop_offsets[0] = 0;
+    if (n <= 0) return 0;
+    // segments sorted by start key and by end key: a repeated key among either is refused
+    std::vector<std::pair<uint32_t, int64_t>> by_start((size_t)n), by_end((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        by_start[(size_t)i] = {keys[2 * i], i};
+        by_end[(size_t)i] = {keys[2 * i + 1], i};
+    }
+    std::sort(by_start.begin(), by_start.end());
+    std::sort(by_end.begin(), by_end.end());
+    for (int64_t i = 1; i < n; ++i)
+        if (by_start[(size_t)i].first == by_start[(size_t)i - 1].first || by_end[(size_t)i].first == by_end[(size_t)i - 1].first)
+            return -1;
+    // next[i]: the segment that starts where i ends; has_prev[i]: some segment ends where i starts
+    std::vector<int64_t> next((size_t)n, -1);
+    std::vector<uint8_t> has_prev((size_t)n, 0), used((size_t)n, 0);
+    for (int64_t i = 0; i < n; ++i) {
+        const auto it = std::lower_bound(by_start.begin(), by_start.end(), std::make_pair(keys[2 * i + 1], (int64_t)-1));
+        if (it != by_start.end() && it->first == keys[2 * i + 1]) {
+            next[(size_t)i] = it->second;
+            has_prev[(size_t)it->second] = 1;
+        }
+    }
+    int64_t at = 0, loops = 0;
+    for (int pass = 0; pass < 2; ++pass) {   // open chains (from a start no segment ends on), then loops
+        for (int64_t i = 0; i < n; ++i) {
+            if (used[(size_t)i] || (pass == 0 && has_prev[(size_t)i])) continue;
+            for (int64_t k = i; k >= 0 && !used[(size_t)k]; k = next[(size_t)k]) {
+                used[(size_t)k] = 1;
+                order[at++] = k;
+            }
+            closed[loops] = pass ? 1 : 0;
+            loop_offsets[++loops] = at;
+        }
+    }
+    return loops;
+}
+
+// ---------------------------------------------------------------------------------------------
 namespace {
 
 struct Builder {

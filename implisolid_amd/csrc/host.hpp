@@ -50,6 +50,20 @@ void bounds_edges(const float search[6], int depth, float* edges);
 // rounded to float.  False if resolution - 2 margin < 1 or margin < 0.
 bool fit_box(const float search[6], const float bounds[6], int resolution, int margin, float out[6]);
 
+// The sample coordinates of a slice (implisolid_slice): R cells per axis of rect {xmin, xmax, ymin,
+// ymax}; xs[i] = xmin + (float)i * ((xmax - xmin) / (float)R) for i < R, each operation rounded to float
+// on its own, xs[R] = xmax, and ys the same way.  xs, ys: R + 1 floats each.  Throws InputError for a
+// resolution outside [1, 4096] or a rect that is not finite with min < max on both axes.
+constexpr int kSliceMaxResolution = 4096, kSliceMaxLayers = 65536;
+constexpr int kSliceTile = 16;   // cells per tile side: part of the ABI (it fixes the segments' order)
+void slice_coords(const float rect[4], int resolution, float* xs, float* ys);
+// Chains one layer's segments {start key, end key} into polylines by exact key matching
+// (implisolid_slice_loops): order = a permutation of the segment indices, every polyline's segments
+// consecutive; open chains first (by first segment), then closed loops, each from its lowest-indexed
+// segment (by that index).  loop_offsets: polylines + 1 entries; closed: one flag per polyline.
+// Returns the number of polylines, or -1 if a key starts two segments or ends two.
+int64_t slice_loops(const uint32_t* keys, int64_t n_segments, int64_t* order, int64_t* loop_offsets, uint8_t* closed);
+
 // The caller-supplied SDF tables of an object's sdf_3d nodes (sdf_3d.hpp:73-102: read from the node
 // itself).  They travel beside the Program, whose NT_SDF3D parameter rows (program.hpp SdfParam)
 // hold each table's place in the object's device table arena:

@@ -88,6 +88,46 @@ void launch_bounds_levels(const Program* d_prog, int prog_depth, const float* d_
                           const float* d_edges, int depth, uint32_t* const d_box[2], uint64_t* const d_modes[2],
                           uint32_t cap, BoundsState* d_state, hipStream_t s);
 
+// the interpreter's stack class for a program of this depth (eval.hip: 12 slots at least, see there)
+int eval_depth(int depth);
+// exclusive scan of n uint32 into out[0 .. n], out[n] = the total (ob02.hip's scan kernels); sums:
+// scratch of n / 4096 + 2 words; zero_in leaves in[] zeroed
+void launch_scan_u32(uint32_t* in, uint32_t* out, int64_t n, uint32_t* sums, bool zero_in, hipStream_t s);
+
+// Slicing (implisolid_slice; DESIGN "Slices of the solid"): the marching-squares contours of the
+// planes z[l] on an R-cell grid of xs x ys (host.hpp slice_coords), in tiles of kSliceTile cells.
+// One chunk = `n` consecutive (layer, tile) items from global item `first` (item = layer * tiles per
+// layer + ty * ntx + tx); all launches on s, no host synchronisation inside a function.
+struct SliceGrid {
+    int R, ntx;          // cells and tiles per axis
+    uint32_t tpl;        // tiles per layer = ntx^2
+};
+struct SliceState {      // zeroed before classify
+    uint32_t n_listed, pad;
+    unsigned long long samples;   // samples the listed tiles hold
+};
+constexpr int kSliceSide = kSliceTile + 1, kSliceSamples = kSliceSide * kSliceSide;
+constexpr uint32_t kSliceMaxChunk = 1u << 20;   // items per chunk: 512 segments each stay below 2^32
+// classify: one thread per item; prune: bound the tile's box with the interval interpreter and list
+// only mixed tiles (with their modes words), else list every tile with modes word 0.  list / lmodes:
+// n entries (chunk-local item indices, in any order)
+void launch_slice_classify(const Program* d_prog, int prog_depth, const float* d_tab, float2 tab_range, const float* d_xs,
+                           const float* d_ys, const float* d_z, SliceGrid g, int64_t first, uint32_t n, bool prune,
+                           uint32_t* d_list, uint64_t* d_lmodes, SliceState* d_state, hipStream_t s);
+// march: one block per listed tile; its samples into d_samples[slot][kSliceSamples], its segment
+// count into d_counts[item] (zeroed by the caller: unlisted tiles hold 0)
+void launch_slice_march(const Program* d_prog, int prog_depth, const float* d_tab, const float* d_xs, const float* d_ys,
+                        const float* d_z, SliceGrid g, int64_t first, uint32_t n_listed, const uint32_t* d_list,
+                        const uint64_t* d_lmodes, float* d_samples, uint32_t* d_counts, hipStream_t s);
+// emit: one block per listed tile; segments {x0, y0, x1, y1} and keys {start, end} at
+// d_offsets[item] (the exclusive scan of d_counts) + the cell's prefix inside the tile; total: the
+// chunk's segment count (nothing is written at or past it)
+void launch_slice_emit(const float* d_xs, const float* d_ys, SliceGrid g, int64_t first, uint32_t n_listed,
+                       const uint32_t* d_list, const float* d_samples, const uint32_t* d_offsets, uint32_t total,
+                       float* d_xy, uint32_t* d_keys, hipStream_t s);
+// out[k] = d_offsets[k * tpl] for k <= n_layers: the chunk's per-layer offsets and its total
+void launch_slice_layer_offsets(const uint32_t* d_offsets, uint32_t tpl, uint32_t n_layers, uint32_t* d_out, hipStream_t s);
+
 // the min / max pyramid of one sdf_3d table inside an object's table arena (host.hpp SdfTable: the
 // padded table at tab_off, level L at lvl_off[L]); one launch per level, in order on s
 void launch_sdf3d_pyramid(float* d_arena, uint32_t tab_off, int sx, int sy, int sz, uint32_t level0, int n_levels,

@@ -2295,12 +2295,16 @@ void Ob02::build_topology(bool deg_zeroed) {
 
 void Ob02::scan(uint32_t* in, uint32_t* out, int64_t n, bool zero_in) {
     const int64_t tiles = (n + kScanTile - 1) / kScanTile;
+    if (tiles > 1) scan_tmp_.reserve((size_t)(tiles + 1) * 4);
+    launch_scan_u32(in, out, n, scan_tmp_.as<uint32_t>(), zero_in, s);
+}
+
+void launch_scan_u32(uint32_t* in, uint32_t* out, int64_t n, uint32_t* sums, bool zero_in, hipStream_t s) {
+    const int64_t tiles = (n + kScanTile - 1) / kScanTile;
     if (tiles <= 1) {
         k_scan_u32<<<1, 1024, 0, s>>>(in, out, n, zero_in ? 1 : 0);
         return;
     }
-    scan_tmp_.reserve((size_t)(tiles + 1) * 4);
-    uint32_t* sums = scan_tmp_.as<uint32_t>();
     k_scan_tile_sums<<<(unsigned)tiles, 256, 0, s>>>(in, n, sums);
     k_scan_tiles<<<(unsigned)tiles, 256, 0, s>>>(in, n, sums, out, zero_in ? 1 : 0);
 }

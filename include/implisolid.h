@@ -252,6 +252,62 @@ int implisolid_last_fit_box(float out[6]);
  * level launches with HIP events; returns the last such figure in milliseconds (-1: none yet) */
 double implisolid_debug_bounds_ms(int enable);
 
+/* Additive: the solid's closed outlines on the planes z = z[l], by marching squares on the GPU (no
+ * reference counterpart; a slicer's input).
+ *   rect        {xmin, xmax, ymin, ymax}, finite with min < max
+ *   resolution  R in [1, 4096] cells per axis; the samples are xs[0 .. R] x ys[0 .. R] of
+ *               implisolid_slice_coords
+ *   z           n_layers in [1, 65536] finite plane heights, in the caller's order (they may repeat and
+ *               need not be sorted)
+ * F[l][j][i] is implisolid_eval_points' value at (xs[i], ys[j], z[l]); a sample is solid iff !(F < 0)
+ * (marching cubes' rule; a NaN counts as solid).  Cell (i, j), i, j < R, has the corners c0 = (i, j),
+ * c1 = (i + 1, j), c2 = (i + 1, j + 1), c3 = (i, j + 1); case bit k is set iff ck is solid.  With
+ * W = R + 1 its edges and their keys are
+ *   e0 bottom c0-c1  2 (j W + i)          e1 right c1-c2  2 (j W + i + 1) + 1
+ *   e2 top    c3-c2  2 ((j + 1) W + i)    e3 left  c0-c3  2 (j W + i) + 1
+ * (even: an x-edge, odd: a y-edge, each named after its lower sample).  Segments are directed with the
+ * solid on their left (x right, y up):
+ *   case 1 e0>e3   2 e1>e0   4 e2>e1   8 e3>e2   3 e1>e3   6 e2>e0   5 e0>e3 then e2>e1
+ *       14 e3>e0  13 e0>e1  11 e1>e2   7 e2>e3  12 e3>e1   9 e0>e2  10 e1>e0 then e3>e2
+ * (0 and 15: none; the saddles 5 and 10 always cut their two solid corners off separately).  An
+ * endpoint lies on its edge, interpolated from the edge's lower sample a to its higher sample b:
+ * mu = (0.f - a) / (b - a); on an x-edge at (i, j) x = xs[i] + mu * (xs[i + 1] - xs[i]), y = ys[j]; on a
+ * y-edge x = xs[i], y = ys[j] + mu * (ys[j + 1] - ys[j]); every operation rounded to float on its own.
+ * Both cells that share an edge compute the same bits, so a contour's segments chain by key.
+ * Order: by layer, then by tile of 16 x 16 cells row-major (ty, tx), then by cell row-major inside
+ * the tile (j, i), then the table's order.  The tile size is part of the interface.
+ *   returns        S, the number of segments, or -1 with implisolid_last_error(): a bad rect,
+ *                  resolution, n_layers or z, an unsupported node, or a total that reaches 2^31
+ *   layer_offsets  n_layers + 1 entries: layer l's segments are [layer_offsets[l], layer_offsets[l + 1])
+ *   stats          (may be NULL) [(layer, tile) pairs, tiles evaluated, samples evaluated, chunks]
+ * The result stays in one library-owned slot, in host memory, until the next implisolid_slice call:
+ *   slice_copy     copies it: xy = 4 S floats {x_start, y_start, x_end, y_end}, keys = 2 S words
+ *                  {start key, end key}; 0, or -1 when there is no result
+ * At implisolid_set_pruning level >= 1 each (layer, tile) is first bounded by the interval evaluator
+ * over the box of its end samples and {z, z}: a tile that is all solid or all empty is skipped, the
+ * others evaluate their samples with the bound's modes word (bit-identical values); at level 0 every
+ * tile is evaluated.  Only the work differs.  Layers are processed in chunks of at most
+ * IMPLISOLID_SLICE_CHUNK tiles (environment, read at each call; default and maximum 2^20, at least one
+ * layer's tiles), which bounds the device scratch. */
+int64_t implisolid_slice(const char* shape_json, int ignore_root_matrix, const float rect[4], int resolution,
+                         const float* z, int n_layers, int64_t* layer_offsets, int64_t stats[4]);
+int implisolid_slice_copy(float* xy, uint32_t* keys);
+/* host only (no GPU): the sample coordinates, R + 1 floats each.  xs[i] = xmin + (float)i * ((xmax -
+ * xmin) / (float)R) for i < R, every operation rounded to float on its own, xs[R] = xmax; ys likewise.
+ * 0, or -1 (resolution, rect) */
+int implisolid_slice_coords(const float rect[4], int resolution, float* xs, float* ys);
+/* host only: chains ONE layer's keys (pass the layer's sub-array, 2 n_segments words) into polylines
+ * by exact key matching.  order (n_segments entries) is a permutation of the segment indices in which
+ * each polyline's segments are consecutive and every segment's end key is the next one's start key;
+ * polyline p is order[loop_offsets[p] .. loop_offsets[p + 1]) and closed[p] says whether its last
+ * segment ends where its first starts (loop_offsets: n_segments + 1 entries, closed: n_segments).
+ * Open chains come first: each starts at a key no segment ends on (the contour meets the rect there),
+ * in the order of their first segments.  Closed loops follow, each from its lowest-indexed segment, in
+ * the order of those.  Returns the number of polylines, or -1 if a key starts two segments or ends
+ * two (implisolid_slice never produces that). */
+int64_t implisolid_slice_loops(const uint32_t* keys, int64_t n_segments, int64_t* order, int64_t* loop_offsets,
+                               uint8_t* closed);
+
 /* host-only: compile an MP5 tree to the node program; info = {n_instr, depth, n_mats, 0};
    mats_out receives n_mats inverse matrices (12 floats each, up to 256) */
 /* Additive, host only (no GPU): generate and hipRTC-compile the tree kernel for this shape.
