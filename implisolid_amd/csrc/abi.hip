@@ -1556,7 +1556,7 @@ int32_t* implisolid_slab_faces(implisolid_slab* s) { return s->engine.d_faces();
 float* implisolid_slab_field(implisolid_slab* s) { return s->engine.d_field(); }
 
 int implisolid_slab_stats_n(implisolid_slab* s, int64_t* out, int n) {
-    constexpr int kStats = 10;
+    constexpr int kStats = 13;
     try {
         if (!out || n < 0) throw InputError("slab_stats: null output or negative length");
         uint32_t c[16];
@@ -1569,7 +1569,11 @@ int implisolid_slab_stats_n(implisolid_slab* s, int64_t* out, int n) {
             g.n_cells,
             c[14],       // mixed coarse boxes of the last eval (the fill kernel's copy of [13])
             c[1],        // the vertex pass's copy of the halo count (mc_types.hpp counters)
-            c[0]};       // unit parts
+            // unit parts: c[0] counts the vertex pass's wave work items, two small units (c[8]) to one
+            (int64_t)c[0] + c[8] / 2,
+            c[8],        // small units (paired in the vertex pass, mc_types.hpp kPairCells)
+            c[7],        // heavy units' parts
+            c[0]};       // wave work items of the vertex pass
         for (int k = 0; k < n && k < kStats; ++k) out[k] = v[k];
         return kStats;
     } catch (const std::exception& e) {

@@ -108,7 +108,7 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t x) {
 // Per-unit sums through LDS atomics.
 //   -> unit_cnt[64 group + k] = k-th non-empty unit of the group {unit in group, own / tri / act
 //      exclusive bases in the group}; scan_blk[c][group] = the group's sums (own, tri, act, halo
-//      own, non-empty units), read by k_unit_scan.
+//      own, heavy / light parts, small units, non-empty units), read by k_unit_scan.
 __device__ __forceinline__ void mc_count_body(const GridDesc& g, const MCBuffers& b) {
     __shared__ uint32_t s_u[kGroupUnits][4];
     __shared__ uint32_t s_cm[kGroupUnits];   // per unit: its chunks holding non-trivial cells (bit c)
@@ -163,13 +163,16 @@ __device__ __forceinline__ void mc_count_body(const GridDesc& g, const MCBuffers
         }
         uint32_t* d = s_u[ui];
         if (own) atomicAdd(&d[0], own);
-        if (tri) { atomicAdd(&d[1], tri); atomicAdd(&d[2], act); }
+        if (tri) atomicAdd(&d[1], tri);
+        // active cells (low half) and non-trivial cells, halo layer included (high half): a unit
+        // holds at most kUnitRows * m < 2^15 cells
+        atomicAdd(&d[2], act | ((uint32_t)__popcll((unsigned long long)k.nt) << 16));
         if (hal) atomicAdd(&d[3], hal);
     }
     __syncthreads();
     if (t < 64) {   // wave 0, one lane per unit of the group (kGroupUnits == 64; blockDim >= 64)
         const int64_t u = G * kGroupUnits + t;
-        const uint32_t own = s_u[t][0], tri = s_u[t][1], act = s_u[t][2], hal = s_u[t][3];
+        const uint32_t own = s_u[t][0], tri = s_u[t][1], act = s_u[t][2] & 0xffffu, ntc = s_u[t][2] >> 16, hal = s_u[t][3];
         const bool ne = u < nu && (own | tri) != 0;
         // the group's non-empty units in order, with their exclusive bases inside the group
         const uint32_t eo = wave_incl_scan<uint32_t>(own, t) - own;
@@ -181,19 +184,27 @@ __device__ __forceinline__ void mc_count_body(const GridDesc& g, const MCBuffers
         // units' parts (mc_types.hpp kHeavyCells) and light units' parts counted apart
         const uint32_t parts = ne ? min((uint32_t)kMaxParts, max(1u, (act + kPartCells - 1) / kPartCells)) : 0u;
         const bool heavy = act > kHeavyCells;
-        const uint32_t ph = heavy ? parts : 0u, pl = heavy ? 0u : parts;
+        // small (mc_types.hpp kPairCells): all its non-trivial cells (the halo layer's too) are one
+        // half-wave window, and the rows of its masked chunks one half-wave of items
+        const bool small = ne && ntc <= kPairCells && nch <= kChunkMaskBits &&
+                           (uint32_t)(kUnitRows * __popc(s_cm[t])) <= kPairCells;
+        const uint32_t ph = heavy ? parts : 0u, pl = (heavy || small) ? 0u : parts, ps = small ? 1u : 0u;
         const uint32_t eph = wave_incl_scan<uint32_t>(ph, t) - ph, epl = wave_incl_scan<uint32_t>(pl, t) - pl;
+        const uint64_t msm = __ballot(small);
+        const uint32_t eps = (uint32_t)__popcll((unsigned long long)(msm & ((1ull << t) - 1ull)));
         if (ne) {
             b.unit_cnt[G * kGroupUnits + pos] = make_uint4((uint32_t)t, eo, et, ea);
-            b.unit_part[G * kGroupUnits + pos] = (heavy ? eph : epl) | (parts << 16) | ((uint32_t)heavy << 20);
+            b.unit_part[G * kGroupUnits + pos] =
+                (heavy ? eph : small ? eps : epl) | (parts << 16) | ((uint32_t)heavy << 20) | (ps << 21);
             b.unit_cmask[G * kGroupUnits + pos] = s_cm[t];
         }
         const uint32_t sums[kScanParts + 1] = {__shfl(eo + own, 63, 64), __shfl(et + tri, 63, 64),
                                                __shfl(ea + act, 63, 64), wave_sum(hal), __shfl(eph + ph, 63, 64),
-                                               __shfl(epl + pl, 63, 64), (uint32_t)__popcll((unsigned long long)m)};
+                                               __shfl(epl + pl, 63, 64), (uint32_t)__popcll((unsigned long long)msm),
+                                               (uint32_t)__popcll((unsigned long long)m)};
         if (t <= kScanParts) {
             const uint32_t v = t == 0 ? sums[0] : t == 1 ? sums[1] : t == 2 ? sums[2] : t == 3 ? sums[3]
-                             : t == 4 ? sums[4] : t == 5 ? sums[5] : sums[6];
+                             : t == 4 ? sums[4] : t == 5 ? sums[5] : t == 6 ? sums[6] : sums[7];
             b.scan_blk[(int64_t)t * gridDim.x + G] = v;
         }
     }
@@ -221,7 +232,7 @@ __device__ __forceinline__ void unit_scan_body(const GridDesc& g, const MCBuffer
     const uint4 e = b.unit_cnt[G * kGroupUnits + (t < (int)nne ? t : 0)];
     const uint32_t pp = b.unit_part[G * kGroupUnits + (t < (int)nne ? t : 0)];
     const uint32_t cm = b.unit_cmask[G * kGroupUnits + (t < (int)nne ? t : 0)];
-    uint32_t acc[kScanRows] = {0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    uint32_t acc[kScanRows] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
 #pragma unroll 4
     for (int64_t i = t; i < G; i += BS)
 #pragma unroll
@@ -242,26 +253,31 @@ __device__ __forceinline__ void unit_scan_body(const GridDesc& g, const MCBuffer
     if (t < (int)nne) {
         const uint4 ent = make_uint4((uint32_t)(G * kGroupUnits) + e.x, s_base[0] + e.y, s_base[1] + e.z, s_base[2] + e.w);
         const uint32_t P = (pp >> 16) & 15u;
-        const bool heavy = (pp >> 20) & 1u;
-        // heavy parts from the list's front, light parts from its end backwards
-        const uint32_t r = (heavy ? s_base[4] : s_base[5]) + (pp & 0xffffu);
+        const bool heavy = (pp >> 20) & 1u, small = (pp >> 21) & 1u;
+        // heavy parts from the list's front; from its end backwards, interleaved, the light parts
+        // (odd distances) and the small units by their global index (even distances: the halves of
+        // pair p are the small units 2 p and 2 p + 1)
+        const uint32_t r = (heavy ? s_base[4] : small ? s_base[6] : s_base[5]) + (pp & 0xffffu);
         for (uint32_t q = 0; q < P; ++q) {
-            const uint32_t at = heavy ? r + q : b.cap_parts - 1u - (r + q);
+            const uint32_t at = heavy ? r + q : b.cap_parts - (small ? 2u : 1u) - 2u * (r + q);
             b.ulist[at] = ent;
             b.upart[at] = q | (P << 4) | (cm << 8);
         }
     }
     if (last && t == 0) {
         const uint32_t nh = s_base[4] + b.scan_blk[4 * ng + G];
+        const uint32_t ns = s_base[6] + b.scan_blk[6 * ng + G];
         b.counters[7] = nh;                                       // heavy parts (the list's front)
-        b.counters[0] = nh + s_base[5] + b.scan_blk[5 * ng + G];  // unit parts
+        b.counters[8] = ns;                                       // small units, two to a wave
+        // the vertex pass's wave work items: heavy parts, pairs (an odd last one half empty), light parts
+        b.counters[0] = nh + (ns + 1u) / 2u + s_base[5] + b.scan_blk[5 * ng + G];
         b.counters[1] = s_base[3] + b.scan_blk[3 * ng + G];       // halo-owned vertices (ids below the slab's first)
         b.counters[2] = s_base[0] + b.scan_blk[G];                // owned vertices incl. halo
         b.counters[3] = s_base[1] + b.scan_blk[ng + G];           // triangles
         b.counters[4] = s_base[2] + b.scan_blk[2 * ng + G];       // active cells (face records)
         b.counters[5] = s_base[3] + b.scan_blk[3 * ng + G];       // = [1]: [2, 6) is the totals block
                                                                   // copy_counts / read_counts take whole
-        b.counters[6] = s_base[6] + nne;                          // non-empty units (statistics)
+        b.counters[6] = s_base[7] + nne;                          // non-empty units (statistics)
     }
 }
 __global__ __launch_bounds__(kScanBlock) void k_unit_scan(GridDesc g, MCBuffers b) { unit_scan_body<>(g, b); }
@@ -351,7 +367,8 @@ template <int B>
 __global__ __launch_bounds__(B) void k_unit_scan_b(const ObjArgs* __restrict__ objs, GridDesc g) {
     unit_scan_body<B>(g, objs[blockIdx.y].mc);
 }
-// vertex pass: one flat index over every object's unit parts (batch_device.hpp), a wave per part
+// vertex pass: one flat index over every object's work items (unit parts and pairs of small units;
+// batch_device.hpp), a wave per item
 __global__ __launch_bounds__(64 * kVertsWaves) void k_mc_cells_b(const CaseInfo* __restrict__ cases,
                                                                 const ObjArgs* __restrict__ objs, int n, GridDesc g) {
     __shared__ uint32_t s_cw[256];
@@ -360,10 +377,10 @@ __global__ __launch_bounds__(64 * kVertsWaves) void k_mc_cells_b(const CaseInfo*
     __shared__ uint32_t s_pre[kMaxBatchObjects + 4];
     const int t = threadIdx.x, wid = t >> 6;
     for (int k = t; k < 256; k += blockDim.x) s_cw[k] = case_word(cases[k]);
-    const uint32_t total = batch_prefix(objs, n, 0, 1u, 0xffffffffu, s_pre);   // counters[0]: unit parts
+    const uint32_t total = batch_prefix(objs, n, 0, 1u, 0xffffffffu, s_pre);   // counters[0]: wave work items
     for (uint32_t e = blockIdx.x * kVertsWaves + wid; e < total; e += gridDim.x * kVertsWaves) {
         const int k = __builtin_amdgcn_readfirstlane(batch_object_of(s_pre, n, e));
-        mc_cells_part(s_cw, g, objs[k].mc, e - s_pre[k], s_bits[wid], s_excl[wid]);
+        mc_cells_item(s_cw, g, objs[k].mc, e - s_pre[k], s_bits[wid], s_excl[wid]);
     }
 }
 // every object's counter block into one array (config 5's setup reads all of them with one copy)

@@ -6,11 +6,12 @@
 
 namespace impli {
 
-template <typename T>
+// inclusive scan over segments of W lanes (lane: the lane's index in its segment)
+template <typename T, int W = 64>
 __device__ __forceinline__ T wave_incl_scan(T x, int lane) {
 #pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T y = __shfl_up(x, o, 64);
+    for (int o = 1; o < W; o <<= 1) {
+        const T y = __shfl_up(x, o, W);
         if (lane >= o) x += y;
     }
     return x;
@@ -136,6 +137,17 @@ __device__ __forceinline__ int select_bit(uint64_t x, uint32_t r) {
     return pos;
 }
 
+// position of the r-th set bit of a 32-bit x (r < popcount(x))
+__device__ __forceinline__ int select_bit32(uint32_t x, uint32_t r) {
+    int pos = 0;
+#pragma unroll
+    for (int w = 16; w > 0; w >>= 1) {
+        const uint32_t c = (uint32_t)__popc(x & ((1u << w) - 1u));
+        if (r >= c) { r -= c; x >>= w; pos += w; }
+    }
+    return pos;
+}
+
 // Waves take the parts of the non-empty units from the flat list (k_unit_scan) grid-stride: every
 // resident wave gets an equal share whatever the surface's distribution over groups, and a heavy
 // unit (up to ~2000 cells) is spread over up to kMaxParts waves instead of serialising its 64-cell
@@ -154,7 +166,72 @@ __device__ __forceinline__ uint32_t case_word(const CaseInfo& c) {
     return w;
 }
 
-__device__ __forceinline__ void mc_cells_part(const uint32_t* s_cw, const GridDesc& g, const MCBuffers& b, uint32_t e,
+// One selected cell of the vertex pass, by its lane (has == false: a lane without a cell): the
+// positions of its owned crossing edges, its owned ids at its cell id, its record.  vrun / frun /
+// arun: the cell's vertex, face and record bases (H: the halo-owned vertices below the slab's ids).
+__device__ __forceinline__ void cell_emit(const GridDesc& g, const MCBuffers& b, uint32_t H, bool has, bool emit,
+                                          int64_t erow, int x, int z, uint32_t L, unsigned ci, uint32_t cw, unsigned own,
+                                          unsigned act, uint32_t vrun, uint32_t frun, uint32_t arun) {
+    const int y = (int)erow % g.m + 1;
+    const int sx = x - 1, sy = y - 1, sl = z - g.fz0;
+    // corners 7 (1,1,1), 5 (1,0,1), 6 (0,1,1), 3 (1,1,0) of the brick-major field
+    // (grid.hpp field_index, split into per-axis terms); lanes without a cell read
+    // sample 0
+    const int cx = has ? sx : 0, cy = has ? sy : 0, cl = has ? sl : 0, d = has ? 1 : 0;
+    const uint32_t fx0 = field_x_term(cx), fx1 = field_x_term(cx + d);
+    const uint32_t fy0 = field_y_term(g, cy), fy1 = field_y_term(g, cy + d);
+    const int64_t fl0 = field_layer_term(g, cl), fl1 = field_layer_term(g, cl + d);
+    const float r7 = b.field[fl1 + (fy1 + fx1)];
+    const float r5 = b.field[fl1 + (fy0 + fx1)];
+    const float r6 = b.field[fl1 + (fy1 + fx0)];
+    const float r3 = b.field[fl0 + (fy1 + fx1)];
+    const bool sx1 = sealed_xy(g, sx + 1), sy1 = sealed_xy(g, sy + 1), sz1 = sealed_z(g, sl + 1);
+    const bool sx0 = sealed_xy(g, sx), sy0 = sealed_xy(g, sy), sz0 = sealed_z(g, sl);
+    const float f7 = (sx1 || sy1 || sz1) ? kSealed : r7;
+    const float f5 = (sx1 || sy0 || sz1) ? kSealed : r5;
+    const float f6 = (sx0 || sy1 || sz1) ? kSealed : r6;
+    const float f3 = (sx1 || sy1 || sz0) ? kSealed : r3;
+    // the cell's owned ids (slot order 5, 6, 10; an unused slot's word is never read)
+    uint32_t ids[3];
+#pragma unroll
+    for (int slot = 0; slot < 3; ++slot) ids[slot] = vrun + (uint32_t)((cw >> (5 + 3 * slot)) & 7u) - 1u - H;
+    if (has && own) {
+        const float fx = ((float)x + g.i0[0]) * g.w[0];
+        const float fy = ((float)y + g.i0[1]) * g.w[1];
+        const float fz = ((float)z + g.i0[2]) * g.w[2];
+        const float fx2 = fx + g.w[0], fy2 = fy + g.w[1], fz2 = fz + g.w[2];
+#pragma unroll
+        for (int slot = 0; slot < 3; ++slot) {
+            const int r = (int)((cw >> (5 + 3 * slot)) & 7u) - 1;
+            if (r < 0 || !emit) continue;
+            const uint32_t out = ids[slot];
+            if (out >= (uint64_t)b.cap_v) { *b.overflow = 1u; continue; }
+            float px, py, pz;
+            if (slot == 0) { const float mu = (0.f - f5) / (f7 - f5); px = fx2; py = fy + mu * g.w[1]; pz = fz2; }
+            else if (slot == 1) { const float mu = (0.f - f6) / (f7 - f6); px = fx + mu * g.w[0]; py = fy2; pz = fz2; }
+            else { const float mu = (0.f - f3) / (f7 - f3); px = fx2; py = fy2; pz = fz + mu * g.w[2]; }
+            b.verts[3 * (size_t)out] = px; b.verts[3 * (size_t)out + 1] = py; b.verts[3 * (size_t)out + 2] = pz;
+        }
+        // the cell's owned ids by cell id (halo cells too: the slab's layer below its
+        // first emitted one), where the face pass looks its owners up
+        *reinterpret_cast<IdTriple*>(b.vid + (size_t)L * 3) = IdTriple{ids[0], ids[1], ids[2]};
+    }
+    if (act) {   // an active cell: its record, at its record index
+        if (arun < (uint64_t)b.cap_rec) b.records[arun] = make_uint4(L, ci, frun, (uint32_t)erow);
+        else *b.overflow = 1u;
+    }
+}
+
+// chunk_ci of the staged item q (bits: the wave's LDS copy of the items' sign words), cell j
+__device__ __forceinline__ unsigned staged_ci(const uint64_t (*bits)[64], int q, int j) {
+    return (unsigned)((bits[0][q] >> j) & 1u) | ((unsigned)((bits[1][q] >> j) & 1u) << 1) |
+           ((unsigned)((bits[3][q] >> j) & 1u) << 2) | ((unsigned)((bits[2][q] >> j) & 1u) << 3) |
+           ((unsigned)((bits[4][q] >> j) & 1u) << 4) | ((unsigned)((bits[5][q] >> j) & 1u) << 5) |
+           ((unsigned)((bits[7][q] >> j) & 1u) << 6) | ((unsigned)((bits[6][q] >> j) & 1u) << 7);
+}
+
+// at: the part's place in the flat list
+__device__ __forceinline__ void mc_cells_part(const uint32_t* s_cw, const GridDesc& g, const MCBuffers& b, uint32_t at,
                                               uint64_t (*bits)[64], uint32_t* excl) {
     const int lane = threadIdx.x & 63;
     const uint32_t H = b.counters[1];
@@ -162,13 +239,10 @@ __device__ __forceinline__ void mc_cells_part(const uint32_t* s_cw, const GridDe
     const int64_t rows = n_rows(g);
     const int items = kUnitRows * nch;
     {
-        // the e-th part: heavy parts from the list's front, then the light ones from its end
-        const uint32_t nh = b.counters[7];
-        e = e < nh ? e : b.cap_parts - 1u - (e - nh);
-        const uint4 ent = b.ulist[e];   // {unit, vbase, fbase, abase}
+        const uint4 ent = b.ulist[at];   // {unit, vbase, fbase, abase}
         // part | parts << 4 | chunk mask << 8: this wave emits windows w % parts == part; the unit's
         // chunks without a non-trivial cell (k_mc_count) are not loaded
-        const uint32_t up = b.upart[e];
+        const uint32_t up = b.upart[at];
         const uint32_t part = up & 15u, parts = (up >> 4) & 15u;
         const uint32_t cmask = nch <= kChunkMaskBits ? up >> 8 : ~0u;
         const int64_t u = ent.x;
@@ -204,12 +278,7 @@ __device__ __forceinline__ void mc_cells_part(const uint32_t* s_cw, const GridDe
                 for (int step = 32; step > 0; step >>= 1)
                     if (excl[q + step] <= ce) q += step;
                 const int j = has ? select_bit(bits[8][q], ce - excl[q]) : 0;
-                const unsigned ci =
-                    has ? (unsigned)((bits[0][q] >> j) & 1u) | ((unsigned)((bits[1][q] >> j) & 1u) << 1) |
-                              ((unsigned)((bits[3][q] >> j) & 1u) << 2) | ((unsigned)((bits[2][q] >> j) & 1u) << 3) |
-                              ((unsigned)((bits[4][q] >> j) & 1u) << 4) | ((unsigned)((bits[5][q] >> j) & 1u) << 5) |
-                              ((unsigned)((bits[7][q] >> j) & 1u) << 6) | ((unsigned)((bits[6][q] >> j) & 1u) << 7)
-                        : 0u;   // chunk_ci of item q, cell j
+                const unsigned ci = has ? staged_ci(bits, q, j) : 0u;
                 const int it = i0 + q;
                 const int64_t erow = u * kUnitRows + it / nch;
                 const int x = 64 * (it % nch) + 1 + j;
@@ -223,57 +292,9 @@ __device__ __forceinline__ void mc_cells_part(const uint32_t* s_cw, const GridDe
                 const unsigned inc = wave_incl_scan<unsigned>(p, lane);
                 const unsigned pre = inc - p, tot = __shfl(inc, 63, 64);
                 const uint32_t vrun = vrun0 + fld(pre, 0);
-                if (mine) {
-                    const int y = (int)erow % g.m + 1;
-                    const int sx = x - 1, sy = y - 1, sl = z - g.fz0;
-                    // corners 7 (1,1,1), 5 (1,0,1), 6 (0,1,1), 3 (1,1,0) of the brick-major field
-                    // (grid.hpp field_index, split into per-axis terms); lanes without a cell read
-                    // sample 0
-                    const int cx = has ? sx : 0, cy = has ? sy : 0, cl = has ? sl : 0, d = has ? 1 : 0;
-                    const uint32_t fx0 = field_x_term(cx), fx1 = field_x_term(cx + d);
-                    const uint32_t fy0 = field_y_term(g, cy), fy1 = field_y_term(g, cy + d);
-                    const int64_t fl0 = field_layer_term(g, cl), fl1 = field_layer_term(g, cl + d);
-                    const float r7 = b.field[fl1 + (fy1 + fx1)];
-                    const float r5 = b.field[fl1 + (fy0 + fx1)];
-                    const float r6 = b.field[fl1 + (fy1 + fx0)];
-                    const float r3 = b.field[fl0 + (fy1 + fx1)];
-                    const bool sx1 = sealed_xy(g, sx + 1), sy1 = sealed_xy(g, sy + 1), sz1 = sealed_z(g, sl + 1);
-                    const bool sx0 = sealed_xy(g, sx), sy0 = sealed_xy(g, sy), sz0 = sealed_z(g, sl);
-                    const float f7 = (sx1 || sy1 || sz1) ? kSealed : r7;
-                    const float f5 = (sx1 || sy0 || sz1) ? kSealed : r5;
-                    const float f6 = (sx0 || sy1 || sz1) ? kSealed : r6;
-                    const float f3 = (sx1 || sy1 || sz0) ? kSealed : r3;
-                    // the cell's owned ids (slot order 5, 6, 10; an unused slot's word is never read)
-                    uint32_t ids[3];
-#pragma unroll
-                    for (int slot = 0; slot < 3; ++slot) ids[slot] = vrun + (uint32_t)((cw >> (5 + 3 * slot)) & 7u) - 1u - H;
-                    if (has && own) {
-                        const float fx = ((float)x + g.i0[0]) * g.w[0];
-                        const float fy = ((float)y + g.i0[1]) * g.w[1];
-                        const float fz = ((float)z + g.i0[2]) * g.w[2];
-                        const float fx2 = fx + g.w[0], fy2 = fy + g.w[1], fz2 = fz + g.w[2];
-#pragma unroll
-                        for (int slot = 0; slot < 3; ++slot) {
-                            const int r = (int)((cw >> (5 + 3 * slot)) & 7u) - 1;
-                            if (r < 0 || !emit) continue;
-                            const uint32_t out = ids[slot];
-                            if (out >= (uint64_t)b.cap_v) { *b.overflow = 1u; continue; }
-                            float px, py, pz;
-                            if (slot == 0) { const float mu = (0.f - f5) / (f7 - f5); px = fx2; py = fy + mu * g.w[1]; pz = fz2; }
-                            else if (slot == 1) { const float mu = (0.f - f6) / (f7 - f6); px = fx + mu * g.w[0]; py = fy2; pz = fz2; }
-                            else { const float mu = (0.f - f3) / (f7 - f3); px = fx2; py = fy2; pz = fz + mu * g.w[2]; }
-                            b.verts[3 * (size_t)out] = px; b.verts[3 * (size_t)out + 1] = py; b.verts[3 * (size_t)out + 2] = pz;
-                        }
-                        // the cell's owned ids by cell id (halo cells too: the slab's layer below its
-                        // first emitted one), where the face pass looks its owners up
-                        *reinterpret_cast<IdTriple*>(b.vid + (size_t)L * 3) = IdTriple{ids[0], ids[1], ids[2]};
-                    }
-                    if (act) {   // an active cell: its record, at its record index
-                        const uint32_t arun = arun0 + fld(pre, 2);
-                        if (arun < (uint64_t)b.cap_rec) b.records[arun] = make_uint4(L, ci, frun0 + fld(pre, 1), (uint32_t)erow);
-                        else *b.overflow = 1u;
-                    }
-                }
+                if (mine)
+                    cell_emit(g, b, H, has, emit, erow, x, z, L, ci, cw, own, act, vrun, frun0 + fld(pre, 1),
+                              arun0 + fld(pre, 2));
                 vrun0 += fld(tot, 0);
                 frun0 += fld(tot, 1);
                 arun0 += fld(tot, 2);
@@ -282,17 +303,92 @@ __device__ __forceinline__ void mc_cells_part(const uint32_t* s_cw, const GridDe
     }
 }
 
+// A pair of small units (mc_types.hpp kPairCells) by one wave: lanes 0-31 take the small unit
+// 2 p, lanes 32-63 the small unit 2 p + 1, each as mc_cells_part takes a one-window unit, with its
+// own list entry, its own half of the LDS scratch, and scans and shuffles of width 32.  A half's
+// items are the unit's rows times the chunks its mask names (row-major, so still in cell order;
+// k_mc_count made sure they are at most 32).  ns: the small units; an odd last one leaves its
+// pair's second half without cells (that half reads the first half's entry).
+__device__ __forceinline__ void mc_cells_pair(const uint32_t* s_cw, const GridDesc& g, const MCBuffers& b, uint32_t p,
+                                              uint32_t ns, uint64_t (*bits)[64], uint32_t* excl) {
+    // (the lane index taken through an empty asm: otherwise everything derived from it here -- the
+    // half-wave scans' lane masks among it -- is hoisted out of the caller's loop and kept in
+    // registers across the part path, which then spills)
+    int lane = threadIdx.x & 63;
+    asm volatile("" : "+v"(lane));
+    const int hl = lane & 31, hb = lane & 32;   // lane in its half; the half's first lane
+    const uint32_t H = b.counters[1];
+    const int64_t rows = n_rows(g);
+    const uint32_t k = 2u * p + (uint32_t)(lane >> 5);
+    const bool live = k < ns;
+    const uint32_t at = b.cap_parts - 2u - 2u * (live ? k : k - 1u);
+    const uint4 ent = b.ulist[at];   // {unit, vbase, fbase, abase}
+    const uint32_t cmask = b.upart[at] >> 8;
+    const int nc = max(1, (int)__popc(cmask));   // <= kPairCells / kUnitRows = 8
+    const uint32_t u = ent.x;
+    // the half's item hl: row hl / nc of the unit, the (hl % nc)-th chunk of the mask; lanes past
+    // the items read row 0's first chunk and drop it (no branch around the loads).  hl / nc as
+    // hl * ceil(256 / nc) >> 8, exact for hl < 32 and nc <= 8 (the bytes: ceil(256 / nc) - 1)
+    const int ir = (int)(((uint32_t)hl * ((uint32_t)((0x1F242A333F557FFFull >> (8 * (nc - 1))) & 0xffu) + 1u)) >> 8);
+    const uint32_t irow = u * kUnitRows + (uint32_t)ir;   // rows of a slab < 2^31 (load_chunk)
+    const bool item = live && cmask != 0u && ir < kUnitRows && (int64_t)irow < rows;
+    const int ic = select_bit32(cmask, (uint32_t)(hl - ir * nc));
+    ChunkBits kb;
+    load_chunk(g, b.signs, item ? (int64_t)irow : 0, item ? ic : 0, kb);
+    if (!item) kb.nt = 0;
+    const uint32_t cnt = (uint32_t)__popcll((unsigned long long)kb.nt);
+    const uint32_t incl = wave_incl_scan<uint32_t, 32>(cnt, hl);
+    const uint32_t total = __shfl(incl, 31, 32);   // <= kPairCells: one window
+    __builtin_amdgcn_wave_barrier();   // the wave's previous LDS reads are done
+    bits[0][lane] = kb.s00; bits[1][lane] = kb.t00; bits[2][lane] = kb.s10; bits[3][lane] = kb.t10;
+    bits[4][lane] = kb.s01; bits[5][lane] = kb.t01; bits[6][lane] = kb.s11; bits[7][lane] = kb.t11;
+    bits[8][lane] = kb.nt;
+    // beside the item's exclusive cell count (<= 32, bits 0-7): its chunk and its row in the unit
+    excl[lane] = (incl - cnt) | ((uint32_t)ic << 8) | ((uint32_t)ir << 16);
+    __builtin_amdgcn_wave_barrier();
+    const uint32_t ce = (uint32_t)hl;
+    const bool has = ce < total;
+    int q = 0;   // the half's item holding cell ce (as in mc_cells_part, over 32 items)
+#pragma unroll
+    for (int step = 16; step > 0; step >>= 1)
+        if ((excl[hb + q + step] & 0xffu) <= ce) q += step;
+    const uint32_t qw = excl[hb + q];
+    const int j = has ? select_bit(bits[8][hb + q], ce - (qw & 0xffu)) : 0;
+    const unsigned ci = has ? staged_ci(bits, hb + q, j) : 0u;
+    const int64_t erow = (int64_t)(u * kUnitRows + (qw >> 16));
+    const int x = 64 * (int)((qw >> 8) & 0xffu) + 1 + j;
+    const int z = (int)erow / g.m + g.cz0;
+    const uint32_t L = (uint32_t)(erow * g.m + (x - 1));
+    const uint32_t cw = s_cw[ci];
+    const unsigned c_nown = cw & 3u, c_ntri = (cw >> 2) & 7u;
+    const bool emit = has && z >= g.cz_emit;
+    const unsigned own = has ? c_nown : 0u, tri = emit ? c_ntri : 0u, act = (emit && c_ntri) ? 1u : 0u;
+    const unsigned pk = pack3(own, tri, act);
+    const unsigned pre = wave_incl_scan<unsigned, 32>(pk, hl) - pk;
+    cell_emit(g, b, H, has, emit, erow, x, z, L, ci, cw, own, act, ent.y + fld(pre, 0), ent.z + fld(pre, 1),
+              ent.w + fld(pre, 2));
+}
+
+// the e-th wave work item of a slab's vertex pass: the heavy parts (the list's front), then the
+// pairs of small units, then the light parts (k_unit_scan)
+__device__ __forceinline__ void mc_cells_item(const uint32_t* s_cw, const GridDesc& g, const MCBuffers& b, uint32_t e,
+                                              uint64_t (*bits)[64], uint32_t* excl) {
+    const uint32_t nh = b.counters[7], ns = b.counters[8], np = (ns + 1u) / 2u;
+    if (e >= nh && e - nh < np) mc_cells_pair(s_cw, g, b, e - nh, ns, bits, excl);
+    else mc_cells_part(s_cw, g, b, e < nh ? e : b.cap_parts - 1u - 2u * (e - nh - np), bits, excl);
+}
+
 __device__ __forceinline__ void mc_cells_body(const CaseInfo* __restrict__ cases, const GridDesc& g, const MCBuffers& b) {
     __shared__ uint32_t s_cw[256];
     __shared__ uint64_t s_bits[kVertsWaves][9][64];   // per wave and item: the 8 corner words + nt
     __shared__ uint32_t s_excl[kVertsWaves][64];      // per wave and item: cells in the items before it
     const int t = threadIdx.x, wid = t >> 6;
-    const uint32_t n_ne = b.counters[0];              // non-empty units
+    const uint32_t n_ne = b.counters[0];              // wave work items
     const uint32_t w0 = blockIdx.x * kVertsWaves;
     if (w0 >= n_ne) return;                           // uniform over the block
     for (int k = t; k < 256; k += blockDim.x) s_cw[k] = case_word(cases[k]);
     __syncthreads();
-    for (uint32_t e = w0 + wid; e < n_ne; e += gridDim.x * kVertsWaves) mc_cells_part(s_cw, g, b, e, s_bits[wid], s_excl[wid]);
+    for (uint32_t e = w0 + wid; e < n_ne; e += gridDim.x * kVertsWaves) mc_cells_item(s_cw, g, b, e, s_bits[wid], s_excl[wid]);
 }
 
 }  // namespace impli

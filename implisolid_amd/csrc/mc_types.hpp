@@ -23,12 +23,18 @@ constexpr int kUnitRows = 4;
 constexpr int kGroupUnits = 64;        // units per group: one count block; the group scan's element
 constexpr int kVertsWaves = 4;         // waves per verts block (grid-stride over the unit list)
 constexpr int kVertsMaxBlocks = 4096;  // cells grid cap (2048: +1 us at 512^3)
-constexpr int kScanParts = 6;          // group sums scanned: own, tri, act, halo own, heavy / light unit parts
+constexpr int kScanParts = 7;          // group sums scanned: own, tri, act, halo own, heavy / light parts, small units
 // A unit with more than kHeavyCells active cells takes several 64-cell windows, so its parts live
 // 2-3x longer than a one-window part: the flat list holds them first (from the front) and the
 // light ones after them (placed from the list's end backwards), so the longest parts start in
 // the vertex pass's first wave generation instead of trailing it.
 constexpr uint32_t kHeavyCells = 64;
+// A small unit -- at most kPairCells non-trivial cells, in at most kPairCells (row, chunk) items of
+// the chunks its mask names -- needs half a wave: the vertex pass takes the small units two to a
+// wave (a "pair": the k-th small unit in unit order is half k & 1 of pair k >> 1; lanes 0-31 and
+// 32-63 each run the one-window path on their own unit).  The pairs run after the heavy parts and
+// before the light ones.
+constexpr uint32_t kPairCells = 32;
 // A non-empty unit with many active cells is handed to several waves ("parts"): part p of P takes
 // the unit's 64-cell windows w with w % P == p (the other windows only advance its bases).
 constexpr int kPartCells = 128;        // active cells per part
@@ -38,18 +44,22 @@ struct MCBuffers {
     const float* field;
     const uint64_t* signs;   // sign bitmap of the stored samples (grid.hpp)
     uint4* unit_cnt;         // per group, its non-empty units {unit in group, own, tri, act bases} (k_mc_count)
-    uint32_t* unit_part;     // ... and their parts: in-group part base | part count << 16
+    uint32_t* unit_part;     // ... and their parts: in-group base in their class | part count << 16 |
+                             // heavy << 20 | small << 21
     uint32_t* unit_cmask;    // ... and their chunks holding non-trivial cells (bit c, c < kChunkMaskBits)
-    uint32_t* scan_blk;      // [kScanParts + 1][n_groups]: group sums (own, tri, act, halo own, parts),
+    uint32_t* scan_blk;      // [kScanParts + 1][n_groups]: group sums (own, tri, act, halo own, parts, small units),
                              // then the group's non-empty unit count (not scanned)
     uint4* ulist;            // all parts of the non-empty units in order: {unit, vbase, fbase, abase}
     uint32_t* upart;         // ... part index | part count << 4 | the unit's chunk mask << 8 (k_unit_scan)
-    uint32_t cap_parts;      // ulist / upart entries: heavy parts at [0, H), light at [cap - L, cap)
+    uint32_t cap_parts;      // ulist / upart entries: heavy parts at [0, H); from the end backwards, the
+                             // r-th light part at cap - 1 - 2 r and the k-th small unit at cap - 2 - 2 k
+                             // (8 heavy + 2 light + 2 small units <= 8 units: the regions cannot meet)
     const uint32_t* umark;   // [unit][chunk]: the 64-cell chunks of a unit whose cells touch an evaluated
     uint32_t mark_id;        // brick hold mark_id (k_brick_fill); null: every chunk is counted (dense eval)
-    uint32_t* counters;      // [0] unit parts, [1] halo own (read by the vertex pass), [2..5] totals
+    uint32_t* counters;      // [0] the vertex pass's wave work items (heavy parts + pairs of small units +
+                             // light parts), [1] halo own (read by the vertex pass), [2..5] totals
                              // own/tri/act/halo (copied as one block; [5] == [1]), [6] non-empty units,
-                             // [7] heavy unit parts (the flat list's front)
+                             // [7] heavy unit parts (the flat list's front), [8] small units
     uint32_t* vid;           // 3 * n_cells: per cell id L, the slab-local ids (vid - H, mod 2^32) of its
                              // owned edges 5, 6, 10, written for the cells owning a crossing edge (halo
                              // layer included; unused slots undefined) -- the face pass reads an owner's

@@ -379,7 +379,9 @@ int implisolid_slab_set_timing(implisolid_slab* s, int on);
  * halo-owned vertices, cells, mixed coarse boxes of the last eval] (blocking) */
 int implisolid_slab_stats(implisolid_slab* s, int64_t out[8]);
 /* the same figures, then [halo-owned vertices as the vertex pass reads them (counter word 1, must
- * equal [5]), unit parts]: writes min(n, 10) values and returns how many exist (10), or -1 */
+ * equal [5]), unit parts, small units (the vertex pass takes them two to a wave), heavy units'
+ * parts, the vertex pass's wave work items]: writes min(n, 13) values and returns how many exist
+ * (13), or -1 */
 int implisolid_slab_stats_n(implisolid_slab* s, int64_t* out, int n);
 /* the tree kernels the slab's last eval ran: 0 the interpreter, 1 the shape's JIT module, 2 the
  * object's baked JIT module */
