@@ -53,6 +53,7 @@ ABI_SYMBOLS = [
     "implisolid_bounds", "implisolid_bounds_edges", "implisolid_fit_box", "implisolid_parse_fit_box",
     "implisolid_last_fit_box", "implisolid_debug_bounds_ms",
     "implisolid_slice", "implisolid_slice_copy", "implisolid_slice_coords", "implisolid_slice_loops",
+    "implisolid_mass", "implisolid_mass_mids", "implisolid_mass_physical",
 ]
 
 # implisolid_progress_callback (include/implisolid.h): verts, n_verts, faces, n_faces,
@@ -200,6 +201,10 @@ def lib():
         "implisolid_slice_coords": ([fp, c_int, fp, fp], c_int),
         "implisolid_slice_loops": ([up, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
                                     ctypes.POINTER(ctypes.c_uint8)], ctypes.c_int64),
+        "implisolid_mass": ([c_char_p, c_int, fp, c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int64),
+                             ctypes.POINTER(ctypes.c_int64)], c_int),
+        "implisolid_mass_mids": ([fp, c_int, fp], c_int),
+        "implisolid_mass_physical": ([fp, c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double)], c_int),
     }
     for name, (args, res) in sig.items():
         try:
@@ -785,6 +790,72 @@ def slice_polylines(shape, rect, resolution, z, ignore_root_matrix=False):
             lines.append((np.ascontiguousarray(pts), bool(closed[p])))
         out.append(lines)
     return out
+
+
+def mass_mids(box, depth):
+    """Host only: the sample table of mass_moments, float32 (3, 2^depth) (x, y, z rows):
+    mid[k] = edge[k] + 0.5f * (edge[k + 1] - edge[k]) over bounds_edges(box, depth)."""
+    fp = ctypes.POINTER(ctypes.c_float)
+    b = _box6(box, "mass_mids")
+    if not 3 <= int(depth) <= 10:
+        raise ImplisolidError("mass_mids: depth must be in [3, 10]")
+    out = np.empty((3, 1 << int(depth)), np.float32)
+    if lib().implisolid_mass_mids(b.ctypes.data_as(fp), int(depth), out.ctypes.data_as(fp)) != 0:
+        raise ImplisolidError(last_error())
+    return out
+
+
+def mass_moments(shape, box, depth, ignore_root_matrix=False, return_stats=False):
+    """The integer moments of the solid cells of `shape` on the 2^depth-cell grid of box {xmin, xmax, ymin,
+    ymax, zmin, zmax}, summed on the GPU (include/implisolid.h implisolid_mass).  Returns (moments
+    uint64 (10,) = [n, Si, Sj, Sk, Sii, Sjj, Skk, Sij, Sjk, Sik], layer_cells int64 (N,)), and with
+    return_stats also [boxes bounded, cells counted whole from solid boxes, samples evaluated, reruns
+    after a list overflow]."""
+    fp = ctypes.POINTER(ctypes.c_float)
+    b = _box6(box, "mass_moments")
+    if not 3 <= int(depth) <= 10:
+        raise ImplisolidError("mass_moments: depth must be in [3, 10]")
+    mom = np.zeros(10, np.uint64)
+    layers = np.zeros(1 << int(depth), np.int64)
+    stats = (ctypes.c_int64 * 4)()
+    rc = lib().implisolid_mass(_s(shape), int(bool(ignore_root_matrix)), b.ctypes.data_as(fp), int(depth),
+                               mom.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                               layers.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), stats)
+    if rc < 0:
+        raise ImplisolidError(last_error())
+    if return_stats:
+        return mom, layers, [int(v) for v in stats]
+    return mom, layers
+
+
+def mass_physical(box, depth, moments):
+    """Host only: (empty, out float64 (10,) = [volume, cx, cy, cz, Ixx, Iyy, Izz, Ixy, Iyz, Ixz]) from the
+    integer moments (implisolid_mass_physical)."""
+    b = _box6(box, "mass_physical")
+    m = np.ascontiguousarray(moments, np.uint64).reshape(-1)
+    if m.size != 10:
+        raise ValueError("mass_physical: ten moments")
+    out = np.zeros(10, np.float64)
+    rc = lib().implisolid_mass_physical(b.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), int(depth),
+                                        m.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                        out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+    if rc < 0:
+        raise ImplisolidError(last_error())
+    return rc == 0, out
+
+
+def mass_properties(shape, box, depth, ignore_root_matrix=False):
+    """Volume, centre of mass and inertia tensor (about the centre of mass, unit density) of the solid
+    inside box, as the union of its solid cells on the 2^depth grid: dict(volume, centre (3,), inertia
+    (3, 3), layer_area (N,), cells, moments, empty).  An empty solid gives zeros and empty = True."""
+    mom, layers = mass_moments(shape, box, depth, ignore_root_matrix)
+    empty, out = mass_physical(box, depth, mom)
+    b = _box6(box, "mass_properties").astype(np.float64)
+    N = float(1 << int(depth))
+    dx, dy = (b[1] - b[0]) / N, (b[3] - b[2]) / N
+    inertia = np.array([[out[4], out[7], out[9]], [out[7], out[5], out[8]], [out[9], out[8], out[6]]])
+    return {"volume": float(out[0]), "centre": out[1:4].copy(), "inertia": inertia,
+            "layer_area": layers.astype(np.float64) * dx * dy, "cells": int(mom[0]), "moments": mom, "empty": bool(empty)}
 
 
 def parse_fit_box(mc_settings):

@@ -1236,6 +1236,139 @@ int64_t implisolid_slice_loops(const uint32_t* keys, int64_t n_segments, int64_t
     return loops;
 }
 
+// ---- mass properties of the solid (implisolid_mass) ----------------------------------------------
+// mass.hip's passes on the current device: E lends its scratch buffers (10: state block, layer counts,
+// edge and sample tables; 11-14: the two lists, as compute_bounds takes them).  The only read-back is
+// the state block with the layer counts behind it, after the last launch; a raised overflow flag voids
+// the run, the lists grow and everything runs again (the first launch zeroes the sums).
+namespace {
+uint32_t mass_list_capacity(int depth) {
+    // as bounds_list_capacity: 8 N^2 boxes by default, clamped the same way
+    uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(8ull << (2 * depth), 4096), 1ull << 21);
+    if (const char* e = std::getenv("IMPLISOLID_MASS_LIST")) {   // read at each call (tests force the rerun path)
+        const long long v = std::atoll(e);
+        if (v > 0) cap = (uint64_t)v;
+    }
+    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(cap, 1), kBoundsMaxList);
+}
+
+bool compute_mass(Engine& E, hipStream_t s, const Program* d_prog, int prog_depth, const float* d_tab, const float box[6],
+                  int depth, uint64_t moments[10], int64_t* layer_cells, int64_t stats[4]) {
+    const int N = 1 << depth, last = depth - 2, first = std::min(3, last);
+    std::vector<float> tables((size_t)3 * (N + 1) + (size_t)3 * N);
+    bounds_edges(box, depth, tables.data());                    // validates depth and box (InputError)
+    mass_mids(box, depth, tables.data() + 3 * (N + 1));
+    const bool prune = Engine::pruning() >= 1;
+    constexpr size_t kStateBytes = 256;
+    static_assert(sizeof(MassState) <= kStateBytes, "the layer counts follow the state block");
+    const size_t head = kStateBytes + (size_t)N * sizeof(uint64_t);   // what is read back
+    uint32_t cap = mass_list_capacity(depth);
+    int64_t reruns = 0;
+    std::vector<uint64_t> h(head / sizeof(uint64_t));
+    MassState hs{};
+    for (bool uploaded = false;;) {
+        // every reserve before any pointer is taken: a DevBuf that grows moves
+        E.scratch(10).reserve(head + tables.size() * sizeof(float));
+        uint32_t* d_box[2] = {nullptr, nullptr};
+        uint64_t* d_modes[2] = {nullptr, nullptr};
+        if (prune) {
+            for (int k = 0; k < 2; ++k) {
+                E.scratch(11 + k).reserve((size_t)cap * sizeof(uint32_t));
+                E.scratch(13 + k).reserve((size_t)cap * sizeof(uint64_t));
+                d_box[k] = E.scratch(11 + k).as<uint32_t>();
+                d_modes[k] = E.scratch(13 + k).as<uint64_t>();
+            }
+        }
+        char* base = E.scratch(10).as<char>();
+        MassState* d_state = reinterpret_cast<MassState*>(base);
+        unsigned long long* d_layers = reinterpret_cast<unsigned long long*>(base + kStateBytes);
+        float* d_edges = reinterpret_cast<float*>(base + head);
+        float* d_mids = d_edges + 3 * (N + 1);
+        if (!uploaded) {
+            IMPLI_HIP(hipMemcpyAsync(d_edges, tables.data(), tables.size() * sizeof(float), hipMemcpyHostToDevice, s));
+            uploaded = true;
+        }
+        launch_mass(d_prog, prog_depth, d_tab, E.tab_range(), d_edges, d_mids, depth, prune, d_box, d_modes, cap, d_state,
+                    d_layers, s);
+        IMPLI_HIP(hipGetLastError());
+        IMPLI_HIP(hipMemcpyAsync(h.data(), base, head, hipMemcpyDeviceToHost, s));
+        IMPLI_HIP(hipStreamSynchronize(s));
+        std::memcpy(&hs, h.data(), sizeof hs);
+        if (!hs.overflow) break;
+        if (cap >= kBoundsMaxList) throw HipError("mass: list overflow at the largest capacity");
+        uint64_t want = 2ull * cap;   // the counts kept counting past the capacity: at least that many
+        for (int l = first; l <= last; ++l) want = std::max<uint64_t>(want, hs.count[l]);
+        cap = (uint32_t)std::min<uint64_t>(want, kBoundsMaxList);
+        ++reruns;
+    }
+    for (int k = 0; k < 10; ++k) moments[k] = hs.moments[k];
+    if (layer_cells)
+        for (int k = 0; k < N; ++k) layer_cells[k] = (int64_t)h[kStateBytes / sizeof(uint64_t) + (size_t)k];
+    if (stats) {
+        stats[0] = (int64_t)hs.bounded;
+        stats[1] = (int64_t)hs.whole_cells;
+        stats[2] = prune ? 64 * (int64_t)hs.count[last] : (int64_t)1 << (3 * depth);
+        stats[3] = reruns;
+    }
+    return hs.moments[0] != 0;
+}
+}  // namespace
+
+int implisolid_mass(const char* shape_json, int ignore_root_matrix, const float box[6], int depth, uint64_t moments[10],
+                    int64_t* layer_cells, int64_t stats[4]) {
+    g_last_error.clear();
+    if (!shape_json || !box || !moments) {
+        report("implisolid_mass: bad arguments", false);
+        return -1;
+    }
+    try {
+        // depth and box first: bad input is refused before anything reaches the device
+        if (depth < kBoundsMinDepth || depth > kBoundsMaxDepth) throw InputError("implisolid_mass: depth must be in [3, 10]");
+        {
+            std::vector<float> probe((size_t)3 * (1 << depth));
+            mass_mids(box, depth, probe.data());
+        }
+        ObjectTables tabs;
+        const Program p = compile_mp5(shape_json, ignore_root_matrix != 0, &tabs);
+        Engine& E = engine();
+        hipStream_t s = abi_stream();
+        TableArena arena;   // the shape's own sdf_3d tables, as implisolid_bounds builds them
+        const float* d_tab = arena.set(tabs, E.d_rabbit());
+        ProbeProgram dp(p);
+        return compute_mass(E, s, dp.get(), p.max_depth, d_tab, box, depth, moments, layer_cells, stats) ? 1 : 0;
+    } catch (const InputError& e) {
+        report(e.what(), true);
+        return -1;
+    } catch (const std::exception& e) {
+        (void)hipDeviceSynchronize();
+        report(e.what(), false);
+        return -1;
+    }
+}
+
+int implisolid_mass_mids(const float box[6], int depth, float* mids) {
+    g_last_error.clear();
+    try {
+        if (!box || !mids) throw InputError("implisolid_mass_mids: bad arguments");
+        mass_mids(box, depth, mids);
+    } catch (const std::exception& e) {
+        report(e.what(), false);
+        return -1;
+    }
+    return 0;
+}
+
+int implisolid_mass_physical(const float box[6], int depth, const uint64_t moments[10], double out[10]) {
+    g_last_error.clear();
+    try {
+        if (!box || !moments || !out) throw InputError("implisolid_mass_physical: bad arguments");
+        return mass_physical(box, depth, moments, out) ? 1 : 0;
+    } catch (const std::exception& e) {
+        report(e.what(), false);
+        return -1;
+    }
+}
+
 int implisolid_parse_fit_box(const char* mc_json, int32_t out[3]) {
     g_last_error.clear();
     try {

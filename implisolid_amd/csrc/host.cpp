@@ -173,6 +173,61 @@ bool fit_box(const float search[6], const float bounds[6], int resolution, int m
 }
 
 // ---------------------------------------------------------------------------------------------
+void mass_mids(const float box[6], int depth, float* mids) {
+    if (depth < kBoundsMinDepth || depth > kBoundsMaxDepth) throw InputError("mass: depth must be in [3, 10]");
+    const int N = 1 << depth;
+    std::vector<float> edges((size_t)3 * (N + 1));
+    bounds_edges(box, depth, edges.data());   // validates depth and box (InputError)
+    for (int a = 0; a < 3; ++a) {
+        const float* e = edges.data() + (size_t)a * (N + 1);
+        float* m = mids + (size_t)a * N;
+        for (int k = 0; k < N; ++k) {
+            const float w = e[k + 1] - e[k];
+            const float half = 0.5f * w;   // rounded on its own (-ffp-contract=off)
+            m[k] = e[k] + half;
+            // what puts a cell's sample inside every interval box that contains the cell
+            if (!(e[k] <= m[k] && m[k] <= e[k + 1])) throw InputError("mass: a cell's sample point left its cell (box too narrow for float)");
+        }
+    }
+}
+
+bool mass_physical(const float box[6], int depth, const uint64_t mom[10], double out[10]) {
+    if (depth < kBoundsMinDepth || depth > kBoundsMaxDepth) throw InputError("mass: depth must be in [3, 10]");
+    double lo[3], d[3];
+    const double N = (double)(1 << depth);
+    for (int a = 0; a < 3; ++a) {
+        const float l = box[2 * a], h = box[2 * a + 1];
+        if (!std::isfinite(l) || !std::isfinite(h) || !(l < h))
+            throw InputError("mass: the box must be finite with min < max on every axis");
+        lo[a] = (double)l;
+        d[a] = ((double)h - (double)l) / N;
+    }
+    for (int k = 0; k < 10; ++k) out[k] = 0.0;
+    const uint64_t n = mom[0];
+    if (n == 0) return false;
+    const double nd = (double)n;
+    const double cell = (d[0] * d[1]) * d[2];
+    const double volume = nd * cell;
+    out[0] = volume;
+    for (int a = 0; a < 3; ++a) out[1 + a] = lo[a] + ((double)mom[1 + a] / nd + 0.5) * d[a];
+    // central second moments from exact integers: c_ab = n S_ab - S_a S_b (negative for some cross terms)
+    auto mu = [&](int a, int b, uint64_t sab) {
+        const __int128 c = (__int128)n * (__int128)sab - (__int128)mom[1 + a] * (__int128)mom[1 + b];
+        const double q = (double)c / (nd * nd) + (a == b ? 1.0 / 12.0 : 0.0);
+        return ((volume * d[a]) * d[b]) * q;
+    };
+    const double mxx = mu(0, 0, mom[4]), myy = mu(1, 1, mom[5]), mzz = mu(2, 2, mom[6]);
+    const double mxy = mu(0, 1, mom[7]), myz = mu(1, 2, mom[8]), mxz = mu(0, 2, mom[9]);
+    out[4] = myy + mzz;
+    out[5] = mxx + mzz;
+    out[6] = mxx + myy;
+    out[7] = -mxy;
+    out[8] = -myz;
+    out[9] = -mxz;
+    return true;
+}
+
+// ---------------------------------------------------------------------------------------------
 void slice_coords(const float rect[4], int resolution, float* xs, float* ys) {
     if (resolution < 1 || resolution > kSliceMaxResolution) throw InputError("slice: resolution must be in [1, 4096]");
     for (int a = 0; a < 2; ++a) {

@@ -50,6 +50,17 @@ void bounds_edges(const float search[6], int depth, float* edges);
 // rounded to float.  False if resolution - 2 margin < 1 or margin < 0.
 bool fit_box(const float search[6], const float bounds[6], int resolution, int margin, float out[6]);
 
+// The sample points of the mass pass (implisolid_mass): per axis mid[k] = edge[k] + 0.5f * (edge[k + 1] -
+// edge[k]) over bounds_edges' table, every operation rounded to float on its own; mids: 3 N floats, x
+// then y then z.  Throws InputError as bounds_edges does, and when some edge[k] <= mid[k] <= edge[k + 1]
+// fails (a cell's sample must lie inside every interval box that contains the cell).
+void mass_mids(const float box[6], int depth, float* mids);
+// Volume, centre of mass and inertia about it from the ten integer moments [n, Si, Sj, Sk, Sii, Sjj,
+// Skk, Sij, Sjk, Sik] (include/implisolid.h implisolid_mass_physical states the arithmetic): out =
+// [volume, cx, cy, cz, Ixx, Iyy, Izz, Ixy, Iyz, Ixz].  False and zeros when n == 0; throws InputError
+// for a bad depth or box.
+bool mass_physical(const float box[6], int depth, const uint64_t moments[10], double out[10]);
+
 // The sample coordinates of a slice (implisolid_slice): R cells per axis of rect {xmin, xmax, ymin,
 // ymax}; xs[i] = xmin + (float)i * ((xmax - xmin) / (float)R) for i < R, each operation rounded to float
 // on its own, xs[R] = xmax, and ys the same way.  xs, ys: R + 1 floats each.  Throws InputError for a

@@ -88,6 +88,26 @@ void launch_bounds_levels(const Program* d_prog, int prog_depth, const float* d_
                           const float* d_edges, int depth, uint32_t* const d_box[2], uint64_t* const d_modes[2],
                           uint32_t cap, BoundsState* d_state, hipStream_t s);
 
+// Mass properties (implisolid_mass; DESIGN "Mass properties of the solid", mass.hip): the ten integer
+// moments of the solid cells' indices and the solid cells per z layer, all launches on s with no host
+// synchronisation between them.  The device state: count[l] = mixed boxes listed at level l (the last
+// level's, depth - 2, is the leaf list's length; the counts keep counting past the capacity), the
+// overflow flag (a list was full: the result is void, rerun with longer lists), the work counters and
+// the moments.
+struct MassState {
+    uint32_t count[12];
+    uint32_t overflow, pad;
+    unsigned long long bounded, whole_cells;   // boxes bounded; cells counted whole from solid boxes
+    unsigned long long moments[10];            // n, Si, Sj, Sk, Sii, Sjj, Skk, Sij, Sjk, Sik
+};
+// d_edges: 3 (2^depth + 1) floats (host.hpp bounds_edges); d_mids: 3 2^depth floats (host.hpp
+// mass_mids); d_layers: 2^depth counters; d_box / d_modes: the two alternating lists of `cap` entries
+// each, as launch_bounds_levels takes them (not read when prune is false: every leaf is evaluated
+// with modes word 0).  State and layer counts are zeroed by the first launch.
+void launch_mass(const Program* d_prog, int prog_depth, const float* d_tab, float2 tab_range, const float* d_edges,
+                 const float* d_mids, int depth, bool prune, uint32_t* const d_box[2], uint64_t* const d_modes[2],
+                 uint32_t cap, MassState* d_state, unsigned long long* d_layers, hipStream_t s);
+
 // the interpreter's stack class for a program of this depth (eval.hip: 12 slots at least, see there)
 int eval_depth(int depth);
 // exclusive scan of n uint32 into out[0 .. n], out[n] = the total (ob02.hip's scan kernels); sums:

@@ -308,6 +308,54 @@ int implisolid_slice_coords(const float rect[4], int resolution, float* xs, floa
 int64_t implisolid_slice_loops(const uint32_t* keys, int64_t n_segments, int64_t* order, int64_t* loop_offsets,
                                uint8_t* closed);
 
+/* Additive: volume, centre of mass and inertia of the solid inside a box, integrated on the GPU over
+ * the solid itself (no mesh, no reference counterpart).
+ *   box    {xmin, xmax, ymin, ymax, zmin, zmax}, finite with min < max
+ *   depth  in [3, 10]: N = 2^depth cells per axis; the cell edges are exactly those of
+ *          implisolid_bounds_edges(box, depth)
+ * The sample point of cell k on an axis is mid[k] = edge[k] + 0.5f * (edge[k + 1] - edge[k]), every
+ * operation rounded to float on its own (implisolid_mass_mids: computed once on the host and uploaded,
+ * the kernels only index the table; the host refuses a box for which some edge[k] <= mid[k] <=
+ * edge[k + 1] fails, so a cell's sample lies inside every interval box that contains the cell).
+ * Cell (i, j, k) is solid iff !(F < 0), F being implisolid_eval_points' value at (midx[i], midy[j],
+ * midz[k]): marching cubes' rule, -0.0 and NaN are solid.  The result is ten unsigned 64-bit sums over
+ * the solid cells,
+ *   moments = [n, sum i, sum j, sum k, sum i^2, sum j^2, sum k^2, sum i j, sum j k, sum i k],
+ * and layer_cells[k] (N entries, may be NULL) = the solid cells with z index k; their sum is n.  All are
+ * integers: they do not depend on the order of summation, the pruning level or the list sizes (at
+ * depth 10 the largest is about 3.6e14).
+ *   returns 1 when n > 0, 0 when the box holds no solid cell, -1 with implisolid_last_error() for a
+ *           depth outside [3, 10], a box side that is not finite with min < max (nothing is
+ *           launched), or an unsupported node
+ *   stats   (may be NULL) [boxes bounded by the interval evaluator, cells counted whole from boxes
+ *           the bound proved solid, samples evaluated, reruns after a list overflowed]
+ * At implisolid_set_pruning level >= 1 the boxes of level min(3, depth - 2) (2^level per axis, modes
+ * word 0) are bounded over their edge extent; an outside box (hi < 0) is dropped, a solid one
+ * (lo >= 0) adds the closed-form sums of its index range, a mixed one (a NaN bound included) is cut
+ * into its eight children, which are bounded with its modes word, down to level depth - 2, whose
+ * mixed boxes (4 x 4 x 4 cells) are evaluated sample by sample with their modes word (bit-identical
+ * values).  At level 0 nothing is bounded and every sample is evaluated.  Only the work differs.  One
+ * device, the interpreter kernels; the lists start at IMPLISOLID_MASS_LIST boxes (environment, read at
+ * each call; default and clamp as IMPLISOLID_BOUNDS_LIST) and grow when a level overflows them, after
+ * which everything runs again. */
+int implisolid_mass(const char* shape_json, int ignore_root_matrix, const float box[6], int depth, uint64_t moments[10],
+                    int64_t* layer_cells, int64_t stats[4]);
+/* host only (no GPU): the sample table, 3 N floats, rows x, y, z.  0, or -1 (depth, box, or a sample
+ * that left its cell) */
+int implisolid_mass_mids(const float box[6], int depth, float* mids);
+/* host only: the physical quantities of the union of the solid cells as cuboids, unit density, in
+ * double from the integers and the box: out = [volume, cx, cy, cz, Ixx, Iyy, Izz, Ixy, Iyz, Ixz], the
+ * inertia about the centre of mass.  Per axis d_a = ((double)hi_a - (double)lo_a) / N;
+ *   cell = (dx * dy) * dz, volume = (double)n * cell,
+ *   centre_a = lo_a + ((double)S_a / (double)n + 0.5) * d_a,
+ *   c_ab = n S_ab - S_a S_b exactly, in a signed 128-bit integer (a cross term can be negative), converted
+ *   to double once, mu_ab = ((volume * d_a) * d_b) * ((double)c_ab / ((double)n * (double)n) +
+ *   (a == b ? 1.0 / 12.0 : 0.0)),
+ *   Ixx = mu_yy + mu_zz, Iyy = mu_xx + mu_zz, Izz = mu_xx + mu_yy, Ixy = -mu_xy, Iyz = -mu_yz,
+ *   Ixz = -mu_xz (no fused multiply-add).  The area of layer k is layer_cells[k] * dx * dy.
+ * Returns 1, 0 with out all zero when n == 0 ("empty"), -1 (depth, box) */
+int implisolid_mass_physical(const float box[6], int depth, const uint64_t moments[10], double out[10]);
+
 /* host-only: compile an MP5 tree to the node program; info = {n_instr, depth, n_mats, 0};
    mats_out receives n_mats inverse matrices (12 floats each, up to 256) */
 /* Additive, host only (no GPU): generate and hipRTC-compile the tree kernel for this shape.
