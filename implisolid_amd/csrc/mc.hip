@@ -109,36 +109,64 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t x) {
 //   -> unit_cnt[64 group + k] = k-th non-empty unit of the group {unit in group, own / tri / act
 //      exclusive bases in the group}; scan_blk[c][group] = the group's sums (own, tri, act, halo
 //      own, heavy / light parts, small units, non-empty units), read by k_unit_scan.
+template <int BS>
 __device__ __forceinline__ void mc_count_body(const GridDesc& g, const MCBuffers& b) {
+    static_assert(BS % 64 == 0 && BS >= kGroupUnits, "whole waves; wave 0 takes a lane per unit of the group");
     __shared__ uint32_t s_u[kGroupUnits][4];
     __shared__ uint32_t s_cm[kGroupUnits];   // per unit: its chunks holding non-trivial cells (bit c)
     __shared__ uint16_t s_fp[kGroupUnits * kMaxChunks];   // the group's candidate (unit, chunk) pairs
     __shared__ uint32_t s_nf;
-    const int t = threadIdx.x, nt_ = blockDim.x;   // triangle counts: chunk_triangles (checked against the table)
-    for (int k = t; k < 4 * kGroupUnits; k += nt_) (&s_u[0][0])[k] = 0u;
-    for (int k = t; k < kGroupUnits; k += nt_) s_cm[k] = 0u;
-    if (t == 0) s_nf = 0u;
+    // the block size is the template's, not blockDim.x: that is a load from the dispatch packet
+    // which everything below waited for
+    const int t = threadIdx.x;   // triangle counts: chunk_triangles (checked against the table)
     const int64_t G = blockIdx.x;
-    const int nch = n_chunks(g);
+    const int nch = n_chunks(g), npairs = kGroupUnits * nch;
     const int64_t rows = n_rows(g), nu = n_units(g);
     const int64_t row0 = G * kGroupUnits * kUnitRows;
-    __syncthreads();
     // candidates: the (unit, chunk) pairs whose cells touch an evaluated brick (the others hold no
-    // non-trivial cell), appended in any order (the counts are sums); a wave's appends take one
-    // LDS atomic
-    for (int p0 = 0; p0 < kGroupUnits * nch; p0 += nt_) {
-        const int p = p0 + t, ui = p / nch, c = p - ui * nch;
-        const int64_t u = G * kGroupUnits + ui;
-        const bool cand = p < kGroupUnits * nch && u < nu && (!b.umark || b.umark[u * nch + c] == b.mark_id);
-        const uint64_t m = __ballot(cand);
+    // non-trivial cell), appended in any order (the counts are sums).  A step takes two rounds of
+    // BS pairs: both marks are loaded (clamped addresses, no branch) before either is used, and a
+    // wave's appends of both rounds take one LDS atomic.  The first step's marks are in flight
+    // while the block clears its sums.
+    int ui[2], ch[2];
+    bool in[2];
+    uint32_t mk[2];
+    auto marks = [&](int p0) {
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int p = p0 + q * BS + t;
+            ui[q] = p / nch;
+            ch[q] = p - ui[q] * nch;
+            in[q] = p < npairs && G * kGroupUnits + ui[q] < nu;
+            mk[q] = b.mark_id;
+        }
+        if (b.umark) {   // null: a dense eval, every chunk is a candidate
+#pragma unroll
+            for (int q = 0; q < 2; ++q) mk[q] = b.umark[in[q] ? (G * kGroupUnits + ui[q]) * nch + ch[q] : 0];
+        }
+    };
+    marks(0);
+    for (int k = t; k < 4 * kGroupUnits; k += BS) (&s_u[0][0])[k] = 0u;
+    for (int k = t; k < kGroupUnits; k += BS) s_cm[k] = 0u;
+    if (t == 0) s_nf = 0u;
+    __syncthreads();
+    for (int p0 = 0;;) {
+        const bool c0 = in[0] & (mk[0] == b.mark_id), c1 = in[1] & (mk[1] == b.mark_id);
+        const uint64_t m0 = __ballot(c0), m1 = __ballot(c1);
+        const uint32_t n0 = (uint32_t)__popcll((unsigned long long)m0), n1 = (uint32_t)__popcll((unsigned long long)m1);
+        const uint64_t below = (1ull << (t & 63)) - 1ull;
         uint32_t base = 0;
-        if ((t & 63) == 0 && m) base = atomicAdd(&s_nf, (uint32_t)__popcll((unsigned long long)m));
+        if ((t & 63) == 0 && n0 + n1) base = atomicAdd(&s_nf, n0 + n1);
         base = __shfl(base, 0, 64);
-        if (cand) s_fp[base + __popcll((unsigned long long)(m & ((1ull << (t & 63)) - 1ull)))] = (uint16_t)(ui * kMaxChunks + c);
+        if (c0) s_fp[base + __popcll((unsigned long long)(m0 & below))] = (uint16_t)(ui[0] * kMaxChunks + ch[0]);
+        if (c1) s_fp[base + n0 + __popcll((unsigned long long)(m1 & below))] = (uint16_t)(ui[1] * kMaxChunks + ch[1]);
+        p0 += 2 * BS;
+        if (p0 >= npairs) break;
+        marks(p0);
     }
     __syncthreads();
     const int n_items = (int)s_nf * kUnitRows;
-    for (int i = t; i < n_items; i += nt_) {
+    for (int i = t; i < n_items; i += BS) {
         ChunkBits k;
         const uint32_t pr = s_fp[i / kUnitRows];
         const int ui = (int)(pr / kMaxChunks), c = (int)(pr % kMaxChunks);
@@ -209,7 +237,9 @@ __device__ __forceinline__ void mc_count_body(const GridDesc& g, const MCBuffers
         }
     }
 }
-__global__ __launch_bounds__(512) void k_mc_count(GridDesc g, MCBuffers b) { mc_count_body(g, b); }
+__global__ __launch_bounds__(512) void k_mc_count(GridDesc g, MCBuffers b) { mc_count_body<512>(g, b); }
+// rows of one chunk (R <= 62): a group has 256 items
+__global__ __launch_bounds__(256) void k_mc_count_s(GridDesc g, MCBuffers b) { mc_count_body<256>(g, b); }
 
 // K2b: one block per group.  Its global bases are the sums of the groups before it, read straight
 // from L2 (kScanParts x G words, all loads in flight together; nothing waits on another block), then
@@ -360,8 +390,9 @@ __global__ __launch_bounds__(256) void k_mc_faces(const CaseInfo* __restrict__ c
 }
 
 // ---- merged launches of an object stream (ObjArgs, kernels.hpp): block row y = object y ----------
-__global__ __launch_bounds__(512) void k_mc_count_b(const ObjArgs* __restrict__ objs, GridDesc g) {
-    mc_count_body(g, objs[blockIdx.y].mc);
+constexpr int kBatchCountLanes = 128;   // (launch_batch_mc)
+__global__ __launch_bounds__(kBatchCountLanes) void k_mc_count_b(const ObjArgs* __restrict__ objs, GridDesc g) {
+    mc_count_body<kBatchCountLanes>(g, objs[blockIdx.y].mc);
 }
 template <int B>
 __global__ __launch_bounds__(B) void k_unit_scan_b(const ObjArgs* __restrict__ objs, GridDesc g) {
@@ -420,10 +451,11 @@ void launch_mc_count(const CaseInfo* d_cases, const GridDesc& g, const MCBuffers
     if (ng == 0) return;
     // lanes over the items of a group (kGroupUnits kUnitRows rows x nch chunks), whole waves, at
     // most 512: twice the resident groups of 1024-lane blocks
-    const int items = kGroupUnits * kUnitRows * ((g.m + 63) / 64);
-    const unsigned threads = (unsigned)std::min(512, (items + 63) / 64 * 64);
+    // (kGroupUnits * kUnitRows = 256 items per chunk column: 256 lanes for a one-chunk row, else 512;
+    // the block size is a template argument of the kernel)
     (void)d_cases;
-    k_mc_count<<<(unsigned)ng, threads, 0, s>>>(g, b);
+    if (n_chunks(g) == 1) k_mc_count_s<<<(unsigned)ng, 256, 0, s>>>(g, b);
+    else k_mc_count<<<(unsigned)ng, 512, 0, s>>>(g, b);
 }
 
 void launch_mc_scan(const GridDesc& g, const MCBuffers& b, hipStream_t s) {
@@ -449,7 +481,6 @@ namespace impli {
 
 // grids of the flat merged vertex / face kernels
 constexpr unsigned kBatchCellBlocks = 4096, kBatchFaceBlocks = 2048;
-constexpr int kBatchCountLanes = 128;
 
 void launch_gather_counters(const ObjArgs* d_objs, int n, uint32_t* d_out, hipStream_t s) {
     if (n > 0) k_gather_counters<<<(unsigned)((n * kCounterWords + 255) / 256), 256, 0, s>>>(d_objs, n, d_out);
@@ -467,9 +498,8 @@ void launch_batch_mc(const ObjArgs* d_objs, int n, const CaseInfo* d_cases, cons
     // costs -- n objects' groups as blocks of kBatchCountLanes lanes (the single-grid path's 512-lane
     // blocks: 4x the waves of a 512^3 grid's count for the same samples).  The scan of <= 64 groups
     // reads them with one wave.
-    const int items = kGroupUnits * kUnitRows * ((g.m + 63) / 64);
-    const unsigned threads = (unsigned)std::min(kBatchCountLanes, (items + 63) / 64 * 64);
-    k_mc_count_b<<<dim3((unsigned)ng, (unsigned)n), threads, 0, s>>>(d_objs, g);
+    // (a group has at least kGroupUnits * kUnitRows = 256 items, so the blocks are always full)
+    k_mc_count_b<<<dim3((unsigned)ng, (unsigned)n), kBatchCountLanes, 0, s>>>(d_objs, g);
     if (ng <= 64) k_unit_scan_b<64><<<dim3((unsigned)ng, (unsigned)n), 64, 0, s>>>(d_objs, g);
     else k_unit_scan_b<kScanBlock><<<dim3((unsigned)ng, (unsigned)n), kScanBlock, 0, s>>>(d_objs, g);
     (void)nu;
