@@ -54,6 +54,7 @@ ABI_SYMBOLS = [
     "implisolid_last_fit_box", "implisolid_debug_bounds_ms",
     "implisolid_slice", "implisolid_slice_copy", "implisolid_slice_coords", "implisolid_slice_loops",
     "implisolid_mass", "implisolid_mass_mids", "implisolid_mass_physical",
+    "implisolid_raster", "implisolid_raster_coords",
 ]
 
 # implisolid_progress_callback (include/implisolid.h): verts, n_verts, faces, n_faces,
@@ -205,6 +206,9 @@ def lib():
                              ctypes.POINTER(ctypes.c_int64)], c_int),
         "implisolid_mass_mids": ([fp, c_int, fp], c_int),
         "implisolid_mass_physical": ([fp, c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double)], c_int),
+        "implisolid_raster": ([c_char_p, c_int, fp, c_int, c_int, c_int, fp, c_int, ctypes.POINTER(ctypes.c_uint8),
+                               ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)], c_int),
+        "implisolid_raster_coords": ([fp, c_int, c_int, c_int, fp, fp], c_int),
     }
     for name, (args, res) in sig.items():
         try:
@@ -790,6 +794,47 @@ def slice_polylines(shape, rect, resolution, z, ignore_root_matrix=False):
             lines.append((np.ascontiguousarray(pts), bool(closed[p])))
         out.append(lines)
     return out
+
+
+def raster_layers(shape, rect, width, height, z, supersample=1, ignore_root_matrix=False, return_stats=False, want_cov=True):
+    """The solid's layers z = z[l] as coverage images on the GPU: width x height pixels of rect {xmin,
+    xmax, ymin, ymax}, supersample x supersample samples per pixel (include/implisolid.h
+    implisolid_raster).  Returns (cov uint8 (L, H, W) = solid samples per pixel, 0 .. supersample^2, row 0
+    at ymin; layer_sum int64 (L,)), and with return_stats also [(layer, tile) pairs, tiles evaluated,
+    tiles filled whole, samples evaluated, chunks].  want_cov=False passes cov = NULL: cov is None and
+    only the sums (and stats) are produced."""
+    fp = ctypes.POINTER(ctypes.c_float)
+    r = _rect4(rect, "raster_layers")
+    zz = np.ascontiguousarray(z, np.float32).reshape(-1)
+    W, H, s = int(width), int(height), int(supersample)
+    if not (1 <= W <= 16384 and 1 <= H <= 16384):
+        raise ImplisolidError("raster_layers: width and height must be in [1, 16384]")
+    cov = np.empty((zz.size, H, W), np.uint8) if want_cov else None
+    sums = np.zeros(zz.size, np.int64)
+    stats = (ctypes.c_int64 * 5)()
+    rc = lib().implisolid_raster(_s(shape), int(bool(ignore_root_matrix)), r.ctypes.data_as(fp), W, H, s,
+                                 zz.ctypes.data_as(fp), int(zz.size),
+                                 cov.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)) if want_cov else None,
+                                 sums.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), stats)
+    if rc != 0:
+        raise ImplisolidError(last_error())
+    if return_stats:
+        return cov, sums, [int(v) for v in stats]
+    return cov, sums
+
+
+def raster_coords(rect, width, height, supersample):
+    """Host only: the sample tables of raster_layers, (mx float32 (width * supersample,), my float32
+    (height * supersample,))."""
+    fp = ctypes.POINTER(ctypes.c_float)
+    r = _rect4(rect, "raster_coords")
+    W, H, s = int(width), int(height), int(supersample)
+    if not (1 <= W <= 16384 and 1 <= H <= 16384) or s not in (1, 2, 4):
+        raise ImplisolidError("raster_coords: width and height must be in [1, 16384], supersample 1, 2 or 4")
+    mx, my = np.empty(W * s, np.float32), np.empty(H * s, np.float32)
+    if lib().implisolid_raster_coords(r.ctypes.data_as(fp), W, H, s, mx.ctypes.data_as(fp), my.ctypes.data_as(fp)) != 0:
+        raise ImplisolidError(last_error())
+    return mx, my
 
 
 def mass_mids(box, depth):

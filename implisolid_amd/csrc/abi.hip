@@ -1236,6 +1236,172 @@ int64_t implisolid_slice_loops(const uint32_t* keys, int64_t n_segments, int64_t
     return loops;
 }
 
+// ---- layer images of the solid (implisolid_raster) -------------------------------------------------
+// Layers go through raster.hip's passes in chunks of whole layers, at most kRasterMaxChunk (layer, tile)
+// items each: the image zeroed, classify, a read-back of the two lists' lengths (they size the grids),
+// evaluate, fill, and the pitched copy of the chunk's image into a pinned staging slot with the chunk's
+// layer sums behind it.  There are two slots: the host copies a chunk from its slot into the caller's
+// buffer while the device works on the next one.  E lends its scratch.
+namespace {
+struct RasterStage {             // the staging slots, kept until exit (grow-only)
+    PinnedVec<uint8_t> img[2];
+    PinnedVec<int64_t> sums;
+};
+RasterStage g_raster;
+
+uint32_t raster_chunk_layers(uint32_t tpl, int n_layers) {
+    uint64_t items = kRasterMaxChunk;
+    if (const char* e = std::getenv("IMPLISOLID_RASTER_CHUNK")) {   // read at each call (tests force several chunks)
+        const long long v = std::atoll(e);
+        if (v > 0) items = std::min<uint64_t>((uint64_t)v, kRasterMaxChunk);
+    }
+    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(items / tpl, 1), (uint64_t)n_layers);
+}
+
+void raster_layers(Engine& E, hipStream_t s, const Program* d_prog, int prog_depth, const float* d_tab, int W, int H, int ss,
+                   const std::vector<float>& mx, const std::vector<float>& my, const float* z, int n_layers, uint8_t* cov,
+                   int64_t* layer_sum, int64_t stats[5]) {
+    RasterGrid g;
+    g.W = W;
+    g.H = H;
+    g.s = ss;
+    g.ntx = (W + kRasterTile - 1) / kRasterTile;
+    g.nty = (H + kRasterTile - 1) / kRasterTile;
+    g.tpl = (uint32_t)g.ntx * (uint32_t)g.nty;   // <= 2^20
+    g.pitch = (uint32_t)(kRasterTile * g.ntx);
+    const uint32_t chunk_layers = raster_chunk_layers(g.tpl, n_layers);
+    const uint32_t cap = chunk_layers * g.tpl;   // items per chunk, <= kRasterMaxChunk
+    const bool prune = Engine::pruning() >= 1;
+    constexpr size_t kStateBytes = 256;
+    static_assert(sizeof(RasterState) <= kStateBytes, "the coordinates follow the state block");
+    const size_t layer_img = (size_t)H * g.pitch, layer_out = (size_t)H * (size_t)W;
+    // every reserve before any pointer is taken: a DevBuf that grows moves
+    E.scratch(10).reserve(kStateBytes + (mx.size() + my.size() + (size_t)n_layers) * sizeof(float));
+    E.scratch(11).reserve((size_t)cap * sizeof(uint32_t));                 // evaluate list
+    E.scratch(12).reserve((size_t)cap * sizeof(uint32_t));                 // fill list
+    E.scratch(13).reserve((size_t)cap * sizeof(uint64_t));                 // the listed tiles' modes
+    E.scratch(9).reserve((size_t)n_layers * sizeof(uint64_t));             // layer sums
+    if (cov) E.scratch(15).reserve((size_t)chunk_layers * layer_img);      // the chunk's image
+    RasterState* d_state = E.scratch(10).as<RasterState>();
+    float* d_mx = reinterpret_cast<float*>(E.scratch(10).as<char>() + kStateBytes);
+    float* d_my = d_mx + mx.size();
+    float* d_z = d_my + my.size();
+    uint32_t* d_list = E.scratch(11).as<uint32_t>();
+    uint32_t* d_fill = E.scratch(12).as<uint32_t>();
+    uint64_t* d_lmodes = E.scratch(13).as<uint64_t>();
+    unsigned long long* d_sums = E.scratch(9).as<unsigned long long>();
+    uint8_t* d_img = cov ? E.scratch(15).as<uint8_t>() : nullptr;
+    IMPLI_HIP(hipMemcpyAsync(d_mx, mx.data(), mx.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    IMPLI_HIP(hipMemcpyAsync(d_my, my.data(), my.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    IMPLI_HIP(hipMemcpyAsync(d_z, z, (size_t)n_layers * sizeof(float), hipMemcpyHostToDevice, s));
+    IMPLI_HIP(hipMemsetAsync(d_sums, 0, (size_t)n_layers * sizeof(uint64_t), s));
+    g_raster.sums.resize((size_t)n_layers);
+    if (cov)
+        for (int k = 0; k < (n_layers > (int)chunk_layers ? 2 : 1); ++k) g_raster.img[k].resize((size_t)chunk_layers * layer_out);
+    int64_t evaluated = 0, filled = 0, samples = 0, chunks = 0;
+    // the chunk whose image is on its way into a staging slot, not yet in cov
+    int pend_l0 = 0;
+    uint32_t pend_nl = 0;
+    auto drain = [&](int slot) {   // after a synchronisation that covers the pending copy
+        if (pend_nl) std::memcpy(cov + (size_t)pend_l0 * layer_out, g_raster.img[slot].data(), (size_t)pend_nl * layer_out);
+        pend_nl = 0;
+    };
+    for (int l0 = 0; l0 < n_layers; l0 += (int)chunk_layers, ++chunks) {
+        const uint32_t nl = (uint32_t)std::min<int64_t>(chunk_layers, n_layers - l0);
+        const uint32_t n = nl * g.tpl;
+        const int64_t first = (int64_t)l0 * g.tpl;
+        const int slot = (int)(chunks & 1);
+        IMPLI_HIP(hipMemsetAsync(d_state, 0, sizeof(RasterState), s));
+        if (cov) IMPLI_HIP(hipMemsetAsync(d_img, 0, (size_t)nl * layer_img, s));   // ordered behind the last chunk's copy
+        launch_raster_classify(d_prog, prog_depth, d_tab, E.tab_range(), d_mx, d_my, d_z, g, first, n, prune, d_list, d_lmodes,
+                               d_fill, d_state, s);
+        IMPLI_HIP(hipGetLastError());
+        RasterState h{};
+        IMPLI_HIP(hipMemcpyAsync(&h, d_state, sizeof h, hipMemcpyDeviceToHost, s));
+        IMPLI_HIP(hipStreamSynchronize(s));   // the last chunk's image has landed in the other slot as well
+        if (h.n_eval > n || h.n_fill > n || (uint64_t)h.n_eval + h.n_fill > n) throw HipError("raster: a tile list overran its chunk");
+        evaluated += h.n_eval;
+        filled += h.n_fill;
+        samples += (int64_t)h.samples;
+        launch_raster_eval(d_prog, prog_depth, d_tab, d_mx, d_my, d_z, g, first, l0, h.n_eval, d_list, d_lmodes, d_img, d_sums, s);
+        launch_raster_fill(g, first, l0, h.n_fill, d_fill, d_img, d_sums, s);
+        IMPLI_HIP(hipGetLastError());
+        if (cov) {
+            uint8_t* dst = g_raster.img[slot].data();
+            if (g.pitch == (uint32_t)W)
+                IMPLI_HIP(hipMemcpyAsync(dst, d_img, (size_t)nl * layer_out, hipMemcpyDeviceToHost, s));
+            else
+                IMPLI_HIP(hipMemcpy2DAsync(dst, (size_t)W, d_img, (size_t)g.pitch, (size_t)W, (size_t)nl * (size_t)H,
+                                           hipMemcpyDeviceToHost, s));
+        }
+        IMPLI_HIP(hipMemcpyAsync(g_raster.sums.data() + l0, d_sums + l0, (size_t)nl * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        if (cov) {
+            drain(slot ^ 1);   // the chunk before this one, while the device works on this one
+            pend_l0 = l0;
+            pend_nl = nl;
+        }
+    }
+    IMPLI_HIP(hipStreamSynchronize(s));
+    if (cov) drain((int)((chunks - 1) & 1));
+    for (int l = 0; l < n_layers; ++l) layer_sum[l] = g_raster.sums.data()[l];
+    if (stats) {
+        stats[0] = (int64_t)n_layers * g.tpl;
+        stats[1] = evaluated;
+        stats[2] = filled;
+        stats[3] = samples;
+        stats[4] = chunks;
+    }
+}
+}  // namespace
+
+int implisolid_raster(const char* shape_json, int ignore_root_matrix, const float rect[4], int width, int height, int supersample,
+                      const float* z, int n_layers, uint8_t* cov, int64_t* layer_sum, int64_t stats[5]) {
+    g_last_error.clear();
+    if (!shape_json || !rect || !z || !layer_sum) {
+        report("implisolid_raster: bad arguments", false);
+        return -1;
+    }
+    try {
+        // the request first: bad input is refused before anything is compiled or reaches the device
+        if (n_layers < 1 || n_layers > kRasterMaxLayers) throw InputError("implisolid_raster: n_layers must be in [1, 65536]");
+        for (int l = 0; l < n_layers; ++l)
+            if (!std::isfinite(z[l])) throw InputError("implisolid_raster: every z must be finite");
+        if (width < 1 || width > kRasterMaxSide || height < 1 || height > kRasterMaxSide)
+            throw InputError("implisolid_raster: width and height must be in [1, 16384]");
+        if (supersample != 1 && supersample != 2 && supersample != 4) throw InputError("implisolid_raster: supersample must be 1, 2 or 4");
+        std::vector<float> mx((size_t)width * supersample), my((size_t)height * supersample);
+        raster_coords(rect, width, height, supersample, mx.data(), my.data());
+        ObjectTables tabs;
+        const Program p = compile_mp5(shape_json, ignore_root_matrix != 0, &tabs);
+        Engine& E = engine();
+        hipStream_t s = abi_stream();
+        TableArena arena;   // the shape's own sdf_3d tables, as implisolid_bounds builds them
+        const float* d_tab = arena.set(tabs, E.d_rabbit());
+        ProbeProgram dp(p);
+        raster_layers(E, s, dp.get(), p.max_depth, d_tab, width, height, supersample, mx, my, z, n_layers, cov, layer_sum, stats);
+        return 0;
+    } catch (const InputError& e) {
+        report(e.what(), true);
+        return -1;
+    } catch (const std::exception& e) {
+        (void)hipDeviceSynchronize();
+        report(e.what(), false);
+        return -1;
+    }
+}
+
+int implisolid_raster_coords(const float rect[4], int width, int height, int supersample, float* mx, float* my) {
+    g_last_error.clear();
+    try {
+        if (!rect || !mx || !my) throw InputError("implisolid_raster_coords: bad arguments");
+        raster_coords(rect, width, height, supersample, mx, my);
+    } catch (const std::exception& e) {
+        report(e.what(), false);
+        return -1;
+    }
+    return 0;
+}
+
 // ---- mass properties of the solid (implisolid_mass) ----------------------------------------------
 // mass.hip's passes on the current device: E lends its scratch buffers (10: state block, layer counts,
 // edge and sample tables; 11-14: the two lists, as compute_bounds takes them).  The only read-back is

@@ -245,6 +245,36 @@ void slice_coords(const float rect[4], int resolution, float* xs, float* ys) {
     }
 }
 
+void raster_coords(const float rect[4], int width, int height, int supersample, float* mx, float* my) {
+    if (width < 1 || width > kRasterMaxSide) throw InputError("raster: width must be in [1, 16384]");
+    if (height < 1 || height > kRasterMaxSide) throw InputError("raster: height must be in [1, 16384]");
+    if (supersample != 1 && supersample != 2 && supersample != 4) throw InputError("raster: supersample must be 1, 2 or 4");
+    std::vector<float> edges;
+    for (int a = 0; a < 2; ++a) {
+        const float lo = rect[2 * a], hi = rect[2 * a + 1];
+        const float width_f = hi - lo;
+        if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo < hi) || !std::isfinite(width_f))
+            throw InputError("raster: the rect must be finite with min < max on both axes");
+        const int n = (a ? height : width) * supersample;   // sub-cells on the axis
+        const float step = width_f / (float)n;
+        edges.resize((size_t)n + 1);
+        for (int k = 0; k < n; ++k) {
+            const float off = (float)k * step;   // rounded on its own (-ffp-contract=off)
+            edges[k] = lo + off;
+        }
+        edges[n] = hi;
+        float* m = a ? my : mx;
+        for (int k = 0; k < n; ++k) {
+            const float w = edges[k + 1] - edges[k];
+            const float half = 0.5f * w;         // rounded on its own
+            m[k] = edges[k] + half;
+            // what puts a tile's samples inside the box of its first and last ones
+            if (!(edges[k] <= m[k] && m[k] <= edges[k + 1]))
+                throw InputError("raster: a sample point left its sub-cell (rect too narrow for float)");
+        }
+    }
+}
+
 int64_t slice_loops(const uint32_t* keys, int64_t n, int64_t* order, int64_t* loop_offsets, uint8_t* closed) {
     loop_offsets[0] = 0;
     if (n <= 0) return 0;

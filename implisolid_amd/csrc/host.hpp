@@ -68,6 +68,14 @@ bool mass_physical(const float box[6], int depth, const uint64_t moments[10], do
 constexpr int kSliceMaxResolution = 4096, kSliceMaxLayers = 65536;
 constexpr int kSliceTile = 16;   // cells per tile side: part of the ABI (it fixes the segments' order)
 void slice_coords(const float rect[4], int resolution, float* xs, float* ys);
+// The sample coordinates of a raster (implisolid_raster): width x height pixels of rect, s = supersample
+// sub-cells per pixel and axis.  The W s + 1 sub-cell edges follow slice_coords' formula with W s cells;
+// mx[k] = edge[k] + 0.5f * (edge[k + 1] - edge[k]) as mass_mids has it, my the same over H s.  mx: W s
+// floats, my: H s floats.  Throws InputError for a width or height outside [1, 16384], a supersample
+// other than 1, 2, 4, a rect that is not finite with min < max, or a sample outside its sub-cell.
+constexpr int kRasterMaxSide = 16384, kRasterMaxLayers = 65536;
+constexpr int kRasterTile = 16;   // pixels per tile side
+void raster_coords(const float rect[4], int width, int height, int supersample, float* mx, float* my);
 // Chains one layer's segments {start key, end key} into polylines by exact key matching
 // (implisolid_slice_loops): order = a permutation of the segment indices, every polyline's segments
 // consecutive; open chains first (by first segment), then closed loops, each from its lowest-indexed

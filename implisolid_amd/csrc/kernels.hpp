@@ -148,6 +148,39 @@ void launch_slice_emit(const float* d_xs, const float* d_ys, SliceGrid g, int64_
 // out[k] = d_offsets[k * tpl] for k <= n_layers: the chunk's per-layer offsets and its total
 void launch_slice_layer_offsets(const uint32_t* d_offsets, uint32_t tpl, uint32_t n_layers, uint32_t* d_out, hipStream_t s);
 
+// Layer images (implisolid_raster; DESIGN "Layer images of the solid", raster.hip): the coverage bytes
+// of the planes z[l] on a W x H-pixel grid with s x s samples per pixel (host.hpp raster_coords), in
+// tiles of kRasterTile pixels.  One chunk = `n` consecutive (layer, tile) items from global item `first`
+// (item = layer * tiles per layer + ty * ntx + tx); all launches on s, no host synchronisation inside a
+// function.  The chunk's device image holds H rows of `pitch` = 16 ntx bytes per layer, so every tile
+// row is 16 aligned bytes; the caller zeroes it (tiles outside the solid are never written).
+struct RasterGrid {
+    int W, H, s;         // pixels per axis, samples per pixel and axis
+    int ntx, nty;        // tiles per axis
+    uint32_t tpl;        // tiles per layer = ntx nty
+    uint32_t pitch;      // bytes per image row = 16 ntx
+};
+struct RasterState {     // zeroed before classify
+    uint32_t n_eval, n_fill;      // the two lists' lengths
+    unsigned long long samples;   // samples the listed tiles evaluate
+};
+constexpr uint32_t kRasterMaxChunk = 1u << 20;   // items per chunk: the image stays at or below 256 MiB
+// classify: one thread per item; prune: bound the tile's box with the interval interpreter, append
+// solid tiles to d_fill and mixed ones (with their modes words) to d_list / d_lmodes, else append
+// every tile to d_list with modes word 0.  The lists hold n entries each (chunk-local item indices,
+// in any order)
+void launch_raster_classify(const Program* d_prog, int prog_depth, const float* d_tab, float2 tab_range, const float* d_mx,
+                            const float* d_my, const float* d_z, RasterGrid g, int64_t first, uint32_t n, bool prune,
+                            uint32_t* d_list, uint64_t* d_lmodes, uint32_t* d_fill, RasterState* d_state, hipStream_t s);
+// eval: one block per listed tile, one pixel per lane; its 256 coverage bytes into d_img (not written
+// when null) and their sum onto d_sums[layer].  l0: the chunk's first layer (the image's row 0)
+void launch_raster_eval(const Program* d_prog, int prog_depth, const float* d_tab, const float* d_mx, const float* d_my,
+                        const float* d_z, RasterGrid g, int64_t first, int l0, uint32_t n_listed, const uint32_t* d_list,
+                        const uint64_t* d_lmodes, uint8_t* d_img, unsigned long long* d_sums, hipStream_t s);
+// fill: sixteen solid tiles per block; s^2 in every pixel of the tile, nx ny s^2 onto d_sums[layer]
+void launch_raster_fill(RasterGrid g, int64_t first, int l0, uint32_t n_fill, const uint32_t* d_fill, uint8_t* d_img,
+                        unsigned long long* d_sums, hipStream_t s);
+
 // the min / max pyramid of one sdf_3d table inside an object's table arena (host.hpp SdfTable: the
 // padded table at tab_off, level L at lvl_off[L]); one launch per level, in order on s
 void launch_sdf3d_pyramid(float* d_arena, uint32_t tab_off, int sx, int sy, int sz, uint32_t level0, int n_levels,

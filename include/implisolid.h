@@ -356,6 +356,45 @@ int implisolid_mass_mids(const float box[6], int depth, float* mids);
  * Returns 1, 0 with out all zero when n == 0 ("empty"), -1 (depth, box) */
 int implisolid_mass_physical(const float box[6], int depth, const uint64_t moments[10], double out[10]);
 
+/* Additive: the solid's layers as coverage images on the GPU, what a masked-resin printer exposes (no
+ * reference counterpart).
+ *   rect        {xmin, xmax, ymin, ymax}, finite with min < max
+ *   width, height  W, H in [1, 16384] pixels
+ *   supersample    s in {1, 2, 4}: sub-samples per axis per pixel
+ *   z           n_layers in [1, 65536] finite plane heights, in the caller's order (they may repeat and
+ *               need not be sorted)
+ * Sub-cell edges: ex[0 .. W s] follows implisolid_slice_coords' formula with W s cells, ex[k] = xmin +
+ * (float)k * ((xmax - xmin) / (float)(W s)) for k < W s, every operation rounded to float on its own,
+ * ex[W s] = xmax; ey the same with H s.  Samples: mx[k] = ex[k] + 0.5f * (ex[k + 1] - ex[k]), my likewise
+ * (implisolid_mass_mids' rule; implisolid_raster_coords: computed once on the host and uploaded, the
+ * kernels only index the tables; the host refuses a rect for which some ex[k] <= mx[k] <= ex[k + 1]
+ * fails).  Coverage: cov[l][py][px] = the number of (a, b) in [0, s)^2 with !(F < 0), F being
+ * implisolid_eval_points' value at (mx[px s + a], my[py s + b], z[l]): marching cubes' rule, -0.0 and
+ * NaN are solid.  It is a byte in 0 .. s^2; row py = 0 is the row at ymin (y up).  layer_sum[l] = the
+ * sum of cov[l] (n_layers entries); the layer's area is layer_sum * pixel area / s^2.  Everything is an
+ * integer: no result depends on the pruning level, the order of the tile lists or of the atomics, or
+ * the chunking.  With W = H = 2^depth and s = 1 on a box's x, y sides and z = implisolid_mass_mids' z
+ * row, layer_sum equals implisolid_mass' layer_cells.
+ *   cov      the caller's host buffer of n_layers * H * W bytes, rows tightly packed, written chunk by
+ *            chunk (there is no library-owned result slot); may be NULL: only sums and stats
+ *   stats    (may be NULL) [(layer, tile) pairs, tiles evaluated, tiles filled whole, samples
+ *            evaluated, chunks]
+ *   returns  0, or -1 with implisolid_last_error(): a bad rect, width, height, supersample, n_layers
+ *            or z, or an unsupported node; all checked before anything is launched
+ * Tiles are 16 x 16 pixels.  At implisolid_set_pruning level >= 1 each (layer, tile) is first bounded by
+ * the interval evaluator over the box of its first and last samples and {z, z}: an outside tile is
+ * left zero, a solid one (lo >= 0) is filled with s^2 without evaluating a sample, the others (a NaN
+ * bound included) evaluate their samples with the bound's modes word (bit-identical values); at
+ * level 0 every tile is evaluated.  Only the work differs.  Layers are processed in chunks of whole
+ * layers of at most IMPLISOLID_RASTER_CHUNK (layer, tile) pairs (environment, read at each call;
+ * default and maximum 2^20, at least one layer's tiles), which bounds the device image and the two
+ * pinned staging slots the chunks pass through.  One device, the interpreter kernels. */
+int implisolid_raster(const char* shape_json, int ignore_root_matrix, const float rect[4], int width, int height,
+                      int supersample, const float* z, int n_layers, uint8_t* cov, int64_t* layer_sum, int64_t stats[5]);
+/* host only (no GPU): the sample tables, mx = W s floats, my = H s floats.  0, or -1 (width, height,
+ * supersample, rect, or a sample that left its sub-cell) */
+int implisolid_raster_coords(const float rect[4], int width, int height, int supersample, float* mx, float* my);
+
 /* host-only: compile an MP5 tree to the node program; info = {n_instr, depth, n_mats, 0};
    mats_out receives n_mats inverse matrices (12 floats each, up to 256) */
 /* Additive, host only (no GPU): generate and hipRTC-compile the tree kernel for this shape.
