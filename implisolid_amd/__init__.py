@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "implisolid_parse_settings", "implisolid_slab_partition", "implisolid_slab_brick_stats",
     "implisolid_slab_set_timing", "implisolid_slab_kernel_times", "implisolid_jit_compile",
     "implisolid_slab_used_jit", "implisolid_set_jit", "implisolid_slab_stats", "implisolid_slab_read_signs",
+    "implisolid_slab_read_fill",
     "implisolid_srand", "implisolid_rand", "implisolid_rand_skip",
     "implisolid_batch_create", "implisolid_batch_run", "implisolid_batch_info", "implisolid_batch_counts",
     "implisolid_batch_download", "implisolid_batch_destroy",
@@ -152,6 +153,7 @@ def lib():
         "implisolid_slab_used_jit": ([c_void_p], c_int),
         "implisolid_slab_stats": ([c_void_p, ctypes.POINTER(ctypes.c_int64)], c_int),
         "implisolid_slab_read_signs": ([c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int64], ctypes.c_int64),
+        "implisolid_slab_read_fill": ([c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int64, ip], ctypes.c_int64),
         "implisolid_set_jit": ([c_int], None),
         "implisolid_jit_compile": ([c_char_p, ctypes.c_char_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_double)],
                                    ctypes.c_int64),
@@ -1100,6 +1102,18 @@ class Slab:
         out = (ctypes.c_int64 * 3)()
         self._rc(lib().implisolid_slab_brick_stats(self.h, out))
         return [int(x) for x in out]
+
+    def read_fill(self):
+        """Blocking host copy of the per-brick fill bytes of the last eval, shape (nbz, nby, nbx):
+        class (bits 0-1) | 0x08 candidate | fill class << 4 | 0x80 claimed."""
+        L = lib()
+        dims = (ctypes.c_int32 * 3)()
+        n = L.implisolid_slab_read_fill(self.h, None, 0, dims)
+        _check()
+        out = np.empty(n, np.uint8)
+        L.implisolid_slab_read_fill(self.h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), n, dims)
+        _check()
+        return out.reshape(int(dims[2]), int(dims[1]), int(dims[0]))
 
     def read_signs(self):
         """Blocking host copy of the sample signs (1 where value < 0), shape (layers, n, n)."""

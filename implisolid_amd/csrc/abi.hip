@@ -1939,6 +1939,22 @@ int implisolid_slab_brick_stats(implisolid_slab* s, int64_t out[3]) {
     return 0;
 }
 
+int64_t implisolid_slab_read_fill(implisolid_slab* s, uint8_t* out, int64_t capacity, int32_t dims[3]) {
+    try {
+        const BrickGrid bg = brick_grid(s->engine.grid());
+        if (dims) { dims[0] = bg.nbx; dims[1] = bg.nby; dims[2] = bg.nbz; }
+        if (out) {
+            if (capacity < bg.n_bricks) throw InputError("implisolid_slab_read_fill: buffer too small");
+            IMPLI_HIP(hipDeviceSynchronize());
+            if (bg.n_bricks) IMPLI_HIP(hipMemcpy(out, s->engine.d_fill(), (size_t)bg.n_bricks, hipMemcpyDeviceToHost));
+        }
+        return bg.n_bricks;
+    } catch (const std::exception& e) {
+        report(e.what(), false);
+        return -1;
+    }
+}
+
 int64_t implisolid_slab_read_field(implisolid_slab* s, float* out, int64_t capacity) {
     try {
         const GridDesc& g = s->engine.grid();

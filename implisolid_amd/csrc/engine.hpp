@@ -192,6 +192,7 @@ public:
     int32_t* d_faces() const { return faces_.as<int32_t>(); }
     float* d_field() const { return field_.as<float>(); }
     const uint64_t* d_signs() const { return signs_.as<uint64_t>(); }
+    const uint8_t* d_fill() const { return fill_.as<uint8_t>(); }   // grid.hpp: fill[b] of the last eval
     const uint32_t* d_counters() const { return counters_.as<uint32_t>(); }
     int depth() const { return depth_; }
     // the most values the object's postfix program holds at once (the value stacks' depth)

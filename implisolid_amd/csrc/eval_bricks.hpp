@@ -163,64 +163,95 @@ __device__ __forceinline__ void eval_one_brick(const Eval& ev, const GridDesc& g
 // shared face has the other sign -- a cell edge across the face changes sign there, so marching
 // cubes reads the candidate's value -- and that no other wave claimed first (atomic on the fill
 // byte).  Face samples are the lanes of the face column / row in both layers, or a whole layer.
-__device__ __forceinline__ uint32_t claim_neighbours(const GridDesc& g, const BrickGrid& bg, const ClaimCtx& cc, int b,
-                                                     const uint64_t neg[kBZ], uint64_t valid) {
-    static_assert(kBZ == 2, "face masks of two-layer bricks");
+//
+// One direction per lane: lane d < 6 owns direction d, so everything per direction is one vector
+// instruction over those lanes -- one load of the six fill bytes, one atomic for all the claims --
+// and the wave's chain after its tree code is two memory round trips: the fill bytes, then the
+// atomics together with the candidates' modes (Modes: ccls, bmodes and cmodes loaded through clamped
+// indices in the same issue group as the atomic; m_lane: lane d's candidate's modes, read by the
+// caller with lane_modes).  The other lanes run direction 0's arithmetic on the brick itself.
+struct ClaimLane {
+    int ax;         // the lane's axis and side (direction d = 2 ax + up; lanes past 5: direction 0)
+    bool up;
+    int an;         // the lane's neighbour brick, the brick itself where that is outside the grid
+    int cx, cy, cz; // its brick coordinates
+};
+// The lane's index where a claim is made, opaque to the optimiser (an empty asm: no instruction).
+// What the claim derives from it alone -- the lane's direction, its axis tests, its face masks -- is
+// invariant in the brick loop; hoisted out of it, it was kept across the tree code (nine VGPRs, six
+// SGPR pairs, two of them spilled: 18 -> 22 spilled SGPRs in the baked config-4 module).
+__device__ __forceinline__ int claim_lane_index() {
+    int lane = threadIdx.x & 63;
+    asm volatile("" : "+v"(lane));
+    return lane;
+}
+__device__ __forceinline__ ClaimLane claim_lane(const BrickGrid& bg, int b, int lane) {
     int bx, by, bz;
     brick_of(b, bg, bx, by, bz);
+    const int d = lane < 6 ? lane : 0;
+    const int ax = d >> 1;
+    const bool up = d & 1;
+    const int c = ax == 0 ? bx : ax == 1 ? by : bz;
+    const int lim = ax == 0 ? bg.nbx : ax == 1 ? bg.nby : bg.nbz;
+    const int step = ax == 0 ? 1 : ax == 1 ? bg.nbx : bg.nbx * bg.nby;
+    const int room = up ? lim - 1 - c : c;   // bricks between this one and the grid's face (selects, no branch)
+    const bool in = (lane < 6) & (room > 0);
+    const int dl = in ? (up ? 1 : -1) : 0;
+    return ClaimLane{ax, up, b + dl * step, bx + (ax == 0 ? dl : 0), by + (ax == 1 ? dl : 0), bz + (ax == 2 ? dl : 0)};
+}
+// direction d's modes out of the per-lane pair (d wave-uniform)
+__device__ __forceinline__ uint64_t lane_modes(uint64_t m_lane, int d) {
+    return ((uint64_t)__builtin_amdgcn_readlane((uint32_t)(m_lane >> 32), d) << 32) |
+           (uint64_t)__builtin_amdgcn_readlane((uint32_t)m_lane, d);
+}
+template <bool Modes>
+__device__ __forceinline__ uint32_t claim_neighbours(const GridDesc& g, const BrickGrid& bg, const ClaimCtx& cc, int b,
+                                                     const uint64_t neg[kBZ], uint64_t valid, uint64_t& m_lane) {
+    static_assert(kBZ == 2, "face masks of two-layer bricks");
+    const int lane = claim_lane_index();
+    const ClaimLane cl = claim_lane(bg, b, lane);
+    // round trip 1: the lane's neighbour's fill byte (a neighbour outside the grid reads the brick's
+    // own byte, which is never a candidate: it is listed)
+    const uint32_t fa = cc.fill[cl.an];
     const int layers = g.fz1 - g.fz0;
-    const bool has1 = bz * kBZ + 1 < layers;
+    const bool has1 = (b / (bg.nbx * bg.nby)) * kBZ + 1 < layers;
     uint64_t col0 = 0, row0 = (1ull << kBX) - 1ull;
 #pragma unroll
     for (int r = 0; r < kBY; ++r) col0 |= 1ull << (r * kBX);
-    const uint64_t colL = col0 << (kBX - 1), rowL = row0 << (kBX * (kBY - 1));
-    // the six neighbours' fill bytes, loaded together (a neighbour outside the grid reads the
-    // brick's own byte, which is never a candidate: it is listed); one memory round trip instead of
-    // one per direction
-    int an[6];
-    uint32_t fa[6];
-#pragma unroll
-    for (int d = 0; d < 6; ++d) {
-        const int ax = d >> 1, up = d & 1;
-        const int c = ax == 0 ? bx : ax == 1 ? by : bz;
-        const int lim = ax == 0 ? bg.nbx : ax == 1 ? bg.nby : bg.nbz;
-        const int step = ax == 0 ? 1 : ax == 1 ? bg.nbx : bg.nbx * bg.nby;
-        const bool in = up ? c + 1 < lim : c > 0;
-        an[d] = in ? (up ? b + step : b - step) : b;
-        fa[d] = cc.fill[an[d]];
+    // the lane's face: its samples in layer 0 and in layer 1
+    const int ax = cl.ax;
+    const bool up = cl.up;
+    const uint64_t fxy = (ax == 0 ? col0 : row0) << (up ? (ax == 0 ? kBX - 1 : kBX * (kBY - 1)) : 0);
+    const uint64_t fz = up ? 0ull : ~0ull;
+    uint64_t f0 = ax == 2 ? fz : fxy, f1 = ax == 2 ? ~fz : fxy;
+    f0 &= valid;
+    f1 = has1 ? (f1 & valid) : 0ull;
+    // a candidate neighbour with a sample of the other sign on the shared face
+    const uint64_t flip = (fa & 3u) == kBrickNeg ? ~0ull : 0ull;
+    const uint64_t differ = ((neg[0] ^ flip) & f0) | ((neg[1] ^ flip) & f1);
+    const bool want_l = lane < 6 && (fa & kBrickCandidate) && cl.an != b && differ != 0ull;
+    const uint32_t want = (uint32_t)__ballot(want_l);
+    if (!want) return 0u;   // uniform
+    // round trip 2, one issue group: every lane's candidate's modes (unconditional, selected after)
+    // and the wanted lanes' claims as one atomic instruction.  Two directions in one 32-bit word are
+    // two lanes' atomics on one address: each sets its own byte and reads its own byte's old flag.
+    uint32_t cls = 0;
+    uint64_t bm = 0, cm = 0;
+    if constexpr (Modes) {
+        const int cb = cl.cx + cl.cy * cc.cnbx + (cl.cz / kCZ) * cc.cplane;
+        cls = cc.ccls[cb];
+        bm = cc.bmodes[cl.an];
+        cm = cc.cmodes[cb];
     }
-    // the directions to claim: a candidate neighbour with a differing sample on the shared face
-    uint32_t want = 0;
-#pragma unroll
-    for (int d = 0; d < 6; ++d) {
-        const int ax = d >> 1, up = d & 1;
-        uint64_t f0, f1;
-        if (ax == 0) f0 = f1 = up ? colL : col0;
-        else if (ax == 1) f0 = f1 = up ? rowL : row0;
-        else { f0 = up ? 0ull : ~0ull; f1 = up ? ~0ull : 0ull; }
-        f0 &= valid;
-        f1 = has1 ? (f1 & valid) : 0ull;
-        const bool aneg = (fa[d] & 3u) == kBrickNeg;
-        const uint64_t differ = aneg ? ((~neg[0] & f0) | (~neg[1] & f1)) : ((neg[0] & f0) | (neg[1] & f1));
-        if ((fa[d] & kBrickCandidate) && an[d] != b && differ) want |= 1u << d;
-    }
-    want = __builtin_amdgcn_readfirstlane(want);
-    if (!want) return 0u;
-    // the claims' atomics issued together by lane 0, their results read after (first claimer wins)
-    uint32_t old[6];
-#pragma unroll
-    for (int d = 0; d < 6; ++d) {
-        old[d] = 0u;
-        if (((want >> d) & 1u) && (threadIdx.x & 63) == 0)
-            old[d] = atomicOr(reinterpret_cast<uint32_t*>(cc.fill + (an[d] & ~3)), (uint32_t)kBrickClaimed << (8 * (an[d] & 3)));
-    }
-    uint32_t claimed = 0;
-#pragma unroll
-    for (int d = 0; d < 6; ++d) {
-        const uint32_t o = __builtin_amdgcn_readfirstlane(old[d]);
-        if (((want >> d) & 1u) && !((o >> (8 * (an[d] & 3))) & kBrickClaimed)) claimed |= 1u << d;
-    }
-    return claimed;
+    const uint32_t shift = 8u * ((uint32_t)cl.an & 3u);
+    uint32_t old = 0u;
+    if (want_l) old = atomicOr(reinterpret_cast<uint32_t*>(cc.fill + (cl.an & ~3)), (uint32_t)kBrickClaimed << shift);
+    // the branch holds the atomic alone: its result is first read here, past the join (an empty asm,
+    // no instruction).  Without it the modes' select was copied into both sides of the branch, each
+    // with its own wait, and the atomic was issued only after the other side's loads had come back.
+    asm volatile("" : "+v"(old));
+    if constexpr (Modes) m_lane = cls == kBrickMixed ? bm : cm;
+    return (uint32_t)__ballot(want_l && !((old >> shift) & kBrickClaimed));   // first claimer wins
 }
 
 // a listed entry: the brick, then (mixed bricks) the candidates it claimed, with their own modes --
@@ -232,22 +263,20 @@ __device__ __forceinline__ void eval_listed(const Eval& ev, const GridDesc& g, c
     const int b = (int)(entry & ~kListCheck);
     const bool check = (entry & kListCheck) && cc.fill;
     int cur = b;
-    uint64_t mcur = m64;
+    uint64_t mcur = m64, m_lane = 0;
     uint32_t claimed = 0;
     for (bool first = true;; first = false) {
         uint64_t neg[kBZ], valid;
         eval_one_brick<Eval, Pair>(ev, g, bg, cur, mcur, field, signs, first, neg, valid);
-        if (first && check) claimed = claim_neighbours(g, bg, cc, b, neg, valid);
+        if (first && check) claimed = claim_neighbours<true>(g, bg, cc, b, neg, valid, m_lane);
         if (!claimed) break;
+        // the next claimed direction: its brick, and its modes from lane d (no loads in this loop)
         const int d = __builtin_ctz(claimed);
         claimed &= claimed - 1u;
         const int ax = d >> 1, up = d & 1;
         const int step = ax == 0 ? 1 : ax == 1 ? bg.nbx : bg.nbx * bg.nby;
         cur = up ? b + step : b - step;
-        int cx, cy, cz;
-        brick_of(cur, bg, cx, cy, cz);
-        const int cb = cx + cy * cc.cnbx + (cz / kCZ) * cc.cplane;
-        mcur = cc.ccls[cb] == kBrickMixed ? cc.bmodes[cur] : cc.cmodes[cb];
+        mcur = lane_modes(m_lane, d);
     }
 }
 
@@ -307,24 +336,20 @@ __device__ __forceinline__ void eval_listed_again(const Eval& ev, const GridDesc
     const int b = (int)(entry & ~kListCheck);
     const bool check = (entry & kListCheck) && cc.fill;
     int cur = b;
-    uint64_t mcur = m64;
+    uint64_t mcur = m64, m_lane = 0;
     uint32_t claimed = 0;
     for (bool first = true;; first = false) {
         uint64_t neg[kBZ], valid;
         cur = __builtin_amdgcn_readfirstlane(cur);
         eval_one_brick_again(ev, g, bg, cur, mcur, ptrs, first, neg, valid);
-        if (first && check) claimed = claim_neighbours(ev.again(g), bg, ev.again(cc), cur, neg, valid);
+        if (first && check) claimed = claim_neighbours<true>(ev.again(g), bg, ev.again(cc), cur, neg, valid, m_lane);
         if (!claimed) break;
-        const ClaimCtx cn = ev.again(cc);
         const int d = __builtin_ctz(claimed);
         claimed &= claimed - 1u;
         const int ax = d >> 1, up = d & 1;
         const int step = ax == 0 ? 1 : ax == 1 ? bg.nbx : bg.nbx * bg.nby;
         cur = up ? b + step : b - step;
-        int cx, cy, cz;
-        brick_of(cur, bg, cx, cy, cz);
-        const int cb = cx + cy * cn.cnbx + (cz / kCZ) * cn.cplane;
-        mcur = cn.ccls[cb] == kBrickMixed ? cn.bmodes[cur] : cn.cmodes[cb];
+        mcur = lane_modes(m_lane, d);
     }
 }
 
@@ -344,7 +369,8 @@ __device__ __forceinline__ void eval_listed_deferred(const Eval& ev, const GridD
     uint64_t neg[kBZ], valid;
     eval_one_brick<Eval, Pair>(ev, g, bg, b, m64, field, signs, true, neg, valid);
     if (!check) return;
-    const uint32_t claimed = claim_neighbours(g, bg, cc, b, neg, valid);
+    uint64_t unused;   // the second pass loads a candidate's modes itself
+    const uint32_t claimed = claim_neighbours<false>(g, bg, cc, b, neg, valid, unused);
     if (!claimed) return;   // uniform
     const int lane = threadIdx.x & 63;
     uint32_t base = 0;

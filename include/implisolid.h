@@ -508,6 +508,11 @@ int64_t implisolid_slab_read_signs(implisolid_slab* s, uint8_t* out, int64_t cap
 /* bricks of the last slab eval: out = [bricks, mixed-sign bricks, sign-filled bricks] (blocking);
  * sign-filled = no value computed (claimed neighbour candidates, which were evaluated, excluded) */
 int implisolid_slab_brick_stats(implisolid_slab* s, int64_t out[3]);
+/* the per-brick fill bytes of the last slab eval (blocking; diagnostics and tests): bits 0-1 the
+ * brick's sign class (0 mixed, 1 positive, 2 negative), bits 4-5 its fill class (0: listed and
+ * evaluated), 0x08 a claim candidate, 0x80 claimed and evaluated by a mixed neighbour's wave.
+ * dims = bricks per axis (x fastest).  Returns the brick count; out may be null. */
+int64_t implisolid_slab_read_fill(implisolid_slab* s, uint8_t* out, int64_t capacity, int32_t dims[3]);
 
 /* Object stream (BASELINE config 5): n objects polygonised with the same mc settings, each with
  * its own buffers.  create runs each object once to size its outputs, then:
