@@ -244,73 +244,118 @@ __global__ __launch_bounds__(256) void k_mc_count_s(GridDesc g, MCBuffers b) { m
 // K2b: one block per group.  Its global bases are the sums of the groups before it, read straight
 // from L2 (kScanParts x G words, all loads in flight together; nothing waits on another block), then
 // its non-empty units go to their place in the flat ordered list.  Groups without non-empty units
-// exit at once; the last group writes the totals.  (A single-block scan plus a flatten kernel took
+// write nothing; the last group writes the totals.  (A single-block scan plus a flatten kernel took
 // 7.3 + 4.5 us at 512^3; a decoupled look-back inside k_mc_count, 28 us more: its status words
 // cross the XCDs' L2s at memory latency, one round trip per 64 groups walked.)
+//
+// The head is one round trip: no address depends on a loaded value, and no load sits behind a
+// branch.  The group's own sums (row 7: its non-empty unit count) are one load by lanes 0-7 of
+// every wave; the units' entries are read at their slot whatever that count is (slots past it hold
+// stale words, masked afterwards; the arrays have a slot per unit of every group); the other groups'
+// sums go through clamped indices in steps of kScanAhead x BS groups, a uniform trip count with
+// every load of a step issued before the first is used.  A group without non-empty units runs the
+// same head and writes nothing (an exit on the count put every other load behind its wait).  The
+// wave sums are DPP scans (48 ds_bpermute round trips, one after the other, as shuffles), and each
+// lane adds the waves' partial sums of the columns it needs itself, so there is one barrier.
 constexpr int kScanBlock = 256;
 constexpr int kScanRows = kScanParts + 1;   // + the non-empty unit counts (summed for statistics)
+constexpr int kScanAhead = 4;               // 1024 groups per step of a 256-lane block: one step up to 512^3
+// the wave's sum of x, every lane active (gfx9 DPP: an inclusive scan by row_shr 1, 2, 4, 8 inside
+// rows of 16 lanes, row_bcast 15 and 31 into the rows above; lane 63 holds the total)
+__device__ __forceinline__ uint32_t wave_total_dpp(uint32_t x) {
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, false);
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, false);
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xf, 0xf, false);
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, false);
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xa, 0xf, false);
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xc, 0xf, false);
+    return (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
+}
+// p[i] through a 32-bit byte offset from the uniform p (4 i < 2^32): one address register, not two
+__device__ __forceinline__ uint32_t load_at(const uint32_t* p, uint32_t i) {
+    return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(p) + (i << 2));
+}
 template <int BS = kScanBlock>
 __device__ __forceinline__ void unit_scan_body(const GridDesc& g, const MCBuffers& b) {
-    static_assert(BS >= kGroupUnits, "a lane per unit of the group");
-    __shared__ uint32_t s_part[BS / 64][kScanRows];
-    __shared__ uint32_t s_base[kScanRows];
-    const int64_t G = blockIdx.x, ng = n_groups(g);
-    const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
-    const bool last = G == ng - 1;
-    const uint32_t nne = b.scan_blk[kScanParts * ng + G];   // non-empty units of the group
-    if (nne == 0 && !last) return;   // uniform
-    const uint4 e = b.unit_cnt[G * kGroupUnits + (t < (int)nne ? t : 0)];
-    const uint32_t pp = b.unit_part[G * kGroupUnits + (t < (int)nne ? t : 0)];
-    const uint32_t cm = b.unit_cmask[G * kGroupUnits + (t < (int)nne ? t : 0)];
+    static_assert(BS >= kGroupUnits && BS % 64 == 0, "a lane per unit of the group, whole waves");
+    static_assert(kScanRows == 8, "lanes 0-7 of a wave hold the group's own sums");
+    constexpr int W = BS / 64;
+    __shared__ uint32_t s_part[kScanRows][W];
+    // 32-bit indices (scan_blk holds 8 (ng + 1) words, the unit arrays 64 ng + 1): a scalar base and
+    // one offset register per load
+    const uint32_t G = blockIdx.x, ng = (uint32_t)n_groups(g);
+    const uint32_t t = threadIdx.x, lane = t & 63u, wid = t >> 6;
+    const bool last = G == ng - 1u;
+    const uint32_t mine = b.scan_blk[(lane & 7u) * ng + G];   // lane c < 8: the group's own sum c
+    const uint32_t slot = G * kGroupUnits + (t & (uint32_t)(kGroupUnits - 1));
+    const uint4 e = b.unit_cnt[slot];
+    const uint32_t pp = b.unit_part[slot];
+    const uint32_t cm = b.unit_cmask[slot];
     uint32_t acc[kScanRows] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-#pragma unroll 4
-    for (int64_t i = t; i < G; i += BS)
+    for (uint32_t i0 = 0; i0 < G; i0 += kScanAhead * BS) {
+        uint32_t v[kScanAhead][kScanRows];
 #pragma unroll
-        for (int c = 0; c < kScanRows; ++c) acc[c] += b.scan_blk[c * ng + i];
+        for (int q = 0; q < kScanAhead; ++q) {   // groups i0 + q BS + t; past G: group 0, dropped below
+            const uint32_t i = i0 + q * BS + t;
 #pragma unroll
-    for (int c = 0; c < kScanRows; ++c) {
-        const uint32_t s = wave_sum(acc[c]);
-        if (lane == 0) s_part[wid][c] = s;
+            for (int c = 0; c < kScanRows; ++c) v[q][c] = load_at(b.scan_blk + c * ng, i < G ? i : 0u);
+        }
+#pragma unroll
+        for (int q = 0; q < kScanAhead; ++q)
+#pragma unroll
+            for (int c = 0; c < kScanRows; ++c) acc[c] += i0 + q * BS + t < G ? v[q][c] : 0u;
     }
+    uint32_t tot[kScanRows];
+#pragma unroll
+    for (int c = 0; c < kScanRows; ++c) tot[c] = wave_total_dpp(acc[c]);
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < kScanRows; ++c) s_part[c][wid] = tot[c];
+    }
+    const uint32_t nne = (uint32_t)__builtin_amdgcn_readlane((int)mine, kScanParts);   // non-empty units of the group
     __syncthreads();
-    if (t < kScanRows) {
+    auto base = [&](int c) {   // the sum of column c over the groups before this one
         uint32_t s = 0;
 #pragma unroll
-        for (int w = 0; w < BS / 64; ++w) s += s_part[w][t];
-        s_base[t] = s;
-    }
-    __syncthreads();
-    if (t < (int)nne) {
-        const uint4 ent = make_uint4((uint32_t)(G * kGroupUnits) + e.x, s_base[0] + e.y, s_base[1] + e.z, s_base[2] + e.w);
+        for (int w = 0; w < W; ++w) s += s_part[c][w];
+        return s;
+    };
+    if (t < nne) {
+        const uint4 ent = make_uint4(G * kGroupUnits + e.x, base(0) + e.y, base(1) + e.z, base(2) + e.w);
         const uint32_t P = (pp >> 16) & 15u;
         const bool heavy = (pp >> 20) & 1u, small = (pp >> 21) & 1u;
         // heavy parts from the list's front; from its end backwards, interleaved, the light parts
         // (odd distances) and the small units by their global index (even distances: the halves of
         // pair p are the small units 2 p and 2 p + 1)
-        const uint32_t r = (heavy ? s_base[4] : small ? s_base[6] : s_base[5]) + (pp & 0xffffu);
+        const uint32_t r = base(heavy ? 4 : small ? 6 : 5) + (pp & 0xffffu);
         for (uint32_t q = 0; q < P; ++q) {
             const uint32_t at = heavy ? r + q : b.cap_parts - (small ? 2u : 1u) - 2u * (r + q);
             b.ulist[at] = ent;
             b.upart[at] = q | (P << 4) | (cm << 8);
         }
     }
-    if (last && t == 0) {
-        const uint32_t nh = s_base[4] + b.scan_blk[4 * ng + G];
-        const uint32_t ns = s_base[6] + b.scan_blk[6 * ng + G];
-        b.counters[7] = nh;                                       // heavy parts (the list's front)
-        b.counters[8] = ns;                                       // small units, two to a wave
-        // the vertex pass's wave work items: heavy parts, pairs (an odd last one half empty), light parts
-        b.counters[0] = nh + (ns + 1u) / 2u + s_base[5] + b.scan_blk[5 * ng + G];
-        b.counters[1] = s_base[3] + b.scan_blk[3 * ng + G];       // halo-owned vertices (ids below the slab's first)
-        b.counters[2] = s_base[0] + b.scan_blk[G];                // owned vertices incl. halo
-        b.counters[3] = s_base[1] + b.scan_blk[ng + G];           // triangles
-        b.counters[4] = s_base[2] + b.scan_blk[2 * ng + G];       // active cells (face records)
-        b.counters[5] = s_base[3] + b.scan_blk[3 * ng + G];       // = [1]: [2, 6) is the totals block
-                                                                  // copy_counts / read_counts take whole
-        b.counters[6] = s_base[7] + nne;                          // non-empty units (statistics)
+    if (last && t < 64u) {   // wave 0: lane c < 8 holds the total of column c
+        const uint32_t total = base((int)(lane & 7u)) + mine;
+        uint32_t T[kScanRows];
+#pragma unroll
+        for (int c = 0; c < kScanRows; ++c) T[c] = (uint32_t)__builtin_amdgcn_readlane((int)total, c);
+        if (t == 0) {
+            b.counters[7] = T[4];                              // heavy parts (the list's front)
+            b.counters[8] = T[6];                              // small units, two to a wave
+            // the vertex pass's wave work items: heavy parts, pairs (an odd last one half empty), light parts
+            b.counters[0] = T[4] + (T[6] + 1u) / 2u + T[5];
+            b.counters[1] = T[3];                              // halo-owned vertices (ids below the slab's first)
+            b.counters[2] = T[0];                              // owned vertices incl. halo
+            b.counters[3] = T[1];                              // triangles
+            b.counters[4] = T[2];                              // active cells (face records)
+            b.counters[5] = T[3];                              // = [1]: [2, 6) is the totals block
+                                                               // copy_counts / read_counts take whole
+            b.counters[6] = T[7];                              // non-empty units (statistics)
+        }
     }
 }
-__global__ __launch_bounds__(kScanBlock) void k_unit_scan(GridDesc g, MCBuffers b) { unit_scan_body<>(g, b); }
+// (eight waves per SIMD as before: the step's 32 sums in flight would take 66 registers, two over)
+__global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(8))) void k_unit_scan(GridDesc g, MCBuffers b) { unit_scan_body<>(g, b); }
 
 __global__ __launch_bounds__(64 * kVertsWaves) __attribute__((amdgpu_waves_per_eu(6))) void k_mc_cells(const CaseInfo* __restrict__ cases, GridDesc g, MCBuffers b) {
     mc_cells_body(cases, g, b);
@@ -335,16 +380,30 @@ __constant__ uint8_t c_edge_slot[12] = {1, 0, 1, 0, 1, 0, 1, 0, 2, 2, 2, 2};
 // one dependent round trip (record -> items -> triples) fewer.  Every address is formed before any
 // load is used (a load under a divergent branch waits alone); an owner the case does not use reads
 // the cell's own triple.  The 12 edges' ids go to LDS, and each triangle is one 12-byte store.
-// one active-cell record i of a slab: its triangles with the vertex ids of their corners
-__device__ __forceinline__ void face_record(const CaseInfo* s_case, uint32_t (*s_w)[256], const GridDesc& g,
-                                            const MCBuffers& b, uint32_t Voff, uint32_t i) {
+// The case facts the face pass needs, 12 bytes per case (the 8 KB CaseInfo table in LDS was a 32-byte
+// load per lane ahead of the barrier): the 15 Bourke edge ids of its triangles, 4 bits each, and
+// owners | ntri << 8.
+struct FaceCases {
+    uint64_t tri[256];
+    uint32_t ow[256];
+};
+__device__ __forceinline__ void face_case_store(FaceCases& fc, int ci, const CaseInfo& c) {
+    uint64_t tri = 0;
+#pragma unroll
+    for (int k = 0; k < 15; ++k) tri |= (uint64_t)(c.tri[k] & 15u) << (4 * k);
+    fc.tri[ci] = tri;
+    fc.ow[ci] = (uint32_t)c.owners | ((uint32_t)c.ntri << 8);
+}
+// one active-cell record r of a slab: its triangles with the vertex ids of their corners
+__device__ __forceinline__ void face_record(const FaceCases& fc, uint32_t (*s_w)[256], const GridDesc& g,
+                                            const MCBuffers& b, uint32_t Voff, const uint4 r) {
     const int t = threadIdx.x;
-    const uint4 r = b.records[i];
     const uint32_t L = r.x, ci = r.y, fbase = r.z;
-    const CaseInfo& C = s_case[ci];
-    const int ntri = C.ntri;
+    const uint32_t ow = fc.ow[ci];
+    uint64_t tri = fc.tri[ci];
+    const int ntri = (int)(ow >> 8);
     if (fbase + ntri > (uint64_t)b.cap_f) { *b.overflow = 1u; return; }
-    const uint32_t need = C.owners;
+    const uint32_t need = ow & 0xffu;
     const uint32_t m = (uint32_t)g.m, m2 = m * m;
     // owners 1..6: -x, -y, -x-y, -z, -y-z, -x-z
     const uint32_t d[6] = {1u, m, m + 1u, m2, m2 + m, m2 + 1u};
@@ -360,29 +419,43 @@ __device__ __forceinline__ void face_record(const CaseInfo* s_case, uint32_t (*s
         s_w[e][t] = sl == 0 ? q.a : sl == 1 ? q.b : q.c;
     }
     int32_t* out = b.faces + 3 * (size_t)fbase;
-    for (int k = 0; k < ntri; ++k) {
+    for (int k = 0; k < ntri; ++k, tri >>= 12) {
         IdTriple f;
-        f.a = Voff + s_w[C.tri[3 * k]][t];
-        f.b = Voff + s_w[C.tri[3 * k + 1]][t];
-        f.c = Voff + s_w[C.tri[3 * k + 2]][t];
+        f.a = Voff + s_w[(uint32_t)tri & 15u][t];
+        f.b = Voff + s_w[((uint32_t)tri >> 4) & 15u][t];
+        f.c = Voff + s_w[((uint32_t)tri >> 8) & 15u][t];
         *reinterpret_cast<IdTriple*>(out + 3 * k) = f;
     }
 }
 
+// The head: the lane's table entry, the record count and the offsets are loaded together; the
+// lane's first record (its address needs the count, not the table) is in flight across the barrier.
+// Lanes past the block's last record read its first one, and a block without records (the record
+// buffer may be empty) the table's first 16 bytes, unused (the table is a device allocation of
+// 32-byte entries, so the uint4 read is aligned and in bounds): no branch around the load, and no exit
+// ahead of the barrier, which would put the table loads behind the count's wait.
 __device__ __forceinline__ void mc_faces_body(const CaseInfo* __restrict__ cases, const GridDesc& g, const MCBuffers& b) {
-    __shared__ CaseInfo s_case[256];
+    __shared__ FaceCases s_fc;
     __shared__ uint32_t s_w[12][256];   // per lane: the vertex id of each of its cell's 12 edges
     const int t = threadIdx.x;
-    s_case[t] = cases[t];
-    __syncthreads();
+    const CaseInfo c = cases[t];
     const uint32_t n_rec = b.counters[4];
-    const uint32_t lim = n_rec < (uint64_t)b.cap_rec ? n_rec : (uint32_t)b.cap_rec;
     uint32_t Voff = b.offsets ? b.offsets[0] : 0u;
     if (b.gathered)
         for (int r = 0; r < b.rank; ++r) Voff += b.gathered[4 * r] - b.gathered[4 * r + 3];
+    const uint32_t lim = n_rec < (uint64_t)b.cap_rec ? n_rec : (uint32_t)b.cap_rec;
     const uint32_t nb = gridDim.x, lb = (blockIdx.x % 8u) * (nb / 8u) + blockIdx.x / 8u;
     const uint32_t per = (lim + nb - 1u) / nb, i_end = min(lim, (lb + 1u) * per);
-    for (uint32_t i = lb * per + t; i < i_end; i += 256) face_record(s_case, s_w, g, b, Voff, i);
+    const uint32_t first = lb * per;
+    uint32_t i = first + t;
+    uint4 r = *(first < i_end ? b.records + (i < i_end ? i : first) : reinterpret_cast<const uint4*>(cases));
+    face_case_store(s_fc, t, c);
+    __syncthreads();
+    while (i < i_end) {
+        face_record(s_fc, s_w, g, b, Voff, r);
+        i += 256;
+        if (i < i_end) r = b.records[i];
+    }
 }
 
 __global__ __launch_bounds__(256) void k_mc_faces(const CaseInfo* __restrict__ cases, GridDesc g, MCBuffers b) {
@@ -395,7 +468,7 @@ __global__ __launch_bounds__(kBatchCountLanes) void k_mc_count_b(const ObjArgs* 
     mc_count_body<kBatchCountLanes>(g, objs[blockIdx.y].mc);
 }
 template <int B>
-__global__ __launch_bounds__(B) void k_unit_scan_b(const ObjArgs* __restrict__ objs, GridDesc g) {
+__global__ __launch_bounds__(B) __attribute__((amdgpu_waves_per_eu(8))) void k_unit_scan_b(const ObjArgs* __restrict__ objs, GridDesc g) {
     unit_scan_body<B>(g, objs[blockIdx.y].mc);
 }
 // vertex pass: one flat index over every object's work items (unit parts and pairs of small units;
@@ -429,18 +502,18 @@ __global__ __launch_bounds__(256) void k_zero_pieces(const ZeroPiece* __restrict
 // face pass: one flat index over every object's records, a lane per record
 __global__ __launch_bounds__(256) void k_mc_faces_b(const CaseInfo* __restrict__ cases, const ObjArgs* __restrict__ objs,
                                                     int n, GridDesc g) {
-    __shared__ CaseInfo s_case[256];
+    __shared__ FaceCases s_fc;
     __shared__ uint32_t s_w[12][256];
     __shared__ uint32_t s_pre[kMaxBatchObjects + 4];
     const int t = threadIdx.x;
-    s_case[t] = cases[t];
+    face_case_store(s_fc, t, cases[t]);
     const uint32_t total = batch_prefix(objs, n, 4, 1u, 0xffffffffu, s_pre);   // counters[4]: active cells
     for (uint32_t gi = blockIdx.x * 256 + t; gi < total; gi += gridDim.x * 256) {
         const int k = batch_object_of(s_pre, n, gi);
         const MCBuffers& b = objs[k].mc;
         const uint32_t i = gi - s_pre[k];
         if (i >= (uint64_t)b.cap_rec) { *b.overflow = 1u; continue; }
-        face_record(s_case, s_w, g, b, b.offsets ? b.offsets[0] : 0u, i);
+        face_record(s_fc, s_w, g, b, b.offsets ? b.offsets[0] : 0u, b.records[i]);
     }
 }
 
