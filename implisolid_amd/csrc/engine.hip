@@ -233,14 +233,16 @@ Engine::Engine(hipStream_t setup, std::vector<ZeroRange>* resets) : resets_(rese
         SharedTables& t = g_tables[dev];
         if (!t.rabbit) {
             const std::vector<float>& all = rabbit_host_table();
-            CaseInfo cases[256];
-            build_case_table(cases);
+            struct { CaseInfo info[256]; uint32_t words[256]; } cases;   // mc_types.hpp kCaseTableBytes
+            static_assert(sizeof cases == kCaseTableBytes, "the case words follow the table");
+            build_case_table(cases.info);
+            build_case_words(cases.info, cases.words);
             void* r = nullptr;
             void* c = nullptr;
             IMPLI_HIP(hipMalloc(&r, all.size() * sizeof(float)));
             IMPLI_HIP(hipMalloc(&c, sizeof cases));
             IMPLI_HIP(hipMemcpy(r, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice));
-            IMPLI_HIP(hipMemcpy(c, cases, sizeof cases, hipMemcpyHostToDevice));
+            IMPLI_HIP(hipMemcpy(c, &cases, sizeof cases, hipMemcpyHostToDevice));
             t.rabbit = r;
             t.rabbit_bytes = all.size() * sizeof(float);
             t.cases = c;
@@ -249,7 +251,7 @@ Engine::Engine(hipStream_t setup, std::vector<ZeroRange>* resets) : resets_(rese
         shared_rabbit_ = t.rabbit;
         shared_rabbit_bytes_ = t.rabbit_bytes;
         rabbit_.attach(t.rabbit, t.rabbit_bytes);
-        cases_.attach(t.cases, sizeof(CaseInfo) * 256);
+        cases_.attach(t.cases, kCaseTableBytes);
         tab_range_ = g_tab_range;
     }
     prog_.reserve(sizeof(Program));

@@ -13,6 +13,8 @@ namespace impli {
 GridDesc make_grid(int R, const float box[6], int cz0, int cz1, int cz_emit);
 
 void build_case_table(CaseInfo out[256]);
+// the vertex pass's word per case (mc_device.hpp case_word), stored behind the table (mc_types.hpp case_words)
+void build_case_words(const CaseInfo cases[256], uint32_t out[256]);
 
 // K1: field at the slab's stored samples
 void launch_eval_field(const Program* d_prog, int depth, const float* d_rabbit, const GridDesc& g, float* d_field,

@@ -92,6 +92,10 @@ void build_case_table(CaseInfo out[256]) {
     }
 }
 
+void build_case_words(const CaseInfo cases[256], uint32_t out[256]) {
+    for (int ci = 0; ci < 256; ++ci) out[ci] = case_word(cases[ci]);
+}
+
 namespace {
 
 __device__ __forceinline__ uint32_t wave_sum(uint32_t x) {
@@ -357,8 +361,8 @@ __device__ __forceinline__ void unit_scan_body(const GridDesc& g, const MCBuffer
 // (eight waves per SIMD as before: the step's 32 sums in flight would take 66 registers, two over)
 __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(8))) void k_unit_scan(GridDesc g, MCBuffers b) { unit_scan_body<>(g, b); }
 
-__global__ __launch_bounds__(64 * kVertsWaves) __attribute__((amdgpu_waves_per_eu(6))) void k_mc_cells(const CaseInfo* __restrict__ cases, GridDesc g, MCBuffers b) {
-    mc_cells_body(cases, g, b);
+__global__ __launch_bounds__(64 * kVertsWaves) __attribute__((amdgpu_waves_per_eu(6))) void k_mc_cells(const uint32_t* __restrict__ cwords, GridDesc g, MCBuffers b) {
+    mc_cells_body(cwords, g, b);
 }
 
 // The face grid: the XCD remap below is a permutation of the blocks only when it is a multiple of 8.
@@ -473,18 +477,19 @@ __global__ __launch_bounds__(B) __attribute__((amdgpu_waves_per_eu(8))) void k_u
 }
 // vertex pass: one flat index over every object's work items (unit parts and pairs of small units;
 // batch_device.hpp), a wave per item
-__global__ __launch_bounds__(64 * kVertsWaves) void k_mc_cells_b(const CaseInfo* __restrict__ cases,
+// (the case words as in mc_cells_body; an item's counters are one load from its object's block)
+__global__ __launch_bounds__(64 * kVertsWaves) void k_mc_cells_b(const uint32_t* __restrict__ cwords,
                                                                 const ObjArgs* __restrict__ objs, int n, GridDesc g) {
     __shared__ uint32_t s_cw[256];
     __shared__ uint64_t s_bits[kVertsWaves][9][64];
     __shared__ uint32_t s_excl[kVertsWaves][64];
     __shared__ uint32_t s_pre[kMaxBatchObjects + 4];
     const int t = threadIdx.x, wid = t >> 6;
-    for (int k = t; k < 256; k += blockDim.x) s_cw[k] = case_word(cases[k]);
+    s_cw[t] = cwords[t];   // 256 lanes, the table's 256 words
     const uint32_t total = batch_prefix(objs, n, 0, 1u, 0xffffffffu, s_pre);   // counters[0]: wave work items
     for (uint32_t e = blockIdx.x * kVertsWaves + wid; e < total; e += gridDim.x * kVertsWaves) {
         const int k = __builtin_amdgcn_readfirstlane(batch_object_of(s_pre, n, e));
-        mc_cells_item(s_cw, g, objs[k].mc, e - s_pre[k], s_bits[wid], s_excl[wid]);
+        mc_cells_item(s_cw, g, objs[k].mc, e - s_pre[k], cells_head(objs[k].mc.counters), s_bits[wid], s_excl[wid]);
     }
 }
 // every object's counter block into one array (config 5's setup reads all of them with one copy)
@@ -544,7 +549,7 @@ void launch_mc_verts(const CaseInfo* d_cases, const GridDesc& g, const MCBuffers
     const int64_t nu = n_units(g);
     if (nu > 0) {
         k_mc_cells<<<(unsigned)std::min<int64_t>((nu + kVertsWaves - 1) / kVertsWaves, kVertsMaxBlocks),
-                     64 * kVertsWaves, 0, s>>>(d_cases, g, b);
+                     64 * kVertsWaves, 0, s>>>(case_words(d_cases), g, b);
     }
 }
 
@@ -576,7 +581,7 @@ void launch_batch_mc(const ObjArgs* d_objs, int n, const CaseInfo* d_cases, cons
     if (ng <= 64) k_unit_scan_b<64><<<dim3((unsigned)ng, (unsigned)n), 64, 0, s>>>(d_objs, g);
     else k_unit_scan_b<kScanBlock><<<dim3((unsigned)ng, (unsigned)n), kScanBlock, 0, s>>>(d_objs, g);
     (void)nu;
-    k_mc_cells_b<<<kBatchCellBlocks, 64 * kVertsWaves, 0, s>>>(d_cases, d_objs, n, g);
+    k_mc_cells_b<<<kBatchCellBlocks, 64 * kVertsWaves, 0, s>>>(case_words(d_cases), d_objs, n, g);
     k_mc_faces_b<<<kBatchFaceBlocks, 256, 0, s>>>(d_cases, d_objs, n, g);
 }
 

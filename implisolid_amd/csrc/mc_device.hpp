@@ -17,6 +17,36 @@ __device__ __forceinline__ T wave_incl_scan(T x, int lane) {
     return x;
 }
 
+// The same sums in registers (gfx9 DPP, as mc.hip wave_total_dpp): row_shr 1, 2, 4, 8 scan the rows
+// of 16 lanes, row_bcast 15 adds a row's total to the row above (row mask 0xa: rows 1 and 3),
+// row_bcast 31 the lower half's total to rows 2 and 3.  A lane without a source, or in a row the
+// mask leaves out, adds the `old` operand, 0.  Integer sums, so the order of the additions does
+// not show.  Call these from wave-uniform control flow with all 64 lanes active: a shuffle read an
+// inactive lane's stale register, a DPP read of an inactive lane is not defined that way.
+#define IMPLI_DPP_ADD(x, ctrl, rows) \
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, ctrl, rows, 0xf, false)
+// every lane's inclusive prefix over the wave
+__device__ __forceinline__ uint32_t wave_incl_scan_dpp(uint32_t x) {
+    IMPLI_DPP_ADD(x, 0x111, 0xf);
+    IMPLI_DPP_ADD(x, 0x112, 0xf);
+    IMPLI_DPP_ADD(x, 0x114, 0xf);
+    IMPLI_DPP_ADD(x, 0x118, 0xf);
+    IMPLI_DPP_ADD(x, 0x142, 0xa);
+    IMPLI_DPP_ADD(x, 0x143, 0xc);
+    return x;
+}
+// ... over the lane's half-wave (lanes 0-31, 32-63): without the row_bcast 31 step nothing crosses
+// from lane 31 to lane 32
+__device__ __forceinline__ uint32_t half_incl_scan_dpp(uint32_t x) {
+    IMPLI_DPP_ADD(x, 0x111, 0xf);
+    IMPLI_DPP_ADD(x, 0x112, 0xf);
+    IMPLI_DPP_ADD(x, 0x114, 0xf);
+    IMPLI_DPP_ADD(x, 0x118, 0xf);
+    IMPLI_DPP_ADD(x, 0x142, 0xa);
+    return x;
+}
+#undef IMPLI_DPP_ADD
+
 // three owned-edge vertex ids, one 12-byte access
 struct __attribute__((packed, aligned(4))) IdTriple { uint32_t a, b, c; };
 
@@ -28,6 +58,10 @@ struct ChunkBits {
     int y, z, x0;   // cell row and first cell x of the chunk
 };
 
+// (kPin: the eight words are held to one point after the loads -- the vertex pass's pair path,
+// where the register of an unused high word was re-used at once, and its write made the fourth load
+// wait for the first)
+template <bool kPin = false>
 __device__ __forceinline__ void load_chunk(const GridDesc& g, const uint64_t* __restrict__ signs, int64_t row, int c,
                                            ChunkBits& k) {
     const int rw = sign_row_words(g);
@@ -46,6 +80,7 @@ __device__ __forceinline__ void load_chunk(const GridDesc& g, const uint64_t* __
         w[q] = signs[rows[q] + c];
         nx[q] = signs[rows[q] + c + 1];
     }
+    if (kPin) asm volatile("" : : "v"(w[0]), "v"(nx[0]), "v"(w[1]), "v"(nx[1]), "v"(w[2]), "v"(nx[2]), "v"(w[3]), "v"(nx[3]));
     // arithmetic mask, not a select: a select of a loaded value is turned back into a load under
     // a branch
     const uint64_t keep = 0ull - (uint64_t)(c + 1 < rw);
@@ -160,7 +195,7 @@ __device__ __forceinline__ int select_bit32(uint32_t x, uint32_t r) {
 // the case facts the vertex pass needs, one word per case: nown (bits 0-1), ntri (2-4), and the
 // rank of owned edge slot s + 1 (0: unused) in bits 5 + 3 s (an 8 KB CaseInfo table in LDS held
 // the cells kernel to five waves per SIMD)
-__device__ __forceinline__ uint32_t case_word(const CaseInfo& c) {
+__host__ __device__ __forceinline__ uint32_t case_word(const CaseInfo& c) {
     uint32_t w = (uint32_t)c.nown | ((uint32_t)c.ntri << 2);
     for (int s = 0; s < 3; ++s) w |= (uint32_t)(c.rank[s] + 1) << (5 + 3 * s);
     return w;
@@ -185,6 +220,10 @@ __device__ __forceinline__ void cell_emit(const GridDesc& g, const MCBuffers& b,
     const float r5 = b.field[fl1 + (fy0 + fx1)];
     const float r6 = b.field[fl1 + (fy1 + fx0)];
     const float r3 = b.field[fl0 + (fy1 + fx1)];
+    // all four samples are one issue group: without the pin the load whose only use is one slot's
+    // branch below sinks into it, a round trip of its own behind the wait for the other three.
+    // Every address is inside the field: a cell's samples, or sample 0 for a lane without a cell.
+    asm volatile("" : : "v"(r7), "v"(r5), "v"(r6), "v"(r3));
     const bool sx1 = sealed_xy(g, sx + 1), sy1 = sealed_xy(g, sy + 1), sz1 = sealed_z(g, sl + 1);
     const bool sx0 = sealed_xy(g, sx), sy0 = sealed_xy(g, sy), sz0 = sealed_z(g, sl);
     const float f7 = (sx1 || sy1 || sz1) ? kSealed : r7;
@@ -230,11 +269,10 @@ __device__ __forceinline__ unsigned staged_ci(const uint64_t (*bits)[64], int q,
            ((unsigned)((bits[7][q] >> j) & 1u) << 6) | ((unsigned)((bits[6][q] >> j) & 1u) << 7);
 }
 
-// at: the part's place in the flat list
+// at: the part's place in the flat list; H: the halo-owned vertices (counters[1], from the caller's head)
 __device__ __forceinline__ void mc_cells_part(const uint32_t* s_cw, const GridDesc& g, const MCBuffers& b, uint32_t at,
-                                              uint64_t (*bits)[64], uint32_t* excl) {
+                                              uint32_t H, uint64_t (*bits)[64], uint32_t* excl) {
     const int lane = threadIdx.x & 63;
-    const uint32_t H = b.counters[1];
     const int nch = (g.m + 63) / 64;
     const int64_t rows = n_rows(g);
     const int items = kUnitRows * nch;
@@ -259,8 +297,9 @@ __device__ __forceinline__ void mc_cells_part(const uint32_t* s_cw, const GridDe
                 if (irow < rows && (ic >= kChunkMaskBits || ((cmask >> ic) & 1u))) load_chunk(g, b.signs, irow, ic, k);
             }
             const uint32_t cnt = (uint32_t)__popcll((unsigned long long)k.nt);
-            const uint32_t incl = wave_incl_scan<uint32_t>(cnt, lane);
-            const uint32_t total = __shfl(incl, 63, 64);
+            // (the loop and the window loop below are wave-uniform, all 64 lanes active: DPP scans)
+            const uint32_t incl = wave_incl_scan_dpp(cnt);
+            const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
             __builtin_amdgcn_wave_barrier();   // the previous batch's LDS reads are done
             bits[0][lane] = k.s00; bits[1][lane] = k.t00; bits[2][lane] = k.s10; bits[3][lane] = k.t10;
             bits[4][lane] = k.s01; bits[5][lane] = k.t01; bits[6][lane] = k.s11; bits[7][lane] = k.t11;
@@ -289,8 +328,8 @@ __device__ __forceinline__ void mc_cells_part(const uint32_t* s_cw, const GridDe
                 const bool emit = has && z >= g.cz_emit;
                 const unsigned own = has ? c_nown : 0u, tri = emit ? c_ntri : 0u, act = (emit && c_ntri) ? 1u : 0u;
                 const unsigned p = pack3(own, tri, act);
-                const unsigned inc = wave_incl_scan<unsigned>(p, lane);
-                const unsigned pre = inc - p, tot = __shfl(inc, 63, 64);
+                const unsigned inc = wave_incl_scan_dpp(p);
+                const unsigned pre = inc - p, tot = (unsigned)__builtin_amdgcn_readlane((int)inc, 63);
                 const uint32_t vrun = vrun0 + fld(pre, 0);
                 if (mine)
                     cell_emit(g, b, H, has, emit, erow, x, z, L, ci, cw, own, act, vrun, frun0 + fld(pre, 1),
@@ -310,14 +349,13 @@ __device__ __forceinline__ void mc_cells_part(const uint32_t* s_cw, const GridDe
 // k_mc_count made sure they are at most 32).  ns: the small units; an odd last one leaves its
 // pair's second half without cells (that half reads the first half's entry).
 __device__ __forceinline__ void mc_cells_pair(const uint32_t* s_cw, const GridDesc& g, const MCBuffers& b, uint32_t p,
-                                              uint32_t ns, uint64_t (*bits)[64], uint32_t* excl) {
+                                              uint32_t ns, uint32_t H, uint64_t (*bits)[64], uint32_t* excl) {
     // (the lane index taken through an empty asm: otherwise everything derived from it here -- the
     // half-wave scans' lane masks among it -- is hoisted out of the caller's loop and kept in
     // registers across the part path, which then spills)
     int lane = threadIdx.x & 63;
     asm volatile("" : "+v"(lane));
     const int hl = lane & 31, hb = lane & 32;   // lane in its half; the half's first lane
-    const uint32_t H = b.counters[1];
     const int64_t rows = n_rows(g);
     const uint32_t k = 2u * p + (uint32_t)(lane >> 5);
     const bool live = k < ns;
@@ -334,11 +372,14 @@ __device__ __forceinline__ void mc_cells_pair(const uint32_t* s_cw, const GridDe
     const bool item = live && cmask != 0u && ir < kUnitRows && (int64_t)irow < rows;
     const int ic = select_bit32(cmask, (uint32_t)(hl - ir * nc));
     ChunkBits kb;
-    load_chunk(g, b.signs, item ? (int64_t)irow : 0, item ? ic : 0, kb);
+    load_chunk<true>(g, b.signs, item ? (int64_t)irow : 0, item ? ic : 0, kb);
     if (!item) kb.nt = 0;
     const uint32_t cnt = (uint32_t)__popcll((unsigned long long)kb.nt);
-    const uint32_t incl = wave_incl_scan<uint32_t, 32>(cnt, hl);
-    const uint32_t total = __shfl(incl, 31, 32);   // <= kPairCells: one window
+    // (the pair path has no divergent branch above this point or below it: all 64 lanes are active
+    // at both half-wave scans)
+    const uint32_t incl = half_incl_scan_dpp(cnt);
+    // the half's total (<= kPairCells: one window), from its last lane
+    const uint32_t total = (uint32_t)(hb ? __builtin_amdgcn_readlane((int)incl, 63) : __builtin_amdgcn_readlane((int)incl, 31));
     __builtin_amdgcn_wave_barrier();   // the wave's previous LDS reads are done
     bits[0][lane] = kb.s00; bits[1][lane] = kb.t00; bits[2][lane] = kb.s10; bits[3][lane] = kb.t10;
     bits[4][lane] = kb.s01; bits[5][lane] = kb.t01; bits[6][lane] = kb.s11; bits[7][lane] = kb.t11;
@@ -364,31 +405,50 @@ __device__ __forceinline__ void mc_cells_pair(const uint32_t* s_cw, const GridDe
     const bool emit = has && z >= g.cz_emit;
     const unsigned own = has ? c_nown : 0u, tri = emit ? c_ntri : 0u, act = (emit && c_ntri) ? 1u : 0u;
     const unsigned pk = pack3(own, tri, act);
-    const unsigned pre = wave_incl_scan<unsigned, 32>(pk, hl) - pk;
+    const unsigned pre = half_incl_scan_dpp(pk) - pk;
     cell_emit(g, b, H, has, emit, erow, x, z, L, ci, cw, own, act, ent.y + fld(pre, 0), ent.z + fld(pre, 1),
               ent.w + fld(pre, 2));
 }
 
-// the e-th wave work item of a slab's vertex pass: the heavy parts (the list's front), then the
-// pairs of small units, then the light parts (k_unit_scan)
-__device__ __forceinline__ void mc_cells_item(const uint32_t* s_cw, const GridDesc& g, const MCBuffers& b, uint32_t e,
-                                              uint64_t (*bits)[64], uint32_t* excl) {
-    const uint32_t nh = b.counters[7], ns = b.counters[8], np = (ns + 1u) / 2u;
-    if (e >= nh && e - nh < np) mc_cells_pair(s_cw, g, b, e - nh, ns, bits, excl);
-    else mc_cells_part(s_cw, g, b, e < nh ? e : b.cap_parts - 1u - 2u * (e - nh - np), bits, excl);
+// The counter words the vertex pass needs -- [0] wave work items, [1] halo-owned vertices, [7] heavy
+// parts, [8] small units -- by one vector load of lanes 0-8 of the calling wave (the other lanes
+// re-read word 0), taken out with readlane: one round trip with nothing ahead of it, where four
+// scalar loads sat behind an exit, the barrier and the item's first branch.  Words 0-8 lie inside
+// the block's kCounterWords words.
+struct CellsHead { uint32_t n_items, H, nh, ns; };
+static_assert(kCounterWords > 8, "the vertex pass reads counter words 0-8");
+__device__ __forceinline__ CellsHead cells_head(const uint32_t* counters) {
+    const int lane = threadIdx.x & 63;
+    const int c = (int)counters[lane < 9 ? lane : 0];
+    return CellsHead{(uint32_t)__builtin_amdgcn_readlane(c, 0), (uint32_t)__builtin_amdgcn_readlane(c, 1),
+                     (uint32_t)__builtin_amdgcn_readlane(c, 7), (uint32_t)__builtin_amdgcn_readlane(c, 8)};
 }
 
-__device__ __forceinline__ void mc_cells_body(const CaseInfo* __restrict__ cases, const GridDesc& g, const MCBuffers& b) {
+// the e-th wave work item of a slab's vertex pass: the heavy parts (the list's front), then the
+// pairs of small units, then the light parts (k_unit_scan); h: the slab's cells_head
+__device__ __forceinline__ void mc_cells_item(const uint32_t* s_cw, const GridDesc& g, const MCBuffers& b, uint32_t e,
+                                              const CellsHead& h, uint64_t (*bits)[64], uint32_t* excl) {
+    const uint32_t nh = h.nh, ns = h.ns, np = (ns + 1u) / 2u;
+    if (e >= nh && e - nh < np) mc_cells_pair(s_cw, g, b, e - nh, ns, h.H, bits, excl);
+    else mc_cells_part(s_cw, g, b, e < nh ? e : b.cap_parts - 1u - 2u * (e - nh - np), h.H, bits, excl);
+}
+
+// The head is one round trip: the counters (cells_head) and the lane's case word (cwords: the 256
+// case words behind the CaseInfo table, mc_types.hpp case_words; 256 lanes, a word each, the
+// table's own size) are issued together with no branch ahead of them.  A block whose first item is
+// past the item count runs the same head, passes the barrier with all its waves and finds its loop
+// empty (an exit on the count ahead of the table loads put them behind its wait).
+__device__ __forceinline__ void mc_cells_body(const uint32_t* __restrict__ cwords, const GridDesc& g, const MCBuffers& b) {
+    static_assert(64 * kVertsWaves == 256, "a lane per case word");
     __shared__ uint32_t s_cw[256];
     __shared__ uint64_t s_bits[kVertsWaves][9][64];   // per wave and item: the 8 corner words + nt
     __shared__ uint32_t s_excl[kVertsWaves][64];      // per wave and item: cells in the items before it
     const int t = threadIdx.x, wid = t >> 6;
-    const uint32_t n_ne = b.counters[0];              // wave work items
-    const uint32_t w0 = blockIdx.x * kVertsWaves;
-    if (w0 >= n_ne) return;                           // uniform over the block
-    for (int k = t; k < 256; k += blockDim.x) s_cw[k] = case_word(cases[k]);
+    const CellsHead h = cells_head(b.counters);
+    s_cw[t] = cwords[t];
     __syncthreads();
-    for (uint32_t e = w0 + wid; e < n_ne; e += gridDim.x * kVertsWaves) mc_cells_item(s_cw, g, b, e, s_bits[wid], s_excl[wid]);
+    for (uint32_t e = blockIdx.x * kVertsWaves + wid; e < h.n_items; e += gridDim.x * kVertsWaves)
+        mc_cells_item(s_cw, g, b, e, h, s_bits[wid], s_excl[wid]);
 }
 
 }  // namespace impli

@@ -17,6 +17,12 @@ struct CaseInfo {
     uint8_t pad2[10];
 };
 static_assert(sizeof(CaseInfo) == 32, "CaseInfo layout");
+// The device case table: the 256 CaseInfo entries, then the vertex pass's 256 case words
+// (mc_device.hpp case_word; kernels.hpp build_case_words), one allocation.
+constexpr size_t kCaseTableBytes = 256 * sizeof(CaseInfo) + 256 * sizeof(uint32_t);
+__host__ __device__ inline const uint32_t* case_words(const CaseInfo* cases) {
+    return reinterpret_cast<const uint32_t*>(cases + 256);
+}
 // MC pipeline.  Cells are numbered L = row * m + (x - 1), row = (z - cz0) * m + (y - 1); a unit is
 // kUnitRows consecutive rows (contiguous in linear order), processed by one wave.
 constexpr int kUnitRows = 4;
