@@ -56,6 +56,7 @@ ABI_SYMBOLS = [
     "implisolid_slice", "implisolid_slice_copy", "implisolid_slice_coords", "implisolid_slice_loops",
     "implisolid_mass", "implisolid_mass_mids", "implisolid_mass_physical",
     "implisolid_raster", "implisolid_raster_coords",
+    "implisolid_raycast", "implisolid_ray_params", "implisolid_debug_raycast_ms",
 ]
 
 # implisolid_progress_callback (include/implisolid.h): verts, n_verts, faces, n_faces,
@@ -211,6 +212,10 @@ def lib():
         "implisolid_raster": ([c_char_p, c_int, fp, c_int, c_int, c_int, fp, c_int, ctypes.POINTER(ctypes.c_uint8),
                                ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)], c_int),
         "implisolid_raster_coords": ([fp, c_int, c_int, c_int, fp, fp], c_int),
+        "implisolid_raycast": ([c_char_p, c_int, fp, fp, ctypes.c_int64, ctypes.c_float, ctypes.c_float, c_int, c_int, ip, fp,
+                                fp, fp, ctypes.POINTER(ctypes.c_int64)], c_int),
+        "implisolid_ray_params": ([ctypes.c_float, ctypes.c_float, c_int, fp], c_int),
+        "implisolid_debug_raycast_ms": ([c_int, ctypes.POINTER(ctypes.c_double)], c_int),
     }
     for name, (args, res) in sig.items():
         try:
@@ -837,6 +842,122 @@ def raster_coords(rect, width, height, supersample):
     if lib().implisolid_raster_coords(r.ctypes.data_as(fp), W, H, s, mx.ctypes.data_as(fp), my.ctypes.data_as(fp)) != 0:
         raise ImplisolidError(last_error())
     return mx, my
+
+
+def ray_params(t0, t1, steps):
+    """Host only: the sample parameters of raycast(), float32 (steps + 1,): ts[k] = t0 + k * ((t1 - t0) /
+    steps) in separately rounded float operations, ts[steps] = t1 (implisolid_ray_params)."""
+    fp = ctypes.POINTER(ctypes.c_float)
+    N = int(steps)
+    if not 1 <= N <= 65536:
+        raise ImplisolidError("ray_params: steps must be in [1, 65536]")
+    ts = np.empty(N + 1, np.float32)
+    if lib().implisolid_ray_params(float(np.float32(t0)), float(np.float32(t1)), N, ts.ctypes.data_as(fp)) != 0:
+        raise ImplisolidError(last_error())
+    return ts
+
+
+def _rays(origins, dirs, what):
+    o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    if o.shape != d.shape:
+        raise ImplisolidError("%s: %d origins for %d directions" % (what, o.shape[0], d.shape[0]))
+    return o, d
+
+
+def raycast(shape, origins, dirs, t0, t1, steps, bisect=16, ignore_root_matrix=False, want_normals=True, return_stats=False):
+    """Rays against the solid on the GPU (include/implisolid.h implisolid_raycast): per ray the first of
+    the steps + 1 samples ray_params(t0, t1, steps) of p(t) = origin + t * dir that is solid, refined by
+    `bisect` bisection rounds.  Returns (hit int32 (n,) = the sample's index, 0 for a ray that starts
+    inside, -1 for a miss; t float32 (n,), t1 on a miss; f float32 (n,) = the field at the returned point;
+    normals float32 (n, 3), zero rows on a miss, or None with want_normals=False), and with return_stats
+    also [segments, segments skipped, segments evaluated, rays that hit, rays that start inside, chunks].
+    ray_points(origins, dirs, t) gives the hit positions."""
+    fp = ctypes.POINTER(ctypes.c_float)
+    o, d = _rays(origins, dirs, "raycast")
+    n = o.shape[0]
+    hit = np.empty(n, np.int32)
+    t = np.empty(n, np.float32)
+    f = np.empty(n, np.float32)
+    nrm = np.empty((n, 3), np.float32) if want_normals else None
+    stats = (ctypes.c_int64 * 6)()
+    rc = lib().implisolid_raycast(_s(shape), int(bool(ignore_root_matrix)), o.ctypes.data_as(fp), d.ctypes.data_as(fp), n,
+                                  float(np.float32(t0)), float(np.float32(t1)), int(steps), int(bisect),
+                                  hit.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), t.ctypes.data_as(fp), f.ctypes.data_as(fp),
+                                  nrm.ctypes.data_as(fp) if want_normals else None, stats)
+    if rc != 0:
+        raise ImplisolidError(last_error())
+    if return_stats:
+        return hit, t, f, nrm, [int(v) for v in stats]
+    return hit, t, f, nrm
+
+
+def ray_points(origins, dirs, t):
+    """Host only: p(t) = origin + t * dir per ray, float32 (n, 3), the product and the sum rounded to
+    float32 separately as raycast() computes them (t: one parameter per ray, or a scalar)."""
+    o, d = _rays(origins, dirs, "ray_points")
+    tt = np.broadcast_to(np.asarray(t, np.float32).reshape(-1), (o.shape[0],))
+    with np.errstate(all="ignore"):
+        return np.add(o, np.multiply(tt[:, None], d, dtype=np.float32), dtype=np.float32)
+
+
+def view_rays(eye, target, up, width, height, fov_y=None, ortho_height=None):
+    """Host only: the rays of a width x height view from `eye` towards `target`, (origins, dirs) float32
+    (height * width, 3) each, row-major with row 0 at the top, through the pixel centres; computed in
+    float64 and rounded once.  fov_y (radians, the full vertical angle): a pinhole at eye, unit
+    directions.  ortho_height (the view's height in world units): parallel rays along the view
+    direction from the view plane through eye.  Exactly one of the two must be given."""
+    if (fov_y is None) == (ortho_height is None):
+        raise ValueError("view_rays: give exactly one of fov_y and ortho_height")
+    W, H = int(width), int(height)
+    if W < 1 or H < 1:
+        raise ValueError("view_rays: width and height must be at least 1")
+    e, tg, u = (np.asarray(v, np.float64).reshape(3) for v in (eye, target, up))
+    fwd = tg - e
+    right = np.cross(fwd, u)
+    if not np.linalg.norm(fwd) > 0 or not np.linalg.norm(right) > 0:
+        raise ValueError("view_rays: eye == target, or up is parallel to the view direction")
+    fwd /= np.linalg.norm(fwd)
+    right /= np.linalg.norm(right)
+    upv = np.cross(right, fwd)
+    half_h = np.tan(0.5 * float(fov_y)) if fov_y is not None else 0.5 * float(ortho_height)
+    if not (np.isfinite(half_h) and half_h > 0):
+        raise ValueError("view_rays: fov_y must be in (0, pi), ortho_height above 0")
+    half_w = half_h * W / H
+    x = (2.0 * (np.arange(W) + 0.5) / W - 1.0) * half_w
+    y = (1.0 - 2.0 * (np.arange(H) + 0.5) / H) * half_h            # row 0 is the top row
+    off = (y[:, None, None] * upv + x[None, :, None] * right).reshape(-1, 3)
+    if fov_y is not None:
+        d = fwd + off
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        o = np.broadcast_to(e, d.shape)
+    else:
+        o = e + off
+        d = np.broadcast_to(fwd, o.shape)
+    return np.ascontiguousarray(o, np.float32), np.ascontiguousarray(d, np.float32)
+
+
+def render_view(shape, eye, target, up, width, height, t0, t1, steps, bisect=16, fov_y=None, ortho_height=None,
+                ignore_root_matrix=False, return_stats=False):
+    """A depth-and-normal image of the solid without a mesh: raycast() over view_rays().  Returns (depth
+    float32 (height, width) = the hit's ray parameter, the distance along the unit direction, NaN where
+    the ray missed; normals float32 (height, width, 3); mask bool (height, width) = the ray hit), and
+    with return_stats also raycast()'s stats."""
+    o, d = view_rays(eye, target, up, width, height, fov_y=fov_y, ortho_height=ortho_height)
+    hit, t, f, nrm, stats = raycast(shape, o, d, t0, t1, steps, bisect, ignore_root_matrix, True, True)
+    H, W = int(height), int(width)
+    mask = (hit >= 0).reshape(H, W)
+    depth = np.where(mask, t.reshape(H, W), np.float32(np.nan)).astype(np.float32)
+    out = (depth, nrm.reshape(H, W, 3), mask)
+    return out + (stats,) if return_stats else out
+
+
+def raycast_kernel_ms(enable=True):
+    """Diagnostics: switch the event timing of raycast()'s kernels on or off; returns the last timed
+    call's (march ms, finish ms), -1 before any."""
+    ms = (ctypes.c_double * 2)()
+    lib().implisolid_debug_raycast_ms(int(bool(enable)), ms)
+    return float(ms[0]), float(ms[1])
 
 
 def mass_mids(box, depth):

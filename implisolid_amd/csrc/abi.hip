@@ -1402,6 +1402,163 @@ int implisolid_raster_coords(const float rect[4], int width, int height, int sup
     return 0;
 }
 
+// ---- rays against the solid (implisolid_raycast) -----------------------------------------------------
+// Rays go through raycast.hip's two passes in chunks of at most kRayMaxChunk rays: the chunk's origins
+// and directions uploaded, march, finish, and the results copied into the caller's arrays.  The work
+// figures add up on the device over the chunks and are read back once.  E lends its scratch.
+namespace {
+bool g_ray_timing = false;       // implisolid_debug_raycast_ms: HIP events around the two launches
+double g_ray_ms[2] = {-1.0, -1.0};
+
+uint32_t ray_chunk_rays() {
+    uint64_t rays = kRayMaxChunk;
+    if (const char* e = std::getenv("IMPLISOLID_RAY_CHUNK")) {   // read at each call (tests force several chunks)
+        const long long v = std::atoll(e);
+        if (v > 0) rays = std::min<uint64_t>((uint64_t)v, kRayMaxChunk);
+    }
+    return (uint32_t)rays;
+}
+
+void cast_rays(Engine& E, hipStream_t s, const Program* d_prog, int prog_depth, const float* d_tab, const std::vector<float>& ts,
+               const float* origins, const float* dirs, int64_t n, int bisect, int32_t* hit, float* t, float* f, float* normals,
+               int64_t stats[6]) {
+    const int N = (int)ts.size() - 1;
+    const uint32_t cap = (uint32_t)std::min<int64_t>(ray_chunk_rays(), n);
+    const bool prune = Engine::pruning() >= 1;
+    constexpr size_t kStateBytes = 256;
+    static_assert(sizeof(RayState) <= kStateBytes, "the sample table follows the state block");
+    // every reserve before any pointer is taken: a DevBuf that grows moves
+    E.scratch(10).reserve(kStateBytes + ts.size() * sizeof(float));
+    E.scratch(11).reserve((size_t)cap * 6 * sizeof(float));                // origins, directions
+    E.scratch(12).reserve((size_t)cap * 3 * sizeof(uint32_t));             // hit, F(ts[hit]), work
+    E.scratch(13).reserve((size_t)cap * sizeof(uint64_t));                 // the hit segments' modes
+    E.scratch(9).reserve((size_t)cap * 2 * sizeof(float));                 // t, f
+    if (normals) E.scratch(15).reserve((size_t)cap * 3 * sizeof(float));
+    RayState* d_state = E.scratch(10).as<RayState>();
+    float* d_ts = reinterpret_cast<float*>(E.scratch(10).as<char>() + kStateBytes);
+    float* d_org = E.scratch(11).as<float>();
+    float* d_dir = d_org + (size_t)cap * 3;
+    int32_t* d_hit = E.scratch(12).as<int32_t>();
+    float* d_fhit = reinterpret_cast<float*>(d_hit + cap);
+    uint32_t* d_work = reinterpret_cast<uint32_t*>(d_hit + 2 * (size_t)cap);
+    uint64_t* d_hmodes = E.scratch(13).as<uint64_t>();
+    float* d_t = E.scratch(9).as<float>();
+    float* d_f = d_t + cap;
+    float* d_n = normals ? E.scratch(15).as<float>() : nullptr;
+    IMPLI_HIP(hipMemsetAsync(d_state, 0, sizeof(RayState), s));
+    IMPLI_HIP(hipMemcpyAsync(d_ts, ts.data(), ts.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    struct Events {
+        hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+        ~Events() {
+            for (auto& x : e)
+                if (x) (void)hipEventDestroy(x);
+        }
+    } events;
+    hipEvent_t* ev = events.e;
+    if (g_ray_timing) {
+        for (auto& e : events.e) IMPLI_HIP(hipEventCreate(&e));
+        g_ray_ms[0] = g_ray_ms[1] = 0.0;
+    }
+    int64_t chunks = 0;
+    for (int64_t first = 0; first < n; first += cap, ++chunks) {
+        const uint32_t nc = (uint32_t)std::min<int64_t>(cap, n - first);
+        IMPLI_HIP(hipMemcpyAsync(d_org, origins + 3 * first, (size_t)nc * 12, hipMemcpyHostToDevice, s));
+        IMPLI_HIP(hipMemcpyAsync(d_dir, dirs + 3 * first, (size_t)nc * 12, hipMemcpyHostToDevice, s));
+        if (ev[0]) IMPLI_HIP(hipEventRecord(ev[0], s));
+        launch_ray_march(d_prog, prog_depth, d_tab, E.tab_range(), d_ts, d_org, d_dir, nc, N, prune, d_hit, d_hmodes, d_fhit,
+                         d_work, s);
+        if (ev[1]) IMPLI_HIP(hipEventRecord(ev[1], s));
+        launch_ray_finish(d_prog, prog_depth, d_tab, d_ts, d_org, d_dir, nc, N, bisect, d_hit, d_hmodes, d_fhit, d_work, d_t,
+                          d_f, d_n, d_state, s);
+        if (ev[2]) IMPLI_HIP(hipEventRecord(ev[2], s));
+        IMPLI_HIP(hipGetLastError());
+        IMPLI_HIP(hipMemcpyAsync(hit + first, d_hit, (size_t)nc * 4, hipMemcpyDeviceToHost, s));
+        IMPLI_HIP(hipMemcpyAsync(t + first, d_t, (size_t)nc * 4, hipMemcpyDeviceToHost, s));
+        IMPLI_HIP(hipMemcpyAsync(f + first, d_f, (size_t)nc * 4, hipMemcpyDeviceToHost, s));
+        if (normals) IMPLI_HIP(hipMemcpyAsync(normals + 3 * first, d_n, (size_t)nc * 12, hipMemcpyDeviceToHost, s));
+        if (ev[0]) {
+            IMPLI_HIP(hipStreamSynchronize(s));
+            float a = 0.f, b = 0.f;
+            IMPLI_HIP(hipEventElapsedTime(&a, ev[0], ev[1]));
+            IMPLI_HIP(hipEventElapsedTime(&b, ev[1], ev[2]));
+            g_ray_ms[0] += a;
+            g_ray_ms[1] += b;
+        }
+    }
+    RayState h{};
+    IMPLI_HIP(hipMemcpyAsync(&h, d_state, sizeof h, hipMemcpyDeviceToHost, s));
+    IMPLI_HIP(hipStreamSynchronize(s));
+    if (stats) {
+        stats[0] = n * (int64_t)((N + kRaySegment - 1) / kRaySegment);
+        stats[1] = (int64_t)h.skipped;
+        stats[2] = (int64_t)h.evaluated;
+        stats[3] = (int64_t)h.hits;
+        stats[4] = (int64_t)h.inside;
+        stats[5] = chunks;
+    }
+}
+}  // namespace
+
+int implisolid_raycast(const char* shape_json, int ignore_root_matrix, const float* origins, const float* dirs, int64_t n,
+                       float t0, float t1, int steps, int bisect, int32_t* hit, float* t, float* f, float* normals,
+                       int64_t stats[6]) {
+    g_last_error.clear();
+    if (!shape_json || (n > 0 && (!origins || !dirs || !hit || !t || !f))) {
+        report("implisolid_raycast: bad arguments", false);
+        return -1;
+    }
+    try {
+        // the request first: bad input is refused before anything is compiled or reaches the device
+        if (n < 0 || n > kRayMaxRays) throw InputError("implisolid_raycast: n must be in [0, 2^24]");
+        if (bisect < 0 || bisect > kRayMaxBisect) throw InputError("implisolid_raycast: bisect must be in [0, 32]");
+        if (steps < 1 || steps > kRayMaxSteps) throw InputError("implisolid_raycast: steps must be in [1, 65536]");
+        std::vector<float> ts((size_t)steps + 1);
+        ray_params(t0, t1, steps, ts.data());
+        for (int64_t i = 0; i < 3 * n; ++i)
+            if (!std::isfinite(origins[i]) || !std::isfinite(dirs[i]))
+                throw InputError("implisolid_raycast: every origin and direction must be finite");
+        ObjectTables tabs;
+        const Program p = compile_mp5(shape_json, ignore_root_matrix != 0, &tabs);
+        if (stats) std::fill(stats, stats + 6, (int64_t)0);
+        if (n == 0) return 0;
+        Engine& E = engine();
+        hipStream_t s = abi_stream();
+        TableArena arena;   // the shape's own sdf_3d tables, as implisolid_bounds builds them
+        const float* d_tab = arena.set(tabs, E.d_rabbit());
+        ProbeProgram dp(p);
+        cast_rays(E, s, dp.get(), p.max_depth, d_tab, ts, origins, dirs, n, bisect, hit, t, f, normals, stats);
+        return 0;
+    } catch (const InputError& e) {
+        report(e.what(), true);
+        return -1;
+    } catch (const std::exception& e) {
+        (void)hipDeviceSynchronize();
+        report(e.what(), false);
+        return -1;
+    }
+}
+
+int implisolid_ray_params(float t0, float t1, int steps, float* ts) {
+    g_last_error.clear();
+    try {
+        if (!ts) throw InputError("implisolid_ray_params: bad arguments");
+        ray_params(t0, t1, steps, ts);
+    } catch (const std::exception& e) {
+        report(e.what(), false);
+        return -1;
+    }
+    return 0;
+}
+
+int implisolid_debug_raycast_ms(int enable, double ms[2]) {
+    g_ray_timing = enable != 0;
+    if (ms) {
+        ms[0] = g_ray_ms[0];
+        ms[1] = g_ray_ms[1];
+    }
+    return 0;
+}
+
 // ---- mass properties of the solid (implisolid_mass) ----------------------------------------------
 // mass.hip's passes on the current device: E lends its scratch buffers (10: state block, layer counts,
 // edge and sample tables; 11-14: the two lists, as compute_bounds takes them).  The only read-back is

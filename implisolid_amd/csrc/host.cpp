@@ -275,6 +275,22 @@ void raster_coords(const float rect[4], int width, int height, int supersample, 
     }
 }
 
+void ray_params(float t0, float t1, int steps, float* ts) {
+    if (steps < 1 || steps > kRayMaxSteps) throw InputError("raycast: steps must be in [1, 65536]");
+    const float width = t1 - t0;
+    if (!std::isfinite(t0) || !std::isfinite(t1) || !(t0 < t1) || !std::isfinite(width))
+        throw InputError("raycast: the range must be finite with t0 < t1");
+    const float step = width / (float)steps;
+    for (int k = 0; k < steps; ++k) {
+        const float off = (float)k * step;   // rounded on its own (-ffp-contract=off)
+        ts[k] = t0 + off;
+    }
+    ts[steps] = t1;
+    // what puts a segment's samples between its end samples (only ts[steps - 1] > t1 can fail)
+    for (int k = 0; k < steps; ++k)
+        if (!(ts[k] <= ts[k + 1])) throw InputError("raycast: the sample parameters are not non-decreasing (range too narrow for float)");
+}
+
 int64_t slice_loops(const uint32_t* keys, int64_t n, int64_t* order, int64_t* loop_offsets, uint8_t* closed) {
     loop_offsets[0] = 0;
     if (n <= 0) return 0;

@@ -76,6 +76,15 @@ void slice_coords(const float rect[4], int resolution, float* xs, float* ys);
 constexpr int kRasterMaxSide = 16384, kRasterMaxLayers = 65536;
 constexpr int kRasterTile = 16;   // pixels per tile side
 void raster_coords(const float rect[4], int width, int height, int supersample, float* mx, float* my);
+// The sample parameters of a ray cast (implisolid_raycast): ts[k] = t0 + (float)k * ((t1 - t0) /
+// (float)steps) for k < steps, each operation rounded to float on its own, ts[steps] = t1; steps + 1
+// floats, shared by all rays.  Throws InputError for steps outside [1, 65536], a range that is not finite
+// with t0 < t1, or a table that is not non-decreasing (ts[steps - 1] > t1: what puts every sample of a
+// segment between the segment's end samples).
+constexpr int kRayMaxSteps = 65536, kRayMaxBisect = 32;
+constexpr int64_t kRayMaxRays = (int64_t)1 << 24;
+constexpr int kRaySegment = 64;   // steps per segment: the unit of the pruning and of the stats
+void ray_params(float t0, float t1, int steps, float* ts);
 // Chains one layer's segments {start key, end key} into polylines by exact key matching
 // (implisolid_slice_loops): order = a permutation of the segment indices, every polyline's segments
 // consecutive; open chains first (by first segment), then closed loops, each from its lowest-indexed

@@ -183,6 +183,30 @@ void launch_raster_eval(const Program* d_prog, int prog_depth, const float* d_ta
 void launch_raster_fill(RasterGrid g, int64_t first, int l0, uint32_t n_fill, const uint32_t* d_fill, uint8_t* d_img,
                         unsigned long long* d_sums, hipStream_t s);
 
+// Rays against the solid (implisolid_raycast; DESIGN "Rays against the solid", raycast.hip): per ray the
+// first solid sample of the table d_ts (host.hpp ray_params, N + 1 floats), the bisection inside its
+// bracket and the normal there.  One chunk = n rays (3 n floats of origins and directions each); both
+// launches on s, no host synchronisation between them.
+struct RayState {        // zeroed before the first chunk; the chunks add to it
+    unsigned long long skipped, evaluated;   // segments proved outside / evaluated, up to each ray's hit segment
+    unsigned long long hits, inside;         // rays with hit >= 0 / hit == 0
+};
+constexpr uint32_t kRayMaxChunk = 1u << 20;   // rays per chunk: 64 MiB of device scratch
+// march: one wave per ray; prune: bound every segment of kRaySegment steps with the interval
+// interpreter, skip the ones proved outside and evaluate the others with their modes words, else
+// evaluate every segment with modes word 0, up to the first solid sample.  Per ray: d_hit (its index,
+// or -1), d_hmodes (the hit segment's modes word), d_fhit (F there) and d_work (segments skipped |
+// evaluated << 16)
+void launch_ray_march(const Program* d_prog, int prog_depth, const float* d_tab, float2 tab_range, const float* d_ts,
+                      const float* d_org, const float* d_dir, uint32_t n, int N, bool prune, int32_t* d_hit,
+                      uint64_t* d_hmodes, float* d_fhit, uint32_t* d_work, hipStream_t s);
+// finish: one lane per ray; B bisection rounds for hit >= 1, the normal (launch_vertex_normals' rule;
+// d_normals nullable) for hit >= 0, d_t / d_f, and the work figures onto *d_state
+void launch_ray_finish(const Program* d_prog, int prog_depth, const float* d_tab, const float* d_ts, const float* d_org,
+                       const float* d_dir, uint32_t n, int N, int B, const int32_t* d_hit, const uint64_t* d_hmodes,
+                       const float* d_fhit, const uint32_t* d_work, float* d_t, float* d_f, float* d_normals,
+                       RayState* d_state, hipStream_t s);
+
 // the min / max pyramid of one sdf_3d table inside an object's table arena (host.hpp SdfTable: the
 // padded table at tab_off, level L at lvl_off[L]); one launch per level, in order on s
 void launch_sdf3d_pyramid(float* d_arena, uint32_t tab_off, int sx, int sy, int sz, uint32_t level0, int n_levels,

@@ -395,6 +395,60 @@ int implisolid_raster(const char* shape_json, int ignore_root_matrix, const floa
  * supersample, rect, or a sample that left its sub-cell) */
 int implisolid_raster_coords(const float rect[4], int width, int height, int supersample, float* mx, float* my);
 
+/* Additive: rays cast at the solid on the GPU -- per ray the first hit, its distance, the field value
+ * and the normal there (no reference counterpart: the reference front end ray-casts the mesh).
+ *   origins, dirs  3 n floats each, n in [0, 2^24], every float finite.  A direction need not have unit
+ *                  length; an all-zero direction is legal (every sample is then the origin)
+ *   t0, t1         finite, t0 < t1
+ *   steps          N in [1, 65536]
+ *   bisect         B in [0, 32]
+ * Sample parameters (implisolid_ray_params: computed once on the host and uploaded, the kernels only
+ * index the table): ts[k] = t0 + (float)k * ((t1 - t0) / (float)N) for k < N, every operation rounded to
+ * float on its own, ts[N] = t1; N + 1 floats shared by all rays.  The host refuses a range for which ts
+ * is not non-decreasing (only ts[N - 1] > t1 can violate it).
+ * Points: p(t) = (ox + t * dx, oy + t * dy, oz + t * dz), every operation rounded to float on its own, no
+ * fused multiply-add.  F(t) is implisolid_eval_points' value at p(t); a sample is solid iff !(F < 0):
+ * marching cubes' rule, -0.0 and NaN are solid.
+ * Per ray, with k the smallest index in 0 .. N whose sample ts[k] is solid:
+ *   no such k   hit = -1, t = t1, f = 0, normal = (0, 0, 0)
+ *   k = 0       (the ray starts inside) hit = 0, t = ts[0], f = F(ts[0]); no bisection
+ *   k >= 1      hit = k; from a = ts[k - 1], b = ts[k], fb = F(b), B rounds of m = a + 0.5f * (b - a),
+ *               fm = F(m), if !(fm < 0) then b = m, fb = fm, else a = m; then t = b, f = fb: the returned
+ *               point is always on the solid side (a round with m == a or m == b ends the rounds: every
+ *               later one would repeat it)
+ *   normal      (normals != NULL, hit >= 0) exactly implisolid_eval_normals' row at p(t) (mcc2.cpp:852-871):
+ *               -g / |g|, and -42 g where |g| <= 0.0001 or is not a number
+ *   hit, t, f   n entries each; normals 3 n floats, may be NULL
+ *   stats       (may be NULL) [segments = n * ceil(N / 64), segments proved outside and skipped,
+ *               segments evaluated -- both counted only up to and including each ray's hit segment --,
+ *               rays with hit >= 0, rays with hit == 0, chunks]
+ *   returns     0, or -1 with implisolid_last_error(): a bad n, range, steps or bisect, a non-finite origin
+ *               or direction, or an unsupported node; all checked before anything is launched.  n = 0
+ *               returns 0 without a launch.
+ * A ray is cut into segments of 64 steps; segment j spans the samples 64 j .. min(64 j + 64, N), both ends
+ * included, so a bracket [ts[k - 1], ts[k]] always lies inside one segment (the hit segment of k >= 1 is
+ * (k - 1) / 64, that of k = 0 is 0).  Rounded multiplication and addition are monotone and ts is
+ * non-decreasing, so every coordinate of every p(t) with t in the segment -- the bisection's midpoints
+ * included -- lies between the coordinates of the segment's two end points.  At implisolid_set_pruning
+ * level >= 1 the box of the two end points is bounded by the interval evaluator: hi < 0 proves every
+ * sample of the segment outside and the segment is skipped; any other bound (lo >= 0 and NaN bounds
+ * included) has the segment's samples, and a bracket found in it, evaluated with the bound's modes word
+ * (bit-identical values).  At level 0 nothing is bounded and every sample up to the hit is evaluated.
+ * Segments after the hit segment are not evaluated.  Only the work differs: no result depends on the
+ * pruning level, the chunking or the order of any atomic.  Rays are processed in chunks of at most
+ * IMPLISOLID_RAY_CHUNK rays (environment, read at each call; default and maximum 2^20, minimum 1), which
+ * bounds the device scratch.  One device, the interpreter kernels. */
+int implisolid_raycast(const char* shape_json, int ignore_root_matrix, const float* origins, const float* dirs, int64_t n,
+                       float t0, float t1, int steps, int bisect, int32_t* hit, float* t, float* f, float* normals,
+                       int64_t stats[6]);
+/* host only (no GPU): the sample parameters, steps + 1 floats.  0, or -1 (steps, the range, or a table
+ * that is not non-decreasing) */
+int implisolid_ray_params(float t0, float t1, int steps, float* ts);
+/* diagnostics: with enable != 0 the following implisolid_raycast calls time their two kernels with HIP
+ * events (a stream synchronisation per chunk); ms (may be NULL) = the last timed call's {march, finish}
+ * milliseconds summed over its chunks, -1 before any.  Returns 0 */
+int implisolid_debug_raycast_ms(int enable, double ms[2]);
+
 /* host-only: compile an MP5 tree to the node program; info = {n_instr, depth, n_mats, 0};
    mats_out receives n_mats inverse matrices (12 floats each, up to 256) */
 /* Additive, host only (no GPU): generate and hipRTC-compile the tree kernel for this shape.
