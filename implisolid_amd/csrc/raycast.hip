@@ -14,6 +14,10 @@
 //                64 j + 1 + lane, for segment 0 sample 0 on lane 0 first.  The lowest solid lane is the
 //                hit and ends the walk.  Without pruning every segment is walked with modes word 0.
 //                Per ray: hit, the hit segment's modes word, F(ts[hit]) and the work done.
+//                t * d may overflow the float range (o, d and ts are finite, p(t) need not be).  The
+//                bound speaks of finite boxes only, so a segment with an end point that is not finite is
+//                never proved outside and is walked with modes word 0; its points that are not finite
+//                take the field of the full matrix rows (ray_field), where 0 * inf = NaN is solid.
 // k_ray_finish : one lane per ray.  hit >= 1 bisects with its segment's modes word; hit >= 0 takes the
 //                normal from vertex_normal_at, the rule of launch_vertex_normals; t, f and the normal
 //                are written; the work figures of the wave's rays are summed and added with one atomic
@@ -48,6 +52,18 @@ __device__ __forceinline__ V3 ray_point(const RayAt& r, float t) {
     return V3{r.ox + ax, r.oy + ay, r.oz + az};
 }
 __device__ __forceinline__ Iv span(float a, float b) { return a < b ? Iv{a, b} : Iv{b, a}; }
+__device__ __forceinline__ bool finite3(const V3& p) { return fabsf(p.x) < INFINITY && fabsf(p.y) < INFINITY && fabsf(p.z) < INFINITY; }
+
+// F at a point of a ray under the segment's modes word.  eval_f_pruned evaluates an XF_DIAG matrix as
+// m_dd v + m_d3, the full row's value at finite points only (program.hpp XformPattern); at a point with an
+// infinite coordinate the field is eval_f's, the full rows' (implisolid_eval_points' value there), and no
+// modes word applies
+template <int D>
+__device__ __forceinline__ float ray_field(const Program* __restrict__ prog, const float* __restrict__ tab, uint64_t m,
+                                           const V3& p) {
+    if (!finite3(p)) return eval_f<D>(prog, tab, p.x, p.y, p.z);
+    return eval_f_pruned<D>(prog, tab, m, p.x, p.y, p.z);
+}
 
 // lane q's 64-bit value in every lane, as a scalar
 __device__ __forceinline__ uint64_t wave_bcast(uint64_t v, int q) {
@@ -81,7 +97,9 @@ __global__ __launch_bounds__(256) void k_ray_march(const Program* __restrict__ p
             const int k1 = min(kSeg * seg + kSeg, N);
             const V3 a = ray_point(ray, ts[kSeg * seg]), b = ray_point(ray, ts[k1]);
             const Iv iv = eval_iv<D>(prog, tab, tab_range, Box{span(a.x, b.x), span(a.y, b.y), span(a.z, b.z)}, 0ull, m);
-            outside = iv.hi < 0.f;   // a NaN bound proves nothing
+            const bool fin = finite3(a) && finite3(b);   // then every point between them is finite
+            outside = fin && iv.hi < 0.f;                // a NaN bound proves nothing
+            if (!fin) m = 0;
         }
         const uint64_t skipm = (uint64_t)__ballot(valid && outside);
         uint64_t live = (uint64_t)__ballot(valid && !outside);
@@ -99,7 +117,7 @@ __global__ __launch_bounds__(256) void k_ray_march(const Program* __restrict__ p
                 float f = -1.f;
                 if (has) {
                     const V3 p = ray_point(ray, ts[k]);
-                    f = eval_f_pruned<D>(prog, tab, mq, p.x, p.y, p.z);
+                    f = ray_field<D>(prog, tab, mq, p);
                 }
                 const uint64_t hm = (uint64_t)__ballot(has && !(f < 0.f));   // marching cubes' rule: -0.0 and NaN are solid
                 if (hm) {
@@ -158,7 +176,7 @@ __global__ __launch_bounds__(256) void k_ray_finish(const Program* __restrict__ 
                     const float mid = a + 0.5f * (t - a);
                     if (mid == a || mid == t) break;   // every later round repeats this one
                     const V3 p = ray_point(ray, mid);
-                    const float fm = eval_f_pruned<D>(prog, tab, m, p.x, p.y, p.z);
+                    const float fm = ray_field<D>(prog, tab, m, p);
                     if (!(fm < 0.f)) {
                         t = mid;
                         f = fm;

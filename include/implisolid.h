@@ -434,6 +434,10 @@ int implisolid_raster_coords(const float rect[4], int width, int height, int sup
  * sample of the segment outside and the segment is skipped; any other bound (lo >= 0 and NaN bounds
  * included) has the segment's samples, and a bracket found in it, evaluated with the bound's modes word
  * (bit-identical values).  At level 0 nothing is bounded and every sample up to the hit is evaluated.
+ * t * d may overflow: origins, directions and ts are finite, p(t) need not be, and F at a point with an
+ * infinite coordinate is still implisolid_eval_points' value (NaN, which is solid, wherever a zero matrix
+ * entry multiplies the infinity).  A segment with an end point that is not finite is never proved outside:
+ * it counts as evaluated, with modes word 0.
  * Segments after the hit segment are not evaluated.  Only the work differs: no result depends on the
  * pruning level, the chunking or the order of any atomic.  Rays are processed in chunks of at most
  * IMPLISOLID_RAY_CHUNK rays (environment, read at each call; default and maximum 2^20, minimum 1), which

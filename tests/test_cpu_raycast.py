@@ -1,6 +1,8 @@
 """Host side of the ray cast (implisolid_ray_params, view_rays, ray_points) against the restatement
-tests/np_raycast.py, and the restatement's own rule against an analytic sphere.  No GPU."""
+tests/np_raycast.py, the restatement's own rule against an analytic sphere, and the inputs of
+tests/test_gpu_raycast_edges.py.  No GPU."""
 import ctypes
+import json
 import os
 import sys
 
@@ -194,3 +196,113 @@ def test_view_rays(impli, kw):
 def test_view_rays_take_exactly_one_projection(impli, kw):
     with pytest.raises(ValueError):
         impli.view_rays(EYE, TARGET, UP, 8, 8, **kw)
+
+
+# ---- the inputs of tests/test_gpu_raycast_edges.py (tests/ray_edge_inputs.py) ---------------------------
+# What the GPU tests rely on is asserted here on the oracle's field alone, so an edit that spoils an input
+# fails without a GPU.
+import ray_edge_inputs as edges   # noqa: E402
+
+
+@pytest.mark.parametrize("N", edges.PLACED_N)
+def test_placed_rays_hit_first_on_the_chosen_samples(oracle, N):
+    case, ks = edges.placed_case(N), edges.placed_ks(N)
+    assert len(case) == len(ks) + edges.MISSES <= 32
+    assert {1, 64, 65, 4096, 4097, N - 1, N} <= set(ks.tolist()) and (N <= 8192 or {8192, 8193} <= set(ks.tolist()))
+    for B in (0, 24):
+        rh, rt, rf, _ = edges.reference(oracle, case, B, normals=False)
+        assert np.array_equal(rh[:len(ks)], ks) and (rh[len(ks):] == -1).all()
+        assert (~(rf[:len(ks)] < 0)).all() and (rt[:len(ks)] <= case.ts[ks]).all()
+    # the samples in front of the hits are outside, and the hits lie in every batch the table has
+    F = edges.sampled(oracle, case)
+    assert (F[np.arange(len(ks)), ks - 1] < 0).all()
+    assert set((edges.hit_segment(ks, N) // 64).tolist()) >= set(range(min((edges.nseg(N) + 63) // 64, 3))), "batches 0, 1 and 2"
+    assert N % 64 != 0 or N == 65536, "the last segment is partial"
+
+
+@pytest.mark.parametrize("name", edges.SEEDED_NAMES)
+def test_seeded_rays_hit_in_both_batches_and_miss(oracle, name):
+    case = edges.seeded_case(name)
+    assert len(case) == edges.SEEDED_RAYS
+    tree = oracle.mp5_to_nodes(json.dumps(case.shape), False)
+    assert oracle.eval_implicit(tree, np.array([edges.SEEDED_INSIDE[name]], f32))[0] > 0
+    rh = edges.reference(oracle, case, 24)[0]
+    print(name, "beyond 4096:", int((rh > 4096).sum()), "up to 4096:", int(((rh >= 1) & (rh <= 4096)).sum()), "misses:", int((rh < 0).sum()))
+    assert (rh > 4096).sum() >= 8 and ((rh >= 1) & (rh <= 4096)).sum() >= 8 and (rh < 0).sum() >= 8
+    assert np.array_equal(rh, edges.reference(oracle, case, 0)[0])
+
+
+def test_the_gap_rays_pass_one_sphere_and_hit_the_other(oracle):
+    case = edges.gap_case()
+    rh = edges.reference(oracle, case, 16)[0]
+    assert rh.tolist() == edges.GAP_HITS == [2460, 6270, 6315, 6479, -1, 6326]
+    assert edges.hit_segment(rh, case.N)[[0, 1, 2, 3, 5]].tolist() == [38, 97, 98, 101, 98]
+    F = edges.sampled(oracle, case)
+    # the ray at x = 0.26 passes the small sphere (z = 1: t = 2, sample 3280) at a field value of -0.082
+    near = F[edges.GAP_PASS, 2800:3800]
+    assert -0.09 < near.max() < -0.08 and near.max() == F[edges.GAP_PASS, :6000].max()
+    # the oblique ray passes it at 0.2515 from its centre (t = 2.04, sample 2940): no sample of it is solid
+    ob = F[edges.GAP_OBLIQUE, 2700:3200]
+    assert -0.0125 < ob.max() < -0.0115 and (F[edges.GAP_OBLIQUE, :6326] < 0).all()
+    # the same points with the directions halved and the range doubled: ts doubles exactly
+    same = edges.gap_case("halved")
+    assert np.array_equal(_u32(same.ts), _u32(f32(2) * case.ts))
+    T = np.broadcast_to(case.ts[None, :], (len(case), case.N + 1))
+    assert np.array_equal(_u32(np_raycast.points(case.o, case.d, T)), _u32(np_raycast.points(same.o, same.d, f32(2) * T)))
+    assert edges.reference(oracle, same, 16)[0].tolist() == edges.GAP_HITS
+    # t1 alone doubled: other samples of the same lines
+    other = edges.reference(oracle, edges.gap_case("halved_t1"), 16)[0]
+    assert (other > 4096).sum() == 4 and 1 <= other[0] <= 4096 and other[4] == -1 and other.tolist() != edges.GAP_HITS
+    # the chunked rays: hits in both batches and misses, ten rays
+    ch = edges.reference(oracle, edges.gap_chunk_case(), 16)[0]
+    assert len(ch) == 10 and ((ch >= 1) & (ch <= 4096)).sum() >= 2 and (ch > 4096).sum() >= 2 and (ch < 0).sum() >= 1
+
+
+@pytest.mark.parametrize("N", edges.OVERFLOW_N)
+@pytest.mark.parametrize("name", edges.OVERFLOW_NAMES)
+def test_the_first_overflowed_sample_is_a_nan_hit(oracle, name, N):
+    case = edges.overflow_case(name, N)
+    assert np.isfinite(case.ts).all() and np.isfinite(case.o).all() and np.isfinite(case.d).all()
+    n = len(edges.OVERFLOW_DIRS)
+    assert (case.d[:n] != 0).all() and ((case.d[:n] < 0).sum(axis=1) == 1).all()
+    assert (np.abs(np.linalg.norm(case.d[:n].astype(np.float64), axis=1) - 4) < 0.25).all()
+    over = edges.first_overflowed(case)
+    F = edges.sampled(oracle, case)
+    rh, rt, rf, rn = edges.reference(oracle, case, 24)
+    print(name, N, "hits", rh.tolist(), "first overflowed", over.tolist(), "t", rt.tolist())
+    assert (over[:n] >= 1).all() and np.array_equal(rh[:n], over[:n]), "the first solid sample is the first overflowed one"
+    assert np.isnan(F[np.arange(n), rh[:n]]).all() and np.isnan(rf[:n]).all() and np.isnan(rn[:n]).all()
+    assert (F[np.arange(n), rh[:n] - 1] < 0).all()
+    # the components overflow at different samples: at the hit only some coordinates are infinite
+    p = np_raycast.points(case.o[:n], case.d[:n], case.ts[rh[:n]])
+    assert (np.isinf(p).sum(axis=1) < 3).any() and not np.isnan(p).any()
+    # the bisection moves t between the last finite and the first overflowed point
+    assert (rt[:n] < case.ts[rh[:n]]).all() and (rt[:n] > case.ts[rh[:n] - 1]).all()
+    assert rh[n] == 0 and rf[n] > 0 and over[n] >= 1, "starts inside, and overflows later"
+    assert rh[n + 1] == -1 and over[n + 1] == -1, "a zero direction never overflows"
+    assert len(set(edges.hit_segment(rh[:n], N).tolist())) > 1 and (N < 4097 or (rh[:n] > 64).all())
+
+
+def test_rays_that_start_behind_their_origin_hit_on_both_sides_of_zero(oracle):
+    import test_gpu_raycast as tg
+    o, d = tg._case(None, oracle, "twist")[:2]
+    case = edges.behind_case(o, d)
+    assert len(case) == tg.N_RAYS and (case.ts < 0).any() and (case.ts > 0).any()
+    rh, rt, rf, _ = edges.reference(oracle, case, 24)
+    print("t < 0:", int(((rh >= 1) & (rt < 0)).sum()), "t > 0:", int(((rh >= 1) & (rt > 0)).sum()), "misses:", int((rh < 0).sum()))
+    assert ((rh >= 1) & (rt < 0)).sum() >= 8 and ((rh >= 1) & (rt > 0)).sum() >= 8 and (rh < 0).sum() >= 8
+
+
+def test_segment_boxes_hold_their_samples():
+    case = edges.gap_case()
+    boxes = edges.segment_boxes(case)
+    assert boxes.shape == (len(case), edges.nseg(case.N), 6) and boxes.dtype == np.float32
+    T = np.broadcast_to(case.ts[None, :], (len(case), case.N + 1))
+    p = np_raycast.points(case.o, case.d, T)
+    for j in (0, 1, 63, 64, edges.nseg(case.N) - 1):
+        q = p[:, 64 * j:min(64 * j + 64, case.N) + 1]
+        assert (boxes[:, j, None, 0::2] <= q).all() and (q <= boxes[:, j, None, 1::2]).all()
+        assert np.array_equal(boxes[:, j, 5], q[:, 0, 2]) and np.array_equal(boxes[:, j, 4], q[:, -1, 2]), "rays down z"
+    assert edges.expected_work(np.array([[-1, -1, 1], [-1, -1, -1]], f32), np.array([130, -1]), 130) == (5, 1)
+    with pytest.raises(AssertionError):
+        edges.expected_work(np.full((1, 3), -1, f32), np.array([70]), 130)
