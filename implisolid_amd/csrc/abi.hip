@@ -20,49 +20,42 @@
 #include "brick_modes.hpp"
 #include "jit.hpp"
 
-#include <chrono>
 #include <rocprofiler-sdk-roctx/roctx.h>
 #include "host.hpp"
 #include "ob02.hpp"
+#include "abi_common.hpp"
 
 using namespace impli;
+using namespace impli::cabi;
 
 namespace {
-
 int g_error_mode = 0;           // 0: abort like the reference, 1: report and return
 thread_local std::string g_last_error;
+}  // namespace
 
-void report(const std::string& msg, bool reference_aborts) {
+// ---- abi_common.hpp's one definitions ------------------------------------------------------------
+void cabi::report(const std::string& msg, bool reference_aborts) {
     g_last_error = msg;
     std::fprintf(stderr, "%s\n", msg.c_str());
     if (reference_aborts && g_error_mode == 0) std::abort();
 }
+std::string& cabi::last_error() { return g_last_error; }
 
-// The host mesh of the last build, in pinned memory (D2H at full PCIe rate, where pageable memory
-// goes through the driver's staging copies) that resize() does not zero (a vector zero-filled 13 MB
-// per 512^3 build before the copy overwrote it).  Grow-only; kept until exit.
-template <class T>
-struct PinnedVec {
-    T* p = nullptr;
-    size_t n = 0, cap = 0;
-    size_t size() const { return n; }
-    T* data() { return p; }
-    const T* data() const { return p; }
-    void resize(size_t m) {
-        if (m > cap) {
-            const size_t nc = std::max(m, cap + cap / 2);
-            T* q = nullptr;
-            if (hipHostMalloc((void**)&q, nc * sizeof(T), hipHostMallocDefault) != hipSuccess || !q)
-                throw HipError("host mesh: pinned allocation failed");
-            if (n) std::memcpy(q, p, n * sizeof(T));
-            if (p) (void)hipHostFree(p);
-            p = q;
-            cap = nc;
-        }
-        n = m;
-    }
-};
-struct GeometryState {               // state_t, mcc2.cpp:165-193
+Engine& cabi::engine() {
+    static std::unique_ptr<Engine> e;
+    if (!e) e.reset(new Engine());
+    return *e;
+}
+
+hipStream_t cabi::abi_stream() {
+    static hipStream_t s = nullptr;
+    if (!s) IMPLI_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    return s;
+}
+
+namespace {
+
+struct GeometryState {               // state_t, mcc2.cpp:165-193; the host mesh of the last build
     bool active = false;
     PinnedVec<float> verts;
     PinnedVec<int32_t> faces;
@@ -132,18 +125,6 @@ struct EvalService {                 // ifunction_service, mcc2.cpp:699-705
     std::vector<float> x, f, grad;
 };
 EvalService g_eval;
-
-Engine& engine() {
-    static std::unique_ptr<Engine> e;
-    if (!e) e.reset(new Engine());
-    return *e;
-}
-
-hipStream_t abi_stream() {
-    static hipStream_t s = nullptr;
-    if (!s) IMPLI_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    return s;
-}
 
 hipStream_t abi_copy_stream() {   // the vertices' device-to-host copy beside the face pass
     static hipStream_t s = nullptr;
@@ -240,91 +221,6 @@ void multi_device_mc(const Program& prog, const ObjectTables& tabs, const MCSett
             if (problems) *problems += (int64_t)bad;
         }
     }
-}
-
-// ---- bounds of the solid (implisolid_bounds, the "fit_box" settings key) ------------------------
-// The descent of eval.hip's k_bounds_level on the current device: E lends its scratch buffers (10:
-// state and edge table, 11-14: the two lists), d_prog / d_tab are the object's program and tables
-// there.  The only read-back is the state block, after the last level; a raised overflow flag voids
-// the run, the lists grow and the descent runs again.  Returns whether the solid has bounds in
-// `search` (else out = search); stats (nullable): boxes bounded, boxes skipped as inside the running
-// bounds, longest list, reruns after overflow.
-bool g_bounds_timing = false;   // implisolid_debug_bounds_ms: HIP events around the level launches
-double g_bounds_ms = -1.0;
-
-uint32_t bounds_list_capacity(int depth) {
-    // default: 8 N^2 boxes (a surface crossing the whole box lists about 6 N^2 at the last level)
-    uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(8ull << (2 * depth), 4096), 1ull << 21);
-    if (const char* e = std::getenv("IMPLISOLID_BOUNDS_LIST")) {   // read at each call (tests force the rerun path)
-        const long long v = std::atoll(e);
-        if (v > 0) cap = (uint64_t)v;
-    }
-    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(cap, 1), kBoundsMaxList);
-}
-
-bool compute_bounds(Engine& E, hipStream_t s, const Program* d_prog, int prog_depth, const float* d_tab,
-                    const float search[6], int depth, float out[6], int64_t stats[4]) {
-    const int N = 1 << depth;
-    std::vector<float> edges((size_t)3 * (N + 1));
-    bounds_edges(search, depth, edges.data());   // validates depth and box (InputError)
-    constexpr size_t kStateBytes = 256;
-    static_assert(sizeof(BoundsState) <= kStateBytes, "the edge table follows the state block");
-    DevBuf& dst = E.scratch(10);
-    dst.reserve(kStateBytes + edges.size() * sizeof(float));
-    BoundsState* d_state = dst.as<BoundsState>();
-    float* d_edges = reinterpret_cast<float*>(dst.as<char>() + kStateBytes);
-    IMPLI_HIP(hipMemcpyAsync(d_edges, edges.data(), edges.size() * sizeof(float), hipMemcpyHostToDevice, s));
-    uint32_t cap = bounds_list_capacity(depth);
-    int64_t reruns = 0;
-    BoundsState h{};
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    struct EvFree {
-        hipEvent_t* e;
-        ~EvFree() { for (int k = 0; k < 2; ++k) if (e[k]) (void)hipEventDestroy(e[k]); }
-    } ev_free{ev};
-    if (g_bounds_timing) for (auto& e : ev) IMPLI_HIP(hipEventCreate(&e));
-    for (;;) {
-        uint32_t* d_box[2];
-        uint64_t* d_modes[2];
-        for (int k = 0; k < 2; ++k) {
-            E.scratch(11 + k).reserve((size_t)cap * sizeof(uint32_t));
-            E.scratch(13 + k).reserve((size_t)cap * sizeof(uint64_t));
-            d_box[k] = E.scratch(11 + k).as<uint32_t>();
-            d_modes[k] = E.scratch(13 + k).as<uint64_t>();
-        }
-        if (ev[0]) IMPLI_HIP(hipEventRecord(ev[0], s));
-        launch_bounds_levels(d_prog, prog_depth, d_tab, E.tab_range(), d_edges, depth, d_box, d_modes, cap, d_state, s);
-        IMPLI_HIP(hipGetLastError());
-        if (ev[1]) IMPLI_HIP(hipEventRecord(ev[1], s));
-        IMPLI_HIP(hipMemcpyAsync(&h, d_state, sizeof h, hipMemcpyDeviceToHost, s));
-        IMPLI_HIP(hipStreamSynchronize(s));
-        if (!h.overflow) break;
-        if (cap >= kBoundsMaxList) throw HipError("bounds: list overflow at the largest capacity");
-        uint64_t want = 2ull * cap;   // the counts kept counting past the capacity: at least that many
-        for (int l = kBoundsMinDepth; l < depth; ++l) want = std::max<uint64_t>(want, h.count[l]);
-        cap = (uint32_t)std::min<uint64_t>(want, kBoundsMaxList);
-        ++reruns;
-    }
-    if (ev[0]) {
-        float ms = 0.f;
-        IMPLI_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        g_bounds_ms = ms;
-    }
-    const bool found = h.key[0] != 0xffffffffu;
-    for (int a = 0; a < 6; ++a) {
-        const uint32_t bits = bounds_key_bits(h.key[a]);
-        float f;
-        std::memcpy(&f, &bits, sizeof f);
-        out[a] = found ? f : search[a];
-    }
-    if (stats) {
-        stats[0] = (int64_t)h.evaluated;
-        stats[1] = (int64_t)h.skipped;
-        stats[2] = 0;
-        for (int l = kBoundsMinDepth; l < depth; ++l) stats[2] = std::max<int64_t>(stats[2], h.count[l]);
-        stats[3] = reruns;
-    }
-    return found;
 }
 
 float g_fit_box[6] = {};     // implisolid_last_fit_box: the box the last build used, if it was fitted
@@ -871,825 +767,6 @@ int implisolid_debug_cos(const double* a, int64_t n, double* out) {
         return -1;
     }
     return 0;
-}
-
-// the diagnostics below hold their own copy of the program on the device (the engine's object, if
-// any, is left alone); freed on every path
-namespace {
-struct ProbeProgram {
-    DevBuf buf;
-    explicit ProbeProgram(const Program& p) {
-        buf.reserve(sizeof(Program));
-        IMPLI_HIP(hipMemcpy(buf.p, &p, sizeof(Program), hipMemcpyHostToDevice));
-    }
-    ~ProbeProgram() { buf.release(); }
-    const Program* get() const { return buf.as<Program>(); }
-};
-}  // namespace
-
-int implisolid_debug_intervals(const char* shape_json, int ignore_root_matrix, int variant, const float* boxes,
-                               const uint64_t* modes_in, int64_t n, float* iv_out, uint64_t* modes_out) {
-    if (!shape_json || variant < 0 || variant > 2 || n < 0 || (n && (!boxes || !iv_out || !modes_out))) {
-        report("implisolid_debug_intervals: bad arguments", false);
-        return -1;
-    }
-    if (n == 0) return 0;
-    TreeJit::Slot* slot = nullptr;
-    try {
-        ObjectTables tabs;
-        const Program p = compile_mp5(shape_json, ignore_root_matrix != 0, &tabs);
-        Engine& E = engine();
-        hipStream_t s = abi_stream();
-        TableArena arena;   // the probed shape's own sdf_3d tables (the engine's rabbit section first either way)
-        const float* d_tab = arena.set(tabs, E.d_rabbit());
-        hipFunction_t fn = nullptr;
-        if (variant) {   // the shape module (1) or the object's baked module (2), compiled before the launch
-            TreeJit& J = TreeJit::instance();
-            const int mode = J.mode();
-            J.set_mode(TreeJit::kSync);
-            slot = J.request(p, TreeJit::kBricks, variant == 2, s);
-            J.set_mode(mode);
-            if (!slot || !slot->ready.load(std::memory_order_acquire) || !slot->k.debug_iv)
-                throw std::runtime_error("implisolid_debug_intervals: the tree module did not compile");
-            fn = slot->k.debug_iv;
-        }
-        ProbeProgram dp(p);
-        DevBuf& db = E.scratch(0);
-        DevBuf& dm = E.scratch(1);
-        DevBuf& dout = E.scratch(2);
-        db.reserve((size_t)n * 24);
-        dm.reserve((size_t)n * 16);   // modes_in, then modes_out
-        dout.reserve((size_t)n * 8);
-        uint64_t* d_mi = modes_in ? dm.as<uint64_t>() : nullptr;
-        uint64_t* d_mo = dm.as<uint64_t>() + n;
-        IMPLI_HIP(hipMemcpyAsync(db.p, boxes, (size_t)n * 24, hipMemcpyHostToDevice, s));
-        if (modes_in) IMPLI_HIP(hipMemcpyAsync(d_mi, modes_in, (size_t)n * 8, hipMemcpyHostToDevice, s));
-        launch_iv_probe(dp.get(), p.max_depth, d_tab, E.tab_range(), db.as<float>(), d_mi, n, dout.as<float>(), d_mo, s,
-                        fn);
-        IMPLI_HIP(hipGetLastError());
-        IMPLI_HIP(hipMemcpyAsync(iv_out, dout.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-        IMPLI_HIP(hipMemcpyAsync(modes_out, d_mo, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-        IMPLI_HIP(hipStreamSynchronize(s));
-        TreeJit::instance().release(slot);
-    } catch (const InputError& e) {
-        TreeJit::instance().release(slot);
-        report(e.what(), true);
-        return -1;
-    } catch (const std::exception& e) {
-        (void)hipDeviceSynchronize();
-        TreeJit::instance().release(slot);
-        report(e.what(), false);
-        return -1;
-    }
-    return 0;
-}
-
-int implisolid_debug_eval_modes(const char* shape_json, int ignore_root_matrix, const float* xyz, const uint64_t* modes,
-                                int64_t n, float* f_out) {
-    if (!shape_json || n < 0 || (n && (!xyz || !modes || !f_out))) {
-        report("implisolid_debug_eval_modes: bad arguments", false);
-        return -1;
-    }
-    if (n == 0) return 0;
-    try {
-        ObjectTables tabs;
-        const Program p = compile_mp5(shape_json, ignore_root_matrix != 0, &tabs);
-        Engine& E = engine();
-        hipStream_t s = abi_stream();
-        TableArena arena;
-        const float* d_tab = arena.set(tabs, E.d_rabbit());
-        ProbeProgram dp(p);
-        DevBuf& dx = E.scratch(0);
-        DevBuf& dm = E.scratch(1);
-        DevBuf& df = E.scratch(2);
-        dx.reserve((size_t)n * 12);
-        dm.reserve((size_t)n * 8);
-        df.reserve((size_t)n * 4);
-        IMPLI_HIP(hipMemcpyAsync(dx.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, s));
-        IMPLI_HIP(hipMemcpyAsync(dm.p, modes, (size_t)n * 8, hipMemcpyHostToDevice, s));
-        launch_eval_modes_probe(dp.get(), p.max_depth, d_tab, dx.as<float>(), dm.as<uint64_t>(), n, df.as<float>(), s);
-        IMPLI_HIP(hipGetLastError());
-        IMPLI_HIP(hipMemcpyAsync(f_out, df.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-        IMPLI_HIP(hipStreamSynchronize(s));
-    } catch (const InputError& e) {
-        report(e.what(), true);
-        return -1;
-    } catch (const std::exception& e) {
-        report(e.what(), false);
-        return -1;
-    }
-    return 0;
-}
-
-int implisolid_bounds(const char* shape_json, int ignore_root_matrix, const float search[6], int depth, float out[6],
-                      int64_t stats[4]) {
-    g_last_error.clear();
-    if (!shape_json || !search || !out) {
-        report("implisolid_bounds: bad arguments", false);
-        return -1;
-    }
-    try {
-        // depth and box first: bad input is refused before anything reaches the device
-        if (depth < kBoundsMinDepth || depth > kBoundsMaxDepth) throw InputError("implisolid_bounds: depth must be in [3, 10]");
-        {
-            std::vector<float> probe((size_t)3 * ((1 << depth) + 1));
-            bounds_edges(search, depth, probe.data());
-        }
-        ObjectTables tabs;
-        const Program p = compile_mp5(shape_json, ignore_root_matrix != 0, &tabs);
-        Engine& E = engine();
-        hipStream_t s = abi_stream();
-        TableArena arena;   // the shape's own sdf_3d tables, as the interval probe builds them
-        const float* d_tab = arena.set(tabs, E.d_rabbit());
-        ProbeProgram dp(p);
-        return compute_bounds(E, s, dp.get(), p.max_depth, d_tab, search, depth, out, stats) ? 1 : 0;
-    } catch (const InputError& e) {
-        report(e.what(), true);
-        return -1;
-    } catch (const std::exception& e) {
-        (void)hipDeviceSynchronize();
-        report(e.what(), false);
-        return -1;
-    }
-}
-
-double implisolid_debug_bounds_ms(int enable) {
-    g_bounds_timing = enable != 0;
-    return g_bounds_ms;
-}
-
-int implisolid_bounds_edges(const float search[6], int depth, float* edges) {
-    g_last_error.clear();
-    try {
-        if (!search || !edges) throw InputError("implisolid_bounds_edges: bad arguments");
-        bounds_edges(search, depth, edges);
-    } catch (const std::exception& e) {
-        report(e.what(), false);
-        return -1;
-    }
-    return 0;
-}
-
-int implisolid_fit_box(const float search[6], const float bounds[6], int resolution, int margin, float out[6]) {
-    g_last_error.clear();
-    if (!search || !bounds || !out || !fit_box(search, bounds, resolution, margin, out)) {
-        report("implisolid_fit_box: resolution - 2 margin must be >= 1 (margin >= 0)", false);
-        return -1;
-    }
-    return 0;
-}
-
-// ---- slices of the solid (implisolid_slice) ------------------------------------------------------
-// Layers go through slice.hip's passes in chunks of whole layers, at most kSliceMaxChunk (layer, tile)
-// items each: classify, a read-back of the list's length (it sizes the sample scratch and the march
-// and emit grids), march, scan, a read-back of the chunk's per-layer offsets and total (they size
-// the output), emit, and the copy into the host slot at the running offset.  E lends its scratch.
-namespace {
-struct SliceSlot {               // the last slice's result; n < 0: none
-    PinnedVec<float> xy;
-    PinnedVec<uint32_t> keys;
-    int64_t n = -1;
-};
-SliceSlot g_slice;
-
-uint32_t slice_chunk_layers(uint32_t tpl, int n_layers) {
-    uint64_t items = kSliceMaxChunk;
-    if (const char* e = std::getenv("IMPLISOLID_SLICE_CHUNK")) {   // read at each call (tests force several chunks)
-        const long long v = std::atoll(e);
-        if (v > 0) items = std::min<uint64_t>((uint64_t)v, kSliceMaxChunk);
-    }
-    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(items / tpl, 1), (uint64_t)n_layers);
-}
-
-int64_t slice_layers(Engine& E, hipStream_t s, const Program* d_prog, int prog_depth, const float* d_tab, int R,
-                     const std::vector<float>& xs, const std::vector<float>& ys, const float* z, int n_layers,
-                     int64_t* layer_offsets, int64_t stats[4]) {
-    SliceGrid g;
-    g.R = R;
-    g.ntx = (R + kSliceTile - 1) / kSliceTile;
-    g.tpl = (uint32_t)g.ntx * (uint32_t)g.ntx;
-    const uint32_t chunk_layers = slice_chunk_layers(g.tpl, n_layers);
-    const uint32_t cap = chunk_layers * g.tpl;   // items per chunk, <= kSliceMaxChunk (tpl <= 2^16)
-    const bool prune = Engine::pruning() >= 1;
-    constexpr size_t kStateBytes = 256;
-    static_assert(sizeof(SliceState) <= kStateBytes, "the coordinates follow the state block");
-    const size_t W = (size_t)R + 1;
-    // every reserve before any pointer is taken: a DevBuf that grows moves
-    E.scratch(10).reserve(kStateBytes + (2 * W + (size_t)n_layers) * sizeof(float));
-    E.scratch(11).reserve((size_t)cap * sizeof(uint32_t));                        // list
-    E.scratch(12).reserve((size_t)cap * sizeof(uint32_t));                        // counts
-    E.scratch(13).reserve((size_t)cap * sizeof(uint64_t));                        // the listed tiles' modes
-    E.scratch(14).reserve(((size_t)cap + 1 + cap / 4096 + 2) * sizeof(uint32_t)); // offsets, then the scan's sums
-    E.scratch(9).reserve(((size_t)chunk_layers + 1) * sizeof(uint32_t));          // per-layer offsets
-    SliceState* d_state = E.scratch(10).as<SliceState>();
-    float* d_xs = reinterpret_cast<float*>(E.scratch(10).as<char>() + kStateBytes);
-    float* d_ys = d_xs + W;
-    float* d_z = d_ys + W;
-    uint32_t* d_list = E.scratch(11).as<uint32_t>();
-    uint32_t* d_counts = E.scratch(12).as<uint32_t>();
-    uint64_t* d_lmodes = E.scratch(13).as<uint64_t>();
-    uint32_t* d_offsets = E.scratch(14).as<uint32_t>();
-    uint32_t* d_sums = d_offsets + cap + 1;
-    uint32_t* d_loff = E.scratch(9).as<uint32_t>();
-    IMPLI_HIP(hipMemcpyAsync(d_xs, xs.data(), W * sizeof(float), hipMemcpyHostToDevice, s));
-    IMPLI_HIP(hipMemcpyAsync(d_ys, ys.data(), W * sizeof(float), hipMemcpyHostToDevice, s));
-    IMPLI_HIP(hipMemcpyAsync(d_z, z, (size_t)n_layers * sizeof(float), hipMemcpyHostToDevice, s));
-    g_slice.xy.resize(0);
-    g_slice.keys.resize(0);
-    int64_t total = 0, listed = 0, samples = 0, chunks = 0;
-    std::vector<uint32_t> loff((size_t)chunk_layers + 1);
-    for (int l0 = 0; l0 < n_layers; l0 += (int)chunk_layers, ++chunks) {
-        const uint32_t nl = (uint32_t)std::min<int64_t>(chunk_layers, n_layers - l0);
-        const uint32_t n = nl * g.tpl;
-        const int64_t first = (int64_t)l0 * g.tpl;
-        IMPLI_HIP(hipMemsetAsync(d_state, 0, sizeof(SliceState), s));
-        IMPLI_HIP(hipMemsetAsync(d_counts, 0, (size_t)n * sizeof(uint32_t), s));
-        launch_slice_classify(d_prog, prog_depth, d_tab, E.tab_range(), d_xs, d_ys, d_z, g, first, n, prune, d_list, d_lmodes,
-                              d_state, s);
-        IMPLI_HIP(hipGetLastError());
-        SliceState h{};
-        IMPLI_HIP(hipMemcpyAsync(&h, d_state, sizeof h, hipMemcpyDeviceToHost, s));
-        IMPLI_HIP(hipStreamSynchronize(s));
-        if (h.n_listed > n) throw HipError("slice: the tile list overran its chunk");
-        listed += h.n_listed;
-        samples += (int64_t)h.samples;
-        uint32_t chunk_total = 0;
-        if (h.n_listed) {
-            E.scratch(15).reserve((size_t)h.n_listed * kSliceSamples * sizeof(float));
-            float* d_samples = E.scratch(15).as<float>();
-            launch_slice_march(d_prog, prog_depth, d_tab, d_xs, d_ys, d_z, g, first, h.n_listed, d_list, d_lmodes, d_samples,
-                               d_counts, s);
-            launch_scan_u32(d_counts, d_offsets, n, d_sums, false, s);
-            launch_slice_layer_offsets(d_offsets, g.tpl, nl, d_loff, s);
-            IMPLI_HIP(hipGetLastError());
-            IMPLI_HIP(hipMemcpyAsync(loff.data(), d_loff, ((size_t)nl + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            IMPLI_HIP(hipStreamSynchronize(s));
-            chunk_total = loff[nl];
-            if (total + (int64_t)chunk_total >= ((int64_t)1 << 31)) throw InputError("implisolid_slice: the slice reaches 2^31 segments");
-            if (chunk_total) {
-                E.scratch(0).reserve((size_t)chunk_total * 4 * sizeof(float));
-                E.scratch(1).reserve((size_t)chunk_total * 2 * sizeof(uint32_t));
-                launch_slice_emit(d_xs, d_ys, g, first, h.n_listed, d_list, d_samples, d_offsets, chunk_total,
-                                  E.scratch(0).as<float>(), E.scratch(1).as<uint32_t>(), s);
-                IMPLI_HIP(hipGetLastError());
-                g_slice.xy.resize((size_t)(total + chunk_total) * 4);
-                g_slice.keys.resize((size_t)(total + chunk_total) * 2);
-                IMPLI_HIP(hipMemcpyAsync(g_slice.xy.data() + 4 * total, E.scratch(0).p, (size_t)chunk_total * 4 * sizeof(float),
-                                         hipMemcpyDeviceToHost, s));
-                IMPLI_HIP(hipMemcpyAsync(g_slice.keys.data() + 2 * total, E.scratch(1).p,
-                                         (size_t)chunk_total * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                IMPLI_HIP(hipStreamSynchronize(s));
-            }
-        } else {
-            std::fill(loff.begin(), loff.end(), 0u);
-        }
-        for (uint32_t k = 0; k < nl; ++k) layer_offsets[l0 + (int)k] = total + loff[k];
-        total += chunk_total;
-    }
-    layer_offsets[n_layers] = total;
-    if (stats) {
-        stats[0] = (int64_t)n_layers * g.tpl;
-        stats[1] = listed;
-        stats[2] = samples;
-        stats[3] = chunks;
-    }
-    return total;
-}
-}  // namespace
-
-int64_t implisolid_slice(const char* shape_json, int ignore_root_matrix, const float rect[4], int resolution, const float* z,
-                         int n_layers, int64_t* layer_offsets, int64_t stats[4]) {
-    g_last_error.clear();
-    g_slice.n = -1;   // whatever happens, the previous result is gone
-    if (!shape_json || !rect || !z || !layer_offsets) {
-        report("implisolid_slice: bad arguments", false);
-        return -1;
-    }
-    try {
-        // the request first: bad input is refused before anything reaches the device
-        if (n_layers < 1 || n_layers > kSliceMaxLayers) throw InputError("implisolid_slice: n_layers must be in [1, 65536]");
-        for (int l = 0; l < n_layers; ++l)
-            if (!std::isfinite(z[l])) throw InputError("implisolid_slice: every z must be finite");
-        if (resolution < 1 || resolution > kSliceMaxResolution) throw InputError("slice: resolution must be in [1, 4096]");
-        std::vector<float> xs((size_t)resolution + 1), ys((size_t)resolution + 1);
-        slice_coords(rect, resolution, xs.data(), ys.data());
-        ObjectTables tabs;
-        const Program p = compile_mp5(shape_json, ignore_root_matrix != 0, &tabs);
-        Engine& E = engine();
-        hipStream_t s = abi_stream();
-        TableArena arena;   // the shape's own sdf_3d tables, as implisolid_bounds builds them
-        const float* d_tab = arena.set(tabs, E.d_rabbit());
-        ProbeProgram dp(p);
-        g_slice.n = slice_layers(E, s, dp.get(), p.max_depth, d_tab, resolution, xs, ys, z, n_layers, layer_offsets, stats);
-        return g_slice.n;
-    } catch (const InputError& e) {
-        report(e.what(), true);
-        return -1;
-    } catch (const std::exception& e) {
-        (void)hipDeviceSynchronize();
-        report(e.what(), false);
-        return -1;
-    }
-}
-
-int implisolid_slice_copy(float* xy, uint32_t* keys) {
-    g_last_error.clear();
-    if (g_slice.n < 0 || (g_slice.n > 0 && (!xy || !keys))) {
-        report(g_slice.n < 0 ? "implisolid_slice_copy: no slice to copy (the last implisolid_slice failed, or none ran)"
-                             : "implisolid_slice_copy: bad arguments", false);
-        return -1;
-    }
-    if (g_slice.n > 0) {
-        std::memcpy(xy, g_slice.xy.data(), (size_t)g_slice.n * 4 * sizeof(float));
-        std::memcpy(keys, g_slice.keys.data(), (size_t)g_slice.n * 2 * sizeof(uint32_t));
-    }
-    return 0;
-}
-
-int implisolid_slice_coords(const float rect[4], int resolution, float* xs, float* ys) {
-    g_last_error.clear();
-    try {
-        if (!rect || !xs || !ys) throw InputError("implisolid_slice_coords: bad arguments");
-        slice_coords(rect, resolution, xs, ys);
-    } catch (const std::exception& e) {
-        report(e.what(), false);
-        return -1;
-    }
-    return 0;
-}
-
-int64_t implisolid_slice_loops(const uint32_t* keys, int64_t n_segments, int64_t* order, int64_t* loop_offsets,
-                               uint8_t* closed) {
-    g_last_error.clear();
-    if (n_segments < 0 || !loop_offsets || (n_segments > 0 && (!keys || !order || !closed))) {
-        report("implisolid_slice_loops: bad arguments", false);
-        return -1;
-    }
-    int64_t loops = -1;
-    try {
-        loops = slice_loops(keys, n_segments, order, loop_offsets, closed);
-    } catch (const std::exception& e) {
-        report(e.what(), false);
-        return -1;
-    }
-    if (loops < 0) report("implisolid_slice_loops: a key starts two segments or ends two", false);
-    return loops;
-}
-
-// ---- layer images of the solid (implisolid_raster) -------------------------------------------------
-// Layers go through raster.hip's passes in chunks of whole layers, at most kRasterMaxChunk (layer, tile)
-// items each: the image zeroed, classify, a read-back of the two lists' lengths (they size the grids),
-// evaluate, fill, and the pitched copy of the chunk's image into a pinned staging slot with the chunk's
-// layer sums behind it.  There are two slots: the host copies a chunk from its slot into the caller's
-// buffer while the device works on the next one.  E lends its scratch.
-namespace {
-struct RasterStage {             // the staging slots, kept until exit (grow-only)
-    PinnedVec<uint8_t> img[2];
-    PinnedVec<int64_t> sums;
-};
-RasterStage g_raster;
-
-uint32_t raster_chunk_layers(uint32_t tpl, int n_layers) {
-    uint64_t items = kRasterMaxChunk;
-    if (const char* e = std::getenv("IMPLISOLID_RASTER_CHUNK")) {   // read at each call (tests force several chunks)
-        const long long v = std::atoll(e);
-        if (v > 0) items = std::min<uint64_t>((uint64_t)v, kRasterMaxChunk);
-    }
-    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(items / tpl, 1), (uint64_t)n_layers);
-}
-
-void raster_layers(Engine& E, hipStream_t s, const Program* d_prog, int prog_depth, const float* d_tab, int W, int H, int ss,
-                   const std::vector<float>& mx, const std::vector<float>& my, const float* z, int n_layers, uint8_t* cov,
-                   int64_t* layer_sum, int64_t stats[5]) {
-    RasterGrid g;
-    g.W = W;
-    g.H = H;
-    g.s = ss;
-    g.ntx = (W + kRasterTile - 1) / kRasterTile;
-    g.nty = (H + kRasterTile - 1) / kRasterTile;
-    g.tpl = (uint32_t)g.ntx * (uint32_t)g.nty;   // <= 2^20
-    g.pitch = (uint32_t)(kRasterTile * g.ntx);
-    const uint32_t chunk_layers = raster_chunk_layers(g.tpl, n_layers);
-    const uint32_t cap = chunk_layers * g.tpl;   // items per chunk, <= kRasterMaxChunk
-    const bool prune = Engine::pruning() >= 1;
-    constexpr size_t kStateBytes = 256;
-    static_assert(sizeof(RasterState) <= kStateBytes, "the coordinates follow the state block");
-    const size_t layer_img = (size_t)H * g.pitch, layer_out = (size_t)H * (size_t)W;
-    // every reserve before any pointer is taken: a DevBuf that grows moves
-    E.scratch(10).reserve(kStateBytes + (mx.size() + my.size() + (size_t)n_layers) * sizeof(float));
-    E.scratch(11).reserve((size_t)cap * sizeof(uint32_t));                 // evaluate list
-    E.scratch(12).reserve((size_t)cap * sizeof(uint32_t));                 // fill list
-    E.scratch(13).reserve((size_t)cap * sizeof(uint64_t));                 // the listed tiles' modes
-    E.scratch(9).reserve((size_t)n_layers * sizeof(uint64_t));             // layer sums
-    if (cov) E.scratch(15).reserve((size_t)chunk_layers * layer_img);      // the chunk's image
-    RasterState* d_state = E.scratch(10).as<RasterState>();
-    float* d_mx = reinterpret_cast<float*>(E.scratch(10).as<char>() + kStateBytes);
-    float* d_my = d_mx + mx.size();
-    float* d_z = d_my + my.size();
-    uint32_t* d_list = E.scratch(11).as<uint32_t>();
-    uint32_t* d_fill = E.scratch(12).as<uint32_t>();
-    uint64_t* d_lmodes = E.scratch(13).as<uint64_t>();
-    unsigned long long* d_sums = E.scratch(9).as<unsigned long long>();
-    uint8_t* d_img = cov ? E.scratch(15).as<uint8_t>() : nullptr;
-    IMPLI_HIP(hipMemcpyAsync(d_mx, mx.data(), mx.size() * sizeof(float), hipMemcpyHostToDevice, s));
-    IMPLI_HIP(hipMemcpyAsync(d_my, my.data(), my.size() * sizeof(float), hipMemcpyHostToDevice, s));
-    IMPLI_HIP(hipMemcpyAsync(d_z, z, (size_t)n_layers * sizeof(float), hipMemcpyHostToDevice, s));
-    IMPLI_HIP(hipMemsetAsync(d_sums, 0, (size_t)n_layers * sizeof(uint64_t), s));
-    g_raster.sums.resize((size_t)n_layers);
-    if (cov)
-        for (int k = 0; k < (n_layers > (int)chunk_layers ? 2 : 1); ++k) g_raster.img[k].resize((size_t)chunk_layers * layer_out);
-    int64_t evaluated = 0, filled = 0, samples = 0, chunks = 0;
-    // the chunk whose image is on its way into a staging slot, not yet in cov
-    int pend_l0 = 0;
-    uint32_t pend_nl = 0;
-    auto drain = [&](int slot) {   // after a synchronisation that covers the pending copy
-        if (pend_nl) std::memcpy(cov + (size_t)pend_l0 * layer_out, g_raster.img[slot].data(), (size_t)pend_nl * layer_out);
-        pend_nl = 0;
-    };
-    for (int l0 = 0; l0 < n_layers; l0 += (int)chunk_layers, ++chunks) {
-        const uint32_t nl = (uint32_t)std::min<int64_t>(chunk_layers, n_layers - l0);
-        const uint32_t n = nl * g.tpl;
-        const int64_t first = (int64_t)l0 * g.tpl;
-        const int slot = (int)(chunks & 1);
-        IMPLI_HIP(hipMemsetAsync(d_state, 0, sizeof(RasterState), s));
-        if (cov) IMPLI_HIP(hipMemsetAsync(d_img, 0, (size_t)nl * layer_img, s));   // ordered behind the last chunk's copy
-        launch_raster_classify(d_prog, prog_depth, d_tab, E.tab_range(), d_mx, d_my, d_z, g, first, n, prune, d_list, d_lmodes,
-                               d_fill, d_state, s);
-        IMPLI_HIP(hipGetLastError());
-        RasterState h{};
-        IMPLI_HIP(hipMemcpyAsync(&h, d_state, sizeof h, hipMemcpyDeviceToHost, s));
-        IMPLI_HIP(hipStreamSynchronize(s));   // the last chunk's image has landed in the other slot as well
-        if (h.n_eval > n || h.n_fill > n || (uint64_t)h.n_eval + h.n_fill > n) throw HipError("raster: a tile list overran its chunk");
-        evaluated += h.n_eval;
-        filled += h.n_fill;
-        samples += (int64_t)h.samples;
-        launch_raster_eval(d_prog, prog_depth, d_tab, d_mx, d_my, d_z, g, first, l0, h.n_eval, d_list, d_lmodes, d_img, d_sums, s);
-        launch_raster_fill(g, first, l0, h.n_fill, d_fill, d_img, d_sums, s);
-        IMPLI_HIP(hipGetLastError());
-        if (cov) {
-            uint8_t* dst = g_raster.img[slot].data();
-            if (g.pitch == (uint32_t)W)
-                IMPLI_HIP(hipMemcpyAsync(dst, d_img, (size_t)nl * layer_out, hipMemcpyDeviceToHost, s));
-            else
-                IMPLI_HIP(hipMemcpy2DAsync(dst, (size_t)W, d_img, (size_t)g.pitch, (size_t)W, (size_t)nl * (size_t)H,
-                                           hipMemcpyDeviceToHost, s));
-        }
-        IMPLI_HIP(hipMemcpyAsync(g_raster.sums.data() + l0, d_sums + l0, (size_t)nl * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        if (cov) {
-            drain(slot ^ 1);   // the chunk before this one, while the device works on this one
-            pend_l0 = l0;
-            pend_nl = nl;
-        }
-    }
-    IMPLI_HIP(hipStreamSynchronize(s));
-    if (cov) drain((int)((chunks - 1) & 1));
-    for (int l = 0; l < n_layers; ++l) layer_sum[l] = g_raster.sums.data()[l];
-    if (stats) {
-        stats[0] = (int64_t)n_layers * g.tpl;
-        stats[1] = evaluated;
-        stats[2] = filled;
-        stats[3] = samples;
-        stats[4] = chunks;
-    }
-}
-}  // namespace
-
-int implisolid_raster(const char* shape_json, int ignore_root_matrix, const float rect[4], int width, int height, int supersample,
-                      const float* z, int n_layers, uint8_t* cov, int64_t* layer_sum, int64_t stats[5]) {
-    g_last_error.clear();
-    if (!shape_json || !rect || !z || !layer_sum) {
-        report("implisolid_raster: bad arguments", false);
-        return -1;
-    }
-    try {
-        // the request first: bad input is refused before anything is compiled or reaches the device
-        if (n_layers < 1 || n_layers > kRasterMaxLayers) throw InputError("implisolid_raster: n_layers must be in [1, 65536]");
-        for (int l = 0; l < n_layers; ++l)
-            if (!std::isfinite(z[l])) throw InputError("implisolid_raster: every z must be finite");
-        if (width < 1 || width > kRasterMaxSide || height < 1 || height > kRasterMaxSide)
-            throw InputError("implisolid_raster: width and height must be in [1, 16384]");
-        if (supersample != 1 && supersample != 2 && supersample != 4) throw InputError("implisolid_raster: supersample must be 1, 2 or 4");
-        std::vector<float> mx((size_t)width * supersample), my((size_t)height * supersample);
-        raster_coords(rect, width, height, supersample, mx.data(), my.data());
-        ObjectTables tabs;
-        const Program p = compile_mp5(shape_json, ignore_root_matrix != 0, &tabs);
-        Engine& E = engine();
-        hipStream_t s = abi_stream();
-        TableArena arena;   // the shape's own sdf_3d tables, as implisolid_bounds builds them
-        const float* d_tab = arena.set(tabs, E.d_rabbit());
-        ProbeProgram dp(p);
-        raster_layers(E, s, dp.get(), p.max_depth, d_tab, width, height, supersample, mx, my, z, n_layers, cov, layer_sum, stats);
-        return 0;
-    } catch (const InputError& e) {
-        report(e.what(), true);
-        return -1;
-    } catch (const std::exception& e) {
-        (void)hipDeviceSynchronize();
-        report(e.what(), false);
-        return -1;
-    }
-}
-
-int implisolid_raster_coords(const float rect[4], int width, int height, int supersample, float* mx, float* my) {
-    g_last_error.clear();
-    try {
-        if (!rect || !mx || !my) throw InputError("implisolid_raster_coords: bad arguments");
-        raster_coords(rect, width, height, supersample, mx, my);
-    } catch (const std::exception& e) {
-        report(e.what(), false);
-        return -1;
-    }
-    return 0;
-}
-
-// ---- rays against the solid (implisolid_raycast) -----------------------------------------------------
-// Rays go through raycast.hip's two passes in chunks of at most kRayMaxChunk rays: the chunk's origins
-// and directions uploaded, march, finish, and the results copied into the caller's arrays.  The work
-// figures add up on the device over the chunks and are read back once.  E lends its scratch.
-namespace {
-bool g_ray_timing = false;       // implisolid_debug_raycast_ms: HIP events around the two launches
-double g_ray_ms[2] = {-1.0, -1.0};
-
-uint32_t ray_chunk_rays() {
-    uint64_t rays = kRayMaxChunk;
-    if (const char* e = std::getenv("IMPLISOLID_RAY_CHUNK")) {   // read at each call (tests force several chunks)
-        const long long v = std::atoll(e);
-        if (v > 0) rays = std::min<uint64_t>((uint64_t)v, kRayMaxChunk);
-    }
-    return (uint32_t)rays;
-}
-
-void cast_rays(Engine& E, hipStream_t s, const Program* d_prog, int prog_depth, const float* d_tab, const std::vector<float>& ts,
-               const float* origins, const float* dirs, int64_t n, int bisect, int32_t* hit, float* t, float* f, float* normals,
-               int64_t stats[6]) {
-    const int N = (int)ts.size() - 1;
-    const uint32_t cap = (uint32_t)std::min<int64_t>(ray_chunk_rays(), n);
-    const bool prune = Engine::pruning() >= 1;
-    constexpr size_t kStateBytes = 256;
-    static_assert(sizeof(RayState) <= kStateBytes, "the sample table follows the state block");
-    // every reserve before any pointer is taken: a DevBuf that grows moves
-    E.scratch(10).reserve(kStateBytes + ts.size() * sizeof(float));
-    E.scratch(11).reserve((size_t)cap * 6 * sizeof(float));                // origins, directions
-    E.scratch(12).reserve((size_t)cap * 3 * sizeof(uint32_t));             // hit, F(ts[hit]), work
-    E.scratch(13).reserve((size_t)cap * sizeof(uint64_t));                 // the hit segments' modes
-    E.scratch(9).reserve((size_t)cap * 2 * sizeof(float));                 // t, f
-    if (normals) E.scratch(15).reserve((size_t)cap * 3 * sizeof(float));
-    RayState* d_state = E.scratch(10).as<RayState>();
-    float* d_ts = reinterpret_cast<float*>(E.scratch(10).as<char>() + kStateBytes);
-    float* d_org = E.scratch(11).as<float>();
-    float* d_dir = d_org + (size_t)cap * 3;
-    int32_t* d_hit = E.scratch(12).as<int32_t>();
-    float* d_fhit = reinterpret_cast<float*>(d_hit + cap);
-    uint32_t* d_work = reinterpret_cast<uint32_t*>(d_hit + 2 * (size_t)cap);
-    uint64_t* d_hmodes = E.scratch(13).as<uint64_t>();
-    float* d_t = E.scratch(9).as<float>();
-    float* d_f = d_t + cap;
-    float* d_n = normals ? E.scratch(15).as<float>() : nullptr;
-    IMPLI_HIP(hipMemsetAsync(d_state, 0, sizeof(RayState), s));
-    IMPLI_HIP(hipMemcpyAsync(d_ts, ts.data(), ts.size() * sizeof(float), hipMemcpyHostToDevice, s));
-    struct Events {
-        hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-        ~Events() {
-            for (auto& x : e)
-                if (x) (void)hipEventDestroy(x);
-        }
-    } events;
-    hipEvent_t* ev = events.e;
-    if (g_ray_timing) {
-        for (auto& e : events.e) IMPLI_HIP(hipEventCreate(&e));
-        g_ray_ms[0] = g_ray_ms[1] = 0.0;
-    }
-    int64_t chunks = 0;
-    for (int64_t first = 0; first < n; first += cap, ++chunks) {
-        const uint32_t nc = (uint32_t)std::min<int64_t>(cap, n - first);
-        IMPLI_HIP(hipMemcpyAsync(d_org, origins + 3 * first, (size_t)nc * 12, hipMemcpyHostToDevice, s));
-        IMPLI_HIP(hipMemcpyAsync(d_dir, dirs + 3 * first, (size_t)nc * 12, hipMemcpyHostToDevice, s));
-        if (ev[0]) IMPLI_HIP(hipEventRecord(ev[0], s));
-        launch_ray_march(d_prog, prog_depth, d_tab, E.tab_range(), d_ts, d_org, d_dir, nc, N, prune, d_hit, d_hmodes, d_fhit,
-                         d_work, s);
-        if (ev[1]) IMPLI_HIP(hipEventRecord(ev[1], s));
-        launch_ray_finish(d_prog, prog_depth, d_tab, d_ts, d_org, d_dir, nc, N, bisect, d_hit, d_hmodes, d_fhit, d_work, d_t,
-                          d_f, d_n, d_state, s);
-        if (ev[2]) IMPLI_HIP(hipEventRecord(ev[2], s));
-        IMPLI_HIP(hipGetLastError());
-        IMPLI_HIP(hipMemcpyAsync(hit + first, d_hit, (size_t)nc * 4, hipMemcpyDeviceToHost, s));
-        IMPLI_HIP(hipMemcpyAsync(t + first, d_t, (size_t)nc * 4, hipMemcpyDeviceToHost, s));
-        IMPLI_HIP(hipMemcpyAsync(f + first, d_f, (size_t)nc * 4, hipMemcpyDeviceToHost, s));
-        if (normals) IMPLI_HIP(hipMemcpyAsync(normals + 3 * first, d_n, (size_t)nc * 12, hipMemcpyDeviceToHost, s));
-        if (ev[0]) {
-            IMPLI_HIP(hipStreamSynchronize(s));
-            float a = 0.f, b = 0.f;
-            IMPLI_HIP(hipEventElapsedTime(&a, ev[0], ev[1]));
-            IMPLI_HIP(hipEventElapsedTime(&b, ev[1], ev[2]));
-            g_ray_ms[0] += a;
-            g_ray_ms[1] += b;
-        }
-    }
-    RayState h{};
-    IMPLI_HIP(hipMemcpyAsync(&h, d_state, sizeof h, hipMemcpyDeviceToHost, s));
-    IMPLI_HIP(hipStreamSynchronize(s));
-    if (stats) {
-        stats[0] = n * (int64_t)((N + kRaySegment - 1) / kRaySegment);
-        stats[1] = (int64_t)h.skipped;
-        stats[2] = (int64_t)h.evaluated;
-        stats[3] = (int64_t)h.hits;
-        stats[4] = (int64_t)h.inside;
-        stats[5] = chunks;
-    }
-}
-}  // namespace
-
-int implisolid_raycast(const char* shape_json, int ignore_root_matrix, const float* origins, const float* dirs, int64_t n,
-                       float t0, float t1, int steps, int bisect, int32_t* hit, float* t, float* f, float* normals,
-                       int64_t stats[6]) {
-    g_last_error.clear();
-    if (!shape_json || (n > 0 && (!origins || !dirs || !hit || !t || !f))) {
-        report("implisolid_raycast: bad arguments", false);
-        return -1;
-    }
-    try {
-        // the request first: bad input is refused before anything is compiled or reaches the device
-        if (n < 0 || n > kRayMaxRays) throw InputError("implisolid_raycast: n must be in [0, 2^24]");
-        if (bisect < 0 || bisect > kRayMaxBisect) throw InputError("implisolid_raycast: bisect must be in [0, 32]");
-        if (steps < 1 || steps > kRayMaxSteps) throw InputError("implisolid_raycast: steps must be in [1, 65536]");
-        std::vector<float> ts((size_t)steps + 1);
-        ray_params(t0, t1, steps, ts.data());
-        for (int64_t i = 0; i < 3 * n; ++i)
-            if (!std::isfinite(origins[i]) || !std::isfinite(dirs[i]))
-                throw InputError("implisolid_raycast: every origin and direction must be finite");
-        ObjectTables tabs;
-        const Program p = compile_mp5(shape_json, ignore_root_matrix != 0, &tabs);
-        if (stats) std::fill(stats, stats + 6, (int64_t)0);
-        if (n == 0) return 0;
-        Engine& E = engine();
-        hipStream_t s = abi_stream();
-        TableArena arena;   // the shape's own sdf_3d tables, as implisolid_bounds builds them
-        const float* d_tab = arena.set(tabs, E.d_rabbit());
-        ProbeProgram dp(p);
-        cast_rays(E, s, dp.get(), p.max_depth, d_tab, ts, origins, dirs, n, bisect, hit, t, f, normals, stats);
-        return 0;
-    } catch (const InputError& e) {
-        report(e.what(), true);
-        return -1;
-    } catch (const std::exception& e) {
-        (void)hipDeviceSynchronize();
-        report(e.what(), false);
-        return -1;
-    }
-}
-
-int implisolid_ray_params(float t0, float t1, int steps, float* ts) {
-    g_last_error.clear();
-    try {
-        if (!ts) throw InputError("implisolid_ray_params: bad arguments");
-        ray_params(t0, t1, steps, ts);
-    } catch (const std::exception& e) {
-        report(e.what(), false);
-        return -1;
-    }
-    return 0;
-}
-
-int implisolid_debug_raycast_ms(int enable, double ms[2]) {
-    g_ray_timing = enable != 0;
-    if (ms) {
-        ms[0] = g_ray_ms[0];
-        ms[1] = g_ray_ms[1];
-    }
-    return 0;
-}
-
-// ---- mass properties of the solid (implisolid_mass) ----------------------------------------------
-// mass.hip's passes on the current device: E lends its scratch buffers (10: state block, layer counts,
-// edge and sample tables; 11-14: the two lists, as compute_bounds takes them).  The only read-back is
-// the state block with the layer counts behind it, after the last launch; a raised overflow flag voids
-// the run, the lists grow and everything runs again (the first launch zeroes the sums).
-namespace {
-uint32_t mass_list_capacity(int depth) {
-    // as bounds_list_capacity: 8 N^2 boxes by default, clamped the same way
-    uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(8ull << (2 * depth), 4096), 1ull << 21);
-    if (const char* e = std::getenv("IMPLISOLID_MASS_LIST")) {   // read at each call (tests force the rerun path)
-        const long long v = std::atoll(e);
-        if (v > 0) cap = (uint64_t)v;
-    }
-    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(cap, 1), kBoundsMaxList);
-}
-
-bool compute_mass(Engine& E, hipStream_t s, const Program* d_prog, int prog_depth, const float* d_tab, const float box[6],
-                  int depth, uint64_t moments[10], int64_t* layer_cells, int64_t stats[4]) {
-    const int N = 1 << depth, last = depth - 2, first = std::min(3, last);
-    std::vector<float> tables((size_t)3 * (N + 1) + (size_t)3 * N);
-    bounds_edges(box, depth, tables.data());                    // validates depth and box (InputError)
-    mass_mids(box, depth, tables.data() + 3 * (N + 1));
-    const bool prune = Engine::pruning() >= 1;
-    constexpr size_t kStateBytes = 256;
-    static_assert(sizeof(MassState) <= kStateBytes, "the layer counts follow the state block");
-    const size_t head = kStateBytes + (size_t)N * sizeof(uint64_t);   // what is read back
-    uint32_t cap = mass_list_capacity(depth);
-    int64_t reruns = 0;
-    std::vector<uint64_t> h(head / sizeof(uint64_t));
-    MassState hs{};
-    for (bool uploaded = false;;) {
-        // every reserve before any pointer is taken: a DevBuf that grows moves
-        E.scratch(10).reserve(head + tables.size() * sizeof(float));
-        uint32_t* d_box[2] = {nullptr, nullptr};
-        uint64_t* d_modes[2] = {nullptr, nullptr};
-        if (prune) {
-            for (int k = 0; k < 2; ++k) {
-                E.scratch(11 + k).reserve((size_t)cap * sizeof(uint32_t));
-                E.scratch(13 + k).reserve((size_t)cap * sizeof(uint64_t));
-                d_box[k] = E.scratch(11 + k).as<uint32_t>();
-                d_modes[k] = E.scratch(13 + k).as<uint64_t>();
-            }
-        }
-        char* base = E.scratch(10).as<char>();
-        MassState* d_state = reinterpret_cast<MassState*>(base);
-        unsigned long long* d_layers = reinterpret_cast<unsigned long long*>(base + kStateBytes);
-        float* d_edges = reinterpret_cast<float*>(base + head);
-        float* d_mids = d_edges + 3 * (N + 1);
-        if (!uploaded) {
-            IMPLI_HIP(hipMemcpyAsync(d_edges, tables.data(), tables.size() * sizeof(float), hipMemcpyHostToDevice, s));
-            uploaded = true;
-        }
-        launch_mass(d_prog, prog_depth, d_tab, E.tab_range(), d_edges, d_mids, depth, prune, d_box, d_modes, cap, d_state,
-                    d_layers, s);
-        IMPLI_HIP(hipGetLastError());
-        IMPLI_HIP(hipMemcpyAsync(h.data(), base, head, hipMemcpyDeviceToHost, s));
-        IMPLI_HIP(hipStreamSynchronize(s));
-        std::memcpy(&hs, h.data(), sizeof hs);
-        if (!hs.overflow) break;
-        if (cap >= kBoundsMaxList) throw HipError("mass: list overflow at the largest capacity");
-        uint64_t want = 2ull * cap;   // the counts kept counting past the capacity: at least that many
-        for (int l = first; l <= last; ++l) want = std::max<uint64_t>(want, hs.count[l]);
-        cap = (uint32_t)std::min<uint64_t>(want, kBoundsMaxList);
-        ++reruns;
-    }
-    for (int k = 0; k < 10; ++k) moments[k] = hs.moments[k];
-    if (layer_cells)
-        for (int k = 0; k < N; ++k) layer_cells[k] = (int64_t)h[kStateBytes / sizeof(uint64_t) + (size_t)k];
-    if (stats) {
-        stats[0] = (int64_t)hs.bounded;
-        stats[1] = (int64_t)hs.whole_cells;
-        stats[2] = prune ? 64 * (int64_t)hs.count[last] : (int64_t)1 << (3 * depth);
-        stats[3] = reruns;
-    }
-    return hs.moments[0] != 0;
-}
-}  // namespace
-
-int implisolid_mass(const char* shape_json, int ignore_root_matrix, const float box[6], int depth, uint64_t moments[10],
-                    int64_t* layer_cells, int64_t stats[4]) {
-    g_last_error.clear();
-    if (!shape_json || !box || !moments) {
-        report("implisolid_mass: bad arguments", false);
-        return -1;
-    }
-    try {
-        // depth and box first: bad input is refused before anything reaches the device
-        if (depth < kBoundsMinDepth || depth > kBoundsMaxDepth) throw InputError("implisolid_mass: depth must be in [3, 10]");
-        {
-            std::vector<float> probe((size_t)3 * (1 << depth));
-            mass_mids(box, depth, probe.data());
-        }
-        ObjectTables tabs;
-        const Program p = compile_mp5(shape_json, ignore_root_matrix != 0, &tabs);
-        Engine& E = engine();
-        hipStream_t s = abi_stream();
-        TableArena arena;   // the shape's own sdf_3d tables, as implisolid_bounds builds them
-        const float* d_tab = arena.set(tabs, E.d_rabbit());
-        ProbeProgram dp(p);
-        return compute_mass(E, s, dp.get(), p.max_depth, d_tab, box, depth, moments, layer_cells, stats) ? 1 : 0;
-    } catch (const InputError& e) {
-        report(e.what(), true);
-        return -1;
-    } catch (const std::exception& e) {
-        (void)hipDeviceSynchronize();
-        report(e.what(), false);
-        return -1;
-    }
-}
-
-int implisolid_mass_mids(const float box[6], int depth, float* mids) {
-    g_last_error.clear();
-    try {
-        if (!box || !mids) throw InputError("implisolid_mass_mids: bad arguments");
-        mass_mids(box, depth, mids);
-    } catch (const std::exception& e) {
-        report(e.what(), false);
-        return -1;
-    }
-    return 0;
-}
-
-int implisolid_mass_physical(const float box[6], int depth, const uint64_t moments[10], double out[10]) {
-    g_last_error.clear();
-    try {
-        if (!box || !moments || !out) throw InputError("implisolid_mass_physical: bad arguments");
-        return mass_physical(box, depth, moments, out) ? 1 : 0;
-    } catch (const std::exception& e) {
-        report(e.what(), false);
-        return -1;
-    }
 }
 
 int implisolid_parse_fit_box(const char* mc_json, int32_t out[3]) {

@@ -1,0 +1,422 @@
+"""The refusal paths of the field queries (bounds, slice, raster, raycast, mass, their host-only
+companions and the two interval probes): the return value and the exact implisolid_last_error() text
+of every request that is refused before anything reaches a device, and that the library answers the
+next call.  The literals in EXPECTED were recorded from the library before the queries moved to
+csrc/abi_queries.hip; they pin that the move changed no error path.  No GPU."""
+import ctypes
+
+import numpy as np
+import pytest
+
+fp = ctypes.POINTER(ctypes.c_float)
+dp = ctypes.POINTER(ctypes.c_double)
+ip = ctypes.POINTER(ctypes.c_int32)
+up = ctypes.POINTER(ctypes.c_uint32)
+lp = ctypes.POINTER(ctypes.c_int64)
+ulp = ctypes.POINTER(ctypes.c_uint64)
+bp = ctypes.POINTER(ctypes.c_uint8)
+
+EYE = [1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1]
+SPHERE = ('{"type": "iellipsoid", "matrix": %s}' % EYE).encode()
+TRUNCATED = b'{"type": "iellipsoid", "matrix": [1, 0'          # not JSON
+NO_SUCH_TYPE = ('{"type": "no_such_solid", "matrix": %s}' % EYE).encode()
+NAN, INF = float("nan"), float("inf")
+
+
+def F(*v):
+    return np.array(v, np.float32)
+
+
+class Args:
+    """One entry's valid request; a case replaces some arguments by name and calls it."""
+
+    def __init__(self, fn, **valid):
+        self.fn, self.valid = fn, valid
+
+    def __call__(self, L, **changed):
+        unknown = set(changed) - set(self.valid)
+        assert not unknown, unknown
+        keep = []   # the arrays outlive the call
+
+        def c(v):
+            if isinstance(v, np.ndarray):
+                keep.append(v)
+                t = {np.float32: fp, np.float64: dp, np.int32: ip, np.uint32: up, np.int64: lp, np.uint64: ulp, np.uint8: bp}
+                return v.ctypes.data_as(t[v.dtype.type])
+            return v
+        return int(getattr(L, self.fn)(*[c(changed.get(k, v)) for k, v in self.valid.items()]))
+
+
+BOX = F(-1, 1, -1, 1, -1, 1)
+RECT = F(-1, 1, -1, 1)
+Z2 = F(-0.25, 0.25)
+RAYS = F(-2, 0, 0, -2, 0.25, 0)
+DIRS = F(1, 0, 0, 1, 0, 0)
+
+
+def i64(n):
+    return np.zeros(n, np.int64)
+
+
+ENTRY = {
+    "bounds": Args("implisolid_bounds", shape=SPHERE, irm=0, search=BOX, depth=4, out=F(*[0] * 6), stats=i64(4)),
+    "mass": Args("implisolid_mass", shape=SPHERE, irm=0, box=BOX, depth=4, moments=np.zeros(10, np.uint64), layers=i64(16),
+                 stats=i64(4)),
+    "slice": Args("implisolid_slice", shape=SPHERE, irm=0, rect=RECT, resolution=8, z=Z2, n_layers=2, offsets=i64(3),
+                  stats=i64(4)),
+    "raster": Args("implisolid_raster", shape=SPHERE, irm=0, rect=RECT, width=8, height=8, supersample=1, z=Z2, n_layers=2,
+                   cov=np.zeros(128, np.uint8), sums=i64(2), stats=i64(5)),
+    "raycast": Args("implisolid_raycast", shape=SPHERE, irm=0, origins=RAYS, dirs=DIRS, n=2, t0=0.0, t1=4.0, steps=8, bisect=4,
+                    hit=np.zeros(2, np.int32), t=F(0, 0), f=F(0, 0), normals=F(*[0] * 6), stats=i64(6)),
+    "intervals": Args("implisolid_debug_intervals", shape=SPHERE, irm=0, variant=0, boxes=F(*BOX), modes_in=None, n=1,
+                      iv=F(0, 0), modes_out=np.zeros(1, np.uint64)),
+    "eval_modes": Args("implisolid_debug_eval_modes", shape=SPHERE, irm=0, xyz=F(0, 0, 0), modes=np.zeros(1, np.uint64), n=1,
+                       f=F(0)),
+    # the host-only entries
+    "bounds_edges": Args("implisolid_bounds_edges", search=BOX, depth=3, edges=F(*[0] * 27)),
+    "fit_box": Args("implisolid_fit_box", search=BOX, bounds=F(-.5, .5, -.5, .5, -.5, .5), resolution=16, margin=2,
+                    out=F(*[0] * 6)),
+    "slice_coords": Args("implisolid_slice_coords", rect=RECT, resolution=4, xs=F(*[0] * 5), ys=F(*[0] * 5)),
+    "slice_loops": Args("implisolid_slice_loops", keys=np.array([1, 2, 2, 1], np.uint32), n=2, order=i64(2), offsets=i64(3),
+                        closed=np.zeros(2, np.uint8)),
+    "slice_copy": Args("implisolid_slice_copy", xy=F(*[0] * 4), keys=np.zeros(2, np.uint32)),
+    "raster_coords": Args("implisolid_raster_coords", rect=RECT, width=4, height=4, supersample=2, mx=F(*[0] * 8),
+                          my=F(*[0] * 8)),
+    "ray_params": Args("implisolid_ray_params", t0=0.0, t1=1.0, steps=4, ts=F(*[0] * 5)),
+    "mass_mids": Args("implisolid_mass_mids", box=BOX, depth=3, mids=F(*[0] * 24)),
+    "mass_physical": Args("implisolid_mass_physical", box=BOX, depth=3, moments=np.zeros(10, np.uint64),
+                          out=np.zeros(10, np.float64)),
+}
+
+REVERSED_BOX = F(1, -1, -1, 1, -1, 1)
+NAN_BOX = F(-1, 1, -1, NAN, -1, 1)
+MANY_Z = np.zeros(65537, np.float32)
+
+# (entry, what the case changes in the entry's valid request)
+CASES = {
+    # ---- bounds -----------------------------------------------------------------------------------
+    "bounds null shape": ("bounds", dict(shape=None)),
+    "bounds null search": ("bounds", dict(search=None)),
+    "bounds null out": ("bounds", dict(out=None)),
+    "bounds depth 2": ("bounds", dict(depth=2)),
+    "bounds depth 11": ("bounds", dict(depth=11)),
+    "bounds reversed box": ("bounds", dict(search=REVERSED_BOX)),
+    "bounds nan box": ("bounds", dict(search=NAN_BOX)),
+    "bounds truncated shape": ("bounds", dict(shape=TRUNCATED)),
+    "bounds unknown type": ("bounds", dict(shape=NO_SUCH_TYPE)),
+    "bounds truncated shape, depth 2": ("bounds", dict(shape=TRUNCATED, depth=2)),
+    "bounds unknown type, reversed box": ("bounds", dict(shape=NO_SUCH_TYPE, search=REVERSED_BOX)),
+    # ---- mass -------------------------------------------------------------------------------------
+    "mass null shape": ("mass", dict(shape=None)),
+    "mass null box": ("mass", dict(box=None)),
+    "mass null moments": ("mass", dict(moments=None)),
+    "mass depth 2": ("mass", dict(depth=2)),
+    "mass depth 11": ("mass", dict(depth=11)),
+    "mass reversed box": ("mass", dict(box=REVERSED_BOX)),
+    "mass nan box": ("mass", dict(box=NAN_BOX)),
+    "mass truncated shape": ("mass", dict(shape=TRUNCATED)),
+    "mass unknown type": ("mass", dict(shape=NO_SUCH_TYPE)),
+    "mass truncated shape, depth 11": ("mass", dict(shape=TRUNCATED, depth=11)),
+    "mass unknown type, nan box": ("mass", dict(shape=NO_SUCH_TYPE, box=NAN_BOX)),
+    # ---- slice ------------------------------------------------------------------------------------
+    "slice null shape": ("slice", dict(shape=None)),
+    "slice null rect": ("slice", dict(rect=None)),
+    "slice null z": ("slice", dict(z=None)),
+    "slice null offsets": ("slice", dict(offsets=None)),
+    "slice 0 layers": ("slice", dict(n_layers=0)),
+    "slice 65537 layers": ("slice", dict(z=MANY_Z, n_layers=65537, offsets=i64(65538))),
+    "slice inf z": ("slice", dict(z=F(0, INF))),
+    "slice nan z": ("slice", dict(z=F(NAN, 0))),
+    "slice resolution 0": ("slice", dict(resolution=0)),
+    "slice resolution 4097": ("slice", dict(resolution=4097)),
+    "slice reversed rect": ("slice", dict(rect=F(1, -1, -1, 1))),
+    "slice truncated shape": ("slice", dict(shape=TRUNCATED)),
+    "slice unknown type": ("slice", dict(shape=NO_SUCH_TYPE)),
+    "slice truncated shape, 0 layers": ("slice", dict(shape=TRUNCATED, n_layers=0)),
+    "slice unknown type, resolution 4097": ("slice", dict(shape=NO_SUCH_TYPE, resolution=4097)),
+    "slice truncated shape, nan z": ("slice", dict(shape=TRUNCATED, z=F(NAN, 0))),
+    # ---- raster -----------------------------------------------------------------------------------
+    "raster null shape": ("raster", dict(shape=None)),
+    "raster null rect": ("raster", dict(rect=None)),
+    "raster null z": ("raster", dict(z=None)),
+    "raster null sums": ("raster", dict(sums=None)),
+    "raster 0 layers": ("raster", dict(n_layers=0)),
+    "raster 65537 layers": ("raster", dict(z=MANY_Z, n_layers=65537, sums=i64(65537), cov=None)),
+    "raster inf z": ("raster", dict(z=F(-INF, 0))),
+    "raster nan z": ("raster", dict(z=F(0, NAN))),
+    "raster width 0": ("raster", dict(width=0)),
+    "raster width 16385": ("raster", dict(width=16385, cov=None)),
+    "raster height 0": ("raster", dict(height=0)),
+    "raster height 16385": ("raster", dict(height=16385, cov=None)),
+    "raster supersample 3": ("raster", dict(supersample=3)),
+    "raster supersample 0": ("raster", dict(supersample=0)),
+    "raster reversed rect": ("raster", dict(rect=F(-1, 1, 1, -1))),
+    "raster truncated shape": ("raster", dict(shape=TRUNCATED)),
+    "raster unknown type": ("raster", dict(shape=NO_SUCH_TYPE)),
+    "raster truncated shape, supersample 3": ("raster", dict(shape=TRUNCATED, supersample=3)),
+    "raster unknown type, width 0": ("raster", dict(shape=NO_SUCH_TYPE, width=0)),
+    "raster truncated shape, 65537 layers": ("raster", dict(shape=TRUNCATED, z=MANY_Z, n_layers=65537, sums=i64(65537), cov=None)),
+    # ---- raycast ----------------------------------------------------------------------------------
+    "raycast null shape": ("raycast", dict(shape=None)),
+    "raycast null origins": ("raycast", dict(origins=None)),
+    "raycast null dirs": ("raycast", dict(dirs=None)),
+    "raycast null hit": ("raycast", dict(hit=None)),
+    "raycast null t": ("raycast", dict(t=None)),
+    "raycast null f": ("raycast", dict(f=None)),
+    "raycast n -1": ("raycast", dict(n=-1)),
+    "raycast n 2^24 + 1": ("raycast", dict(n=(1 << 24) + 1)),
+    "raycast steps 0": ("raycast", dict(steps=0)),
+    "raycast steps 65537": ("raycast", dict(steps=65537)),
+    "raycast bisect -1": ("raycast", dict(bisect=-1)),
+    "raycast bisect 33": ("raycast", dict(bisect=33)),
+    "raycast empty range": ("raycast", dict(t0=1.0, t1=1.0)),
+    "raycast nan origin": ("raycast", dict(origins=F(-2, 0, 0, -2, NAN, 0))),
+    "raycast inf direction": ("raycast", dict(dirs=F(1, 0, 0, INF, 0, 0))),
+    "raycast truncated shape": ("raycast", dict(shape=TRUNCATED)),
+    "raycast unknown type": ("raycast", dict(shape=NO_SUCH_TYPE)),
+    "raycast truncated shape, bisect 33": ("raycast", dict(shape=TRUNCATED, bisect=33)),
+    "raycast unknown type, steps 0": ("raycast", dict(shape=NO_SUCH_TYPE, steps=0)),
+    "raycast truncated shape, nan origin": ("raycast", dict(shape=TRUNCATED, origins=F(-2, 0, 0, -2, NAN, 0))),
+    "raycast unknown type, n -1": ("raycast", dict(shape=NO_SUCH_TYPE, n=-1)),
+    "raycast no rays, truncated shape": ("raycast", dict(shape=TRUNCATED, n=0)),
+    "raycast no rays, unknown type, null arrays": ("raycast", dict(shape=NO_SUCH_TYPE, n=0, origins=None, dirs=None, hit=None,
+                                                                   t=None, f=None, normals=None)),
+    "raycast no rays, steps 0": ("raycast", dict(n=0, steps=0)),
+    # ---- the interval probes ----------------------------------------------------------------------
+    "intervals null shape": ("intervals", dict(shape=None)),
+    "intervals variant 3": ("intervals", dict(variant=3)),
+    "intervals n -1": ("intervals", dict(n=-1)),
+    "intervals null boxes": ("intervals", dict(boxes=None)),
+    "intervals truncated shape": ("intervals", dict(shape=TRUNCATED)),
+    "intervals unknown type": ("intervals", dict(shape=NO_SUCH_TYPE)),
+    "eval_modes null shape": ("eval_modes", dict(shape=None)),
+    "eval_modes n -1": ("eval_modes", dict(n=-1)),
+    "eval_modes null modes": ("eval_modes", dict(modes=None)),
+    "eval_modes truncated shape": ("eval_modes", dict(shape=TRUNCATED)),
+    "eval_modes unknown type": ("eval_modes", dict(shape=NO_SUCH_TYPE)),
+    # ---- host only --------------------------------------------------------------------------------
+    "bounds_edges null search": ("bounds_edges", dict(search=None)),
+    "bounds_edges null edges": ("bounds_edges", dict(edges=None)),
+    "bounds_edges depth 2": ("bounds_edges", dict(depth=2)),
+    "bounds_edges reversed box": ("bounds_edges", dict(search=REVERSED_BOX)),
+    "fit_box null bounds": ("fit_box", dict(bounds=None)),
+    "fit_box null out": ("fit_box", dict(out=None)),
+    "fit_box resolution 4, margin 2": ("fit_box", dict(resolution=4)),
+    "fit_box margin -1": ("fit_box", dict(margin=-1)),
+    "slice_coords null rect": ("slice_coords", dict(rect=None)),
+    "slice_coords null ys": ("slice_coords", dict(ys=None)),
+    "slice_coords resolution 0": ("slice_coords", dict(resolution=0)),
+    "slice_coords nan rect": ("slice_coords", dict(rect=F(-1, NAN, -1, 1))),
+    "slice_loops null offsets": ("slice_loops", dict(offsets=None)),
+    "slice_loops null keys": ("slice_loops", dict(keys=None)),
+    "slice_loops n -1": ("slice_loops", dict(n=-1)),
+    "slice_loops a key starts two segments": ("slice_loops", dict(keys=np.array([1, 2, 1, 3], np.uint32))),
+    "raster_coords null rect": ("raster_coords", dict(rect=None)),
+    "raster_coords null my": ("raster_coords", dict(my=None)),
+    "raster_coords supersample 3": ("raster_coords", dict(supersample=3)),
+    "raster_coords width 0": ("raster_coords", dict(width=0)),
+    "ray_params null ts": ("ray_params", dict(ts=None)),
+    "ray_params steps 0": ("ray_params", dict(steps=0)),
+    "ray_params empty range": ("ray_params", dict(t0=2.0, t1=1.0)),
+    "mass_mids null box": ("mass_mids", dict(box=None)),
+    "mass_mids null mids": ("mass_mids", dict(mids=None)),
+    "mass_mids depth 2": ("mass_mids", dict(depth=2)),
+    "mass_physical null moments": ("mass_physical", dict(moments=None)),
+    "mass_physical null out": ("mass_physical", dict(out=None)),
+    "mass_physical depth 11": ("mass_physical", dict(depth=11)),
+    "mass_physical reversed box": ("mass_physical", dict(box=REVERSED_BOX)),
+}
+
+# name -> (return value, implisolid_last_error()), as the library answered before the move
+EXPECTED = {
+    'bounds null shape': (-1, 'implisolid_bounds: bad arguments'),
+    'bounds null search': (-1, 'implisolid_bounds: bad arguments'),
+    'bounds null out': (-1, 'implisolid_bounds: bad arguments'),
+    'bounds depth 2': (-1, 'implisolid_bounds: depth must be in [3, 10]'),
+    'bounds depth 11': (-1, 'implisolid_bounds: depth must be in [3, 10]'),
+    'bounds reversed box': (-1, 'bounds: the search box must be finite with min < max on every axis'),
+    'bounds nan box': (-1, 'bounds: the search box must be finite with min < max on every axis'),
+    'bounds truncated shape': (-1, 'JSON parse error: expected , or ]'),
+    'bounds unknown type': (-1, 'Invalid object you asked for: "no_such_solid"'),
+    'bounds truncated shape, depth 2': (-1, 'implisolid_bounds: depth must be in [3, 10]'),
+    'bounds unknown type, reversed box': (-1, 'bounds: the search box must be finite with min < max on every axis'),
+    'mass null shape': (-1, 'implisolid_mass: bad arguments'),
+    'mass null box': (-1, 'implisolid_mass: bad arguments'),
+    'mass null moments': (-1, 'implisolid_mass: bad arguments'),
+    'mass depth 2': (-1, 'implisolid_mass: depth must be in [3, 10]'),
+    'mass depth 11': (-1, 'implisolid_mass: depth must be in [3, 10]'),
+    'mass reversed box': (-1, 'bounds: the search box must be finite with min < max on every axis'),
+    'mass nan box': (-1, 'bounds: the search box must be finite with min < max on every axis'),
+    'mass truncated shape': (-1, 'JSON parse error: expected , or ]'),
+    'mass unknown type': (-1, 'Invalid object you asked for: "no_such_solid"'),
+    'mass truncated shape, depth 11': (-1, 'implisolid_mass: depth must be in [3, 10]'),
+    'mass unknown type, nan box': (-1, 'bounds: the search box must be finite with min < max on every axis'),
+    'slice null shape': (-1, 'implisolid_slice: bad arguments'),
+    'slice null rect': (-1, 'implisolid_slice: bad arguments'),
+    'slice null z': (-1, 'implisolid_slice: bad arguments'),
+    'slice null offsets': (-1, 'implisolid_slice: bad arguments'),
+    'slice 0 layers': (-1, 'implisolid_slice: n_layers must be in [1, 65536]'),
+    'slice 65537 layers': (-1, 'implisolid_slice: n_layers must be in [1, 65536]'),
+    'slice inf z': (-1, 'implisolid_slice: every z must be finite'),
+    'slice nan z': (-1, 'implisolid_slice: every z must be finite'),
+    'slice resolution 0': (-1, 'slice: resolution must be in [1, 4096]'),
+    'slice resolution 4097': (-1, 'slice: resolution must be in [1, 4096]'),
+    'slice reversed rect': (-1, 'slice: the rect must be finite with min < max on both axes'),
+    'slice truncated shape': (-1, 'JSON parse error: expected , or ]'),
+    'slice unknown type': (-1, 'Invalid object you asked for: "no_such_solid"'),
+    'slice truncated shape, 0 layers': (-1, 'implisolid_slice: n_layers must be in [1, 65536]'),
+    'slice unknown type, resolution 4097': (-1, 'slice: resolution must be in [1, 4096]'),
+    'slice truncated shape, nan z': (-1, 'implisolid_slice: every z must be finite'),
+    'raster null shape': (-1, 'implisolid_raster: bad arguments'),
+    'raster null rect': (-1, 'implisolid_raster: bad arguments'),
+    'raster null z': (-1, 'implisolid_raster: bad arguments'),
+    'raster null sums': (-1, 'implisolid_raster: bad arguments'),
+    'raster 0 layers': (-1, 'implisolid_raster: n_layers must be in [1, 65536]'),
+    'raster 65537 layers': (-1, 'implisolid_raster: n_layers must be in [1, 65536]'),
+    'raster inf z': (-1, 'implisolid_raster: every z must be finite'),
+    'raster nan z': (-1, 'implisolid_raster: every z must be finite'),
+    'raster width 0': (-1, 'implisolid_raster: width and height must be in [1, 16384]'),
+    'raster width 16385': (-1, 'implisolid_raster: width and height must be in [1, 16384]'),
+    'raster height 0': (-1, 'implisolid_raster: width and height must be in [1, 16384]'),
+    'raster height 16385': (-1, 'implisolid_raster: width and height must be in [1, 16384]'),
+    'raster supersample 3': (-1, 'implisolid_raster: supersample must be 1, 2 or 4'),
+    'raster supersample 0': (-1, 'implisolid_raster: supersample must be 1, 2 or 4'),
+    'raster reversed rect': (-1, 'raster: the rect must be finite with min < max on both axes'),
+    'raster truncated shape': (-1, 'JSON parse error: expected , or ]'),
+    'raster unknown type': (-1, 'Invalid object you asked for: "no_such_solid"'),
+    'raster truncated shape, supersample 3': (-1, 'implisolid_raster: supersample must be 1, 2 or 4'),
+    'raster unknown type, width 0': (-1, 'implisolid_raster: width and height must be in [1, 16384]'),
+    'raster truncated shape, 65537 layers': (-1, 'implisolid_raster: n_layers must be in [1, 65536]'),
+    'raycast null shape': (-1, 'implisolid_raycast: bad arguments'),
+    'raycast null origins': (-1, 'implisolid_raycast: bad arguments'),
+    'raycast null dirs': (-1, 'implisolid_raycast: bad arguments'),
+    'raycast null hit': (-1, 'implisolid_raycast: bad arguments'),
+    'raycast null t': (-1, 'implisolid_raycast: bad arguments'),
+    'raycast null f': (-1, 'implisolid_raycast: bad arguments'),
+    'raycast n -1': (-1, 'implisolid_raycast: n must be in [0, 2^24]'),
+    'raycast n 2^24 + 1': (-1, 'implisolid_raycast: n must be in [0, 2^24]'),
+    'raycast steps 0': (-1, 'implisolid_raycast: steps must be in [1, 65536]'),
+    'raycast steps 65537': (-1, 'implisolid_raycast: steps must be in [1, 65536]'),
+    'raycast bisect -1': (-1, 'implisolid_raycast: bisect must be in [0, 32]'),
+    'raycast bisect 33': (-1, 'implisolid_raycast: bisect must be in [0, 32]'),
+    'raycast empty range': (-1, 'raycast: the range must be finite with t0 < t1'),
+    'raycast nan origin': (-1, 'implisolid_raycast: every origin and direction must be finite'),
+    'raycast inf direction': (-1, 'implisolid_raycast: every origin and direction must be finite'),
+    'raycast truncated shape': (-1, 'JSON parse error: expected , or ]'),
+    'raycast unknown type': (-1, 'Invalid object you asked for: "no_such_solid"'),
+    'raycast truncated shape, bisect 33': (-1, 'implisolid_raycast: bisect must be in [0, 32]'),
+    'raycast unknown type, steps 0': (-1, 'implisolid_raycast: steps must be in [1, 65536]'),
+    'raycast truncated shape, nan origin': (-1, 'implisolid_raycast: every origin and direction must be finite'),
+    'raycast unknown type, n -1': (-1, 'implisolid_raycast: n must be in [0, 2^24]'),
+    'raycast no rays, truncated shape': (-1, 'JSON parse error: expected , or ]'),
+    'raycast no rays, unknown type, null arrays': (-1, 'Invalid object you asked for: "no_such_solid"'),
+    'raycast no rays, steps 0': (-1, 'implisolid_raycast: steps must be in [1, 65536]'),
+    'intervals null shape': (-1, 'implisolid_debug_intervals: bad arguments'),
+    'intervals variant 3': (-1, 'implisolid_debug_intervals: bad arguments'),
+    'intervals n -1': (-1, 'implisolid_debug_intervals: bad arguments'),
+    'intervals null boxes': (-1, 'implisolid_debug_intervals: bad arguments'),
+    'intervals truncated shape': (-1, 'JSON parse error: expected , or ]'),
+    'intervals unknown type': (-1, 'Invalid object you asked for: "no_such_solid"'),
+    'eval_modes null shape': (-1, 'implisolid_debug_eval_modes: bad arguments'),
+    'eval_modes n -1': (-1, 'implisolid_debug_eval_modes: bad arguments'),
+    'eval_modes null modes': (-1, 'implisolid_debug_eval_modes: bad arguments'),
+    'eval_modes truncated shape': (-1, 'JSON parse error: expected , or ]'),
+    'eval_modes unknown type': (-1, 'Invalid object you asked for: "no_such_solid"'),
+    'bounds_edges null search': (-1, 'implisolid_bounds_edges: bad arguments'),
+    'bounds_edges null edges': (-1, 'implisolid_bounds_edges: bad arguments'),
+    'bounds_edges depth 2': (-1, 'bounds: depth must be in [3, 10]'),
+    'bounds_edges reversed box': (-1, 'bounds: the search box must be finite with min < max on every axis'),
+    'fit_box null bounds': (-1, 'implisolid_fit_box: resolution - 2 margin must be >= 1 (margin >= 0)'),
+    'fit_box null out': (-1, 'implisolid_fit_box: resolution - 2 margin must be >= 1 (margin >= 0)'),
+    'fit_box resolution 4, margin 2': (-1, 'implisolid_fit_box: resolution - 2 margin must be >= 1 (margin >= 0)'),
+    'fit_box margin -1': (-1, 'implisolid_fit_box: resolution - 2 margin must be >= 1 (margin >= 0)'),
+    'slice_coords null rect': (-1, 'implisolid_slice_coords: bad arguments'),
+    'slice_coords null ys': (-1, 'implisolid_slice_coords: bad arguments'),
+    'slice_coords resolution 0': (-1, 'slice: resolution must be in [1, 4096]'),
+    'slice_coords nan rect': (-1, 'slice: the rect must be finite with min < max on both axes'),
+    'slice_loops null offsets': (-1, 'implisolid_slice_loops: bad arguments'),
+    'slice_loops null keys': (-1, 'implisolid_slice_loops: bad arguments'),
+    'slice_loops n -1': (-1, 'implisolid_slice_loops: bad arguments'),
+    'slice_loops a key starts two segments': (-1, 'implisolid_slice_loops: a key starts two segments or ends two'),
+    'raster_coords null rect': (-1, 'implisolid_raster_coords: bad arguments'),
+    'raster_coords null my': (-1, 'implisolid_raster_coords: bad arguments'),
+    'raster_coords supersample 3': (-1, 'raster: supersample must be 1, 2 or 4'),
+    'raster_coords width 0': (-1, 'raster: width must be in [1, 16384]'),
+    'ray_params null ts': (-1, 'implisolid_ray_params: bad arguments'),
+    'ray_params steps 0': (-1, 'raycast: steps must be in [1, 65536]'),
+    'ray_params empty range': (-1, 'raycast: the range must be finite with t0 < t1'),
+    'mass_mids null box': (-1, 'implisolid_mass_mids: bad arguments'),
+    'mass_mids null mids': (-1, 'implisolid_mass_mids: bad arguments'),
+    'mass_mids depth 2': (-1, 'mass: depth must be in [3, 10]'),
+    'mass_physical null moments': (-1, 'implisolid_mass_physical: bad arguments'),
+    'mass_physical null out': (-1, 'implisolid_mass_physical: bad arguments'),
+    'mass_physical depth 11': (-1, 'mass: depth must be in [3, 10]'),
+    'mass_physical reversed box': (-1, 'mass: the box must be finite with min < max on every axis'),
+}
+
+
+def observe(L, name):
+    entry, changed = CASES[name]
+    rc = ENTRY[entry](L, **changed)
+    return rc, L.implisolid_last_error().decode()
+
+
+def next_call_works(impli):
+    L = impli.lib()
+    ts = F(*[9] * 5)
+    assert ENTRY["ray_params"](L, ts=ts) == 0 and impli.last_error() == ""
+    assert ts.tolist() == [0, 0.25, 0.5, 0.75, 1]
+    assert ENTRY["fit_box"](L) == 0 and impli.last_error() == ""
+
+
+def test_every_case_is_recorded():
+    assert set(CASES) == set(EXPECTED)
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_refusal(impli, name):
+    rc, msg = observe(impli.lib(), name)
+    assert (rc, msg) == EXPECTED[name]
+    assert rc == -1 and msg, "every case here is a refusal"
+    next_call_works(impli)
+
+
+def test_a_bad_request_wins_over_a_bad_shape(impli):
+    # the request is validated before the shape is compiled: both wrong, the request's message
+    L = impli.lib()
+    for name, (entry, changed) in CASES.items():
+        if "shape" not in changed or len(changed) == 1 or changed.get("n") == 0:
+            continue
+        request_only = {k: v for k, v in changed.items() if k != "shape"}
+        assert ENTRY[entry](L, **request_only) == -1
+        assert impli.last_error() == EXPECTED[name][1], name
+        assert ENTRY[entry](L, shape=changed["shape"]) == -1
+        assert impli.last_error() != EXPECTED[name][1], name
+
+
+def test_raycast_without_rays_compiles_the_shape_and_zeroes_the_stats(impli):
+    L = impli.lib()
+    stats = np.full(6, 7, np.int64)
+    assert ENTRY["raycast"](L, n=0, stats=stats) == 0 and impli.last_error() == ""
+    assert stats.tolist() == [0] * 6
+    stats[:] = 7
+    assert ENTRY["raycast"](L, n=0, origins=None, dirs=None, hit=None, t=None, f=None, normals=None, stats=stats) == 0
+    assert impli.last_error() == "" and stats.tolist() == [0] * 6
+    assert ENTRY["raycast"](L, n=0, stats=None) == 0 and impli.last_error() == ""
+    stats[:] = 7
+    rc, msg = observe(L, "raycast no rays, truncated shape")
+    assert (rc, msg) == EXPECTED["raycast no rays, truncated shape"]
+    assert ENTRY["raycast"](L, n=0, shape=TRUNCATED, stats=stats) == -1 and stats.tolist() == [7] * 6, "stats untouched"
+    next_call_works(impli)
+
+
+SLICE_COPY = (-1, "implisolid_slice_copy: no slice to copy (the last implisolid_slice failed, or none ran)")
+
+
+@pytest.mark.parametrize("name", [n for n, (e, _) in CASES.items() if e == "slice"])
+def test_no_slice_to_copy_after_a_refused_slice(impli, name):
+    L = impli.lib()
+    assert observe(L, name)[0] == -1
+    assert (ENTRY["slice_copy"](L), impli.last_error()) == SLICE_COPY
+    assert (ENTRY["slice_copy"](L, xy=None, keys=None), impli.last_error()) == SLICE_COPY
+    next_call_works(impli)
