@@ -57,6 +57,7 @@ ABI_SYMBOLS = [
     "implisolid_mass", "implisolid_mass_mids", "implisolid_mass_physical",
     "implisolid_raster", "implisolid_raster_coords",
     "implisolid_raycast", "implisolid_ray_params", "implisolid_debug_raycast_ms",
+    "implisolid_ray_spans", "implisolid_ray_spans_copy", "implisolid_debug_ray_spans_ms",
 ]
 
 # implisolid_progress_callback (include/implisolid.h): verts, n_verts, faces, n_faces,
@@ -216,6 +217,10 @@ def lib():
                                 fp, fp, ctypes.POINTER(ctypes.c_int64)], c_int),
         "implisolid_ray_params": ([ctypes.c_float, ctypes.c_float, c_int, fp], c_int),
         "implisolid_debug_raycast_ms": ([c_int, ctypes.POINTER(ctypes.c_double)], c_int),
+        "implisolid_ray_spans": ([c_char_p, c_int, fp, fp, ctypes.c_int64, ctypes.c_float, ctypes.c_float, c_int, c_int, c_int,
+                                  ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)], ctypes.c_int64),
+        "implisolid_ray_spans_copy": ([ip, fp, fp, fp], c_int),
+        "implisolid_debug_ray_spans_ms": ([c_int, ctypes.POINTER(ctypes.c_double)], c_int),
     }
     for name, (args, res) in sig.items():
         try:
@@ -958,6 +963,74 @@ def raycast_kernel_ms(enable=True):
     ms = (ctypes.c_double * 2)()
     lib().implisolid_debug_raycast_ms(int(bool(enable)), ms)
     return float(ms[0]), float(ms[1])
+
+
+def ray_spans(shape, origins, dirs, t0, t1, steps, bisect=16, ignore_root_matrix=False, want_normals=False, return_stats=False):
+    """Every solid span along each ray on the GPU (include/implisolid.h implisolid_ray_spans): the maximal
+    runs of solid samples among the steps + 1 samples ray_params(t0, t1, steps) of p(t) = origin + t * dir,
+    entries and exits refined by `bisect` bisection rounds.  Returns (offsets int64 (n + 1,): ray r's spans
+    are rows offsets[r]:offsets[r + 1], in order along the ray; k int32 (S, 2) = {k_in, k_out}, the first
+    solid sample and the first sample behind the span, steps + 1 where the ray ends inside; t float32 (S, 2)
+    and f float32 (S, 2) = the parameter and the field at {entry, exit}, both on the solid side; normals
+    float32 (S, 2, 3), or None without want_normals), and with return_stats also [segments, segments proved
+    outside, proved solid, evaluated, spans, rays with a span, rays that start inside, chunks]."""
+    fp = ctypes.POINTER(ctypes.c_float)
+    o, d = _rays(origins, dirs, "ray_spans")
+    n = o.shape[0]
+    offs = np.zeros(n + 1, np.int64)
+    stats = (ctypes.c_int64 * 8)()
+    S = lib().implisolid_ray_spans(_s(shape), int(bool(ignore_root_matrix)), o.ctypes.data_as(fp), d.ctypes.data_as(fp), n,
+                                   float(np.float32(t0)), float(np.float32(t1)), int(steps), int(bisect), int(bool(want_normals)),
+                                   offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), stats)
+    if S < 0:
+        raise ImplisolidError(last_error())
+    k = np.empty((S, 2), np.int32)
+    t = np.empty((S, 2), np.float32)
+    f = np.empty((S, 2), np.float32)
+    nrm = np.empty((S, 2, 3), np.float32) if want_normals else None
+    if lib().implisolid_ray_spans_copy(k.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), t.ctypes.data_as(fp), f.ctypes.data_as(fp),
+                                       nrm.ctypes.data_as(fp) if want_normals else None) != 0:
+        raise ImplisolidError(last_error())
+    if return_stats:
+        return offs, k, t, f, nrm, [int(v) for v in stats]
+    return offs, k, t, f, nrm
+
+
+def span_lengths(offsets, t, dirs):
+    """Host only: per ray the solid length along it and its span count, (length float64 (n,), count int64
+    (n,)), from ray_spans()'s offsets and t: the sum in span order of (float64(t_out) - float64(t_in)) * |d|,
+    |d| in float64 (np.bincount with weights)."""
+    offs = np.asarray(offsets, np.int64).reshape(-1)
+    n = offs.size - 1
+    tt = np.asarray(t, np.float32).reshape(-1, 2).astype(np.float64)
+    d = np.asarray(dirs, np.float32).reshape(-1, 3).astype(np.float64)
+    if n < 0 or d.shape[0] != n or tt.shape[0] != (offs[n] if n >= 0 else 0):
+        raise ImplisolidError("span_lengths: offsets (n + 1,), t (offsets[n], 2) and dirs (n, 3) do not fit together")
+    count = np.diff(offs)
+    ray = np.repeat(np.arange(n), count)
+    length = np.bincount(ray, weights=(tt[:, 1] - tt[:, 0]) * np.sqrt((d * d).sum(axis=1))[ray], minlength=n)
+    return length.astype(np.float64), count.astype(np.int64)
+
+
+def xray_view(shape, eye, target, up, width, height, t0, t1, steps, bisect=16, fov_y=None, ortho_height=None,
+              ignore_root_matrix=False, return_stats=False):
+    """An accumulated-thickness image of the solid without a mesh: ray_spans() over view_rays(), reduced by
+    span_lengths().  Returns (thickness float64 (height, width) = the solid length along the pixel's ray,
+    count int32 (height, width) = its spans), and with return_stats also ray_spans()'s stats."""
+    o, d = view_rays(eye, target, up, width, height, fov_y=fov_y, ortho_height=ortho_height)
+    offs, k, t, f, _, stats = ray_spans(shape, o, d, t0, t1, steps, bisect, ignore_root_matrix, False, True)
+    length, count = span_lengths(offs, t, d)
+    H, W = int(height), int(width)
+    out = (length.reshape(H, W), count.astype(np.int32).reshape(H, W))
+    return out + (stats,) if return_stats else out
+
+
+def ray_spans_kernel_ms(enable=True):
+    """Diagnostics: switch the event timing of ray_spans()'s kernels on or off; returns the last timed
+    call's (march ms, scan + tally + emit ms, refine ms), -1 before any."""
+    ms = (ctypes.c_double * 3)()
+    lib().implisolid_debug_ray_spans_ms(int(bool(enable)), ms)
+    return float(ms[0]), float(ms[1]), float(ms[2])
 
 
 def mass_mids(box, depth):

@@ -652,6 +652,206 @@ int implisolid_debug_raycast_ms(int enable, double ms[2]) {
 
 }  // extern "C"
 
+// ---- solid spans along rays (implisolid_ray_spans) -----------------------------------------------------
+// Rays go through rayspans.hip's passes in chunks: at most IMPLISOLID_SPAN_CHUNK rays, and at most
+// kSpanMaxWords (ray, segment) words.  Per chunk: the origins and directions uploaded, march, the scan of
+// the per-ray counts, tally, a read-back of the chunk's offsets (their last entry sizes the outputs), emit,
+// refine, and the copies into the host slot at the running offset.  E lends its scratch.
+namespace {
+struct SpanSlot {                // the last call's result; n < 0: none
+    PinnedVec<int32_t> k;
+    PinnedVec<float> t, f, normals;
+    int64_t n = -1;
+    bool has_normals = false;
+};
+SpanSlot g_spans;
+bool g_span_timing = false;      // implisolid_debug_ray_spans_ms: HIP events around the launches
+double g_span_ms[3] = {-1.0, -1.0, -1.0};
+
+int64_t span_rays(Engine& E, hipStream_t s, const Program* d_prog, int prog_depth, const float* d_tab, const std::vector<float>& ts,
+                  const float* origins, const float* dirs, int64_t n, int bisect, bool want_normals, int64_t* span_offsets,
+                  int64_t stats[8]) {
+    const int N = (int)ts.size() - 1;
+    const uint64_t nseg = (uint64_t)((N + kRaySegment - 1) / kRaySegment);
+    const uint64_t by_env = env_limit("IMPLISOLID_SPAN_CHUNK", kRayMaxChunk, kRayMaxChunk);
+    const uint32_t cap = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(by_env, kSpanMaxWords / nseg), (uint64_t)n);   // nseg <= 1024: >= 1
+    const bool prune = Engine::pruning() >= 1;
+    // every reserve before any pointer is taken: a DevBuf that grows moves
+    E.scratch(10).reserve(kStateBytes + ts.size() * sizeof(float));
+    E.scratch(11).reserve((size_t)cap * 6 * sizeof(float));                         // origins, directions
+    E.scratch(12).reserve((size_t)cap * nseg * sizeof(uint64_t));                   // the solidity words
+    E.scratch(13).reserve((size_t)cap * 2 * sizeof(uint32_t));                      // counts, info
+    E.scratch(14).reserve(((size_t)cap + 1 + cap / 4096 + 2) * sizeof(uint32_t));   // offsets, then the scan's sums
+    SpanState* d_state = E.scratch(10).as<SpanState>();
+    float* d_ts = behind_state<SpanState>(E.scratch(10));
+    float* d_org = E.scratch(11).as<float>();
+    float* d_dir = d_org + (size_t)cap * 3;
+    uint64_t* d_words = E.scratch(12).as<uint64_t>();
+    uint32_t* d_counts = E.scratch(13).as<uint32_t>();
+    uint32_t* d_info = d_counts + cap;
+    uint32_t* d_offsets = E.scratch(14).as<uint32_t>();
+    uint32_t* d_sums = d_offsets + cap + 1;
+    IMPLI_HIP(hipMemsetAsync(d_state, 0, sizeof(SpanState), s));
+    IMPLI_HIP(hipMemcpyAsync(d_ts, ts.data(), ts.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    g_spans.k.resize(0);
+    g_spans.t.resize(0);
+    g_spans.f.resize(0);
+    g_spans.normals.resize(0);
+    EventSet<6> ev;
+    if (g_span_timing) {
+        ev.create();
+        g_span_ms[0] = g_span_ms[1] = g_span_ms[2] = 0.0;
+    }
+    int64_t total = 0, chunks = 0;
+    std::vector<uint32_t> off((size_t)cap + 1);
+    for (int64_t first = 0; first < n; first += cap, ++chunks) {
+        const uint32_t nc = (uint32_t)std::min<int64_t>(cap, n - first);
+        IMPLI_HIP(hipMemcpyAsync(d_org, origins + 3 * first, (size_t)nc * 12, hipMemcpyHostToDevice, s));
+        IMPLI_HIP(hipMemcpyAsync(d_dir, dirs + 3 * first, (size_t)nc * 12, hipMemcpyHostToDevice, s));
+        if (ev[0]) IMPLI_HIP(hipEventRecord(ev[0], s));
+        launch_span_march(d_prog, prog_depth, d_tab, E.tab_range(), d_ts, d_org, d_dir, nc, N, prune, d_words, d_counts, d_info, s);
+        if (ev[1]) IMPLI_HIP(hipEventRecord(ev[1], s));
+        launch_scan_u32(d_counts, d_offsets, nc, d_sums, false, s);
+        launch_span_tally(nc, d_counts, d_info, d_state, s);
+        if (ev[2]) IMPLI_HIP(hipEventRecord(ev[2], s));
+        IMPLI_HIP(hipGetLastError());
+        IMPLI_HIP(hipMemcpyAsync(off.data(), d_offsets, ((size_t)nc + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        IMPLI_HIP(hipStreamSynchronize(s));
+        const uint32_t sc = off[nc];   // the chunk's spans
+        if (total + (int64_t)sc >= ((int64_t)1 << 31)) throw InputError("implisolid_ray_spans: the result reaches 2^31 spans");
+        for (uint32_t i = 0; i < nc; ++i) span_offsets[first + i] = total + off[i];
+        if (sc) {
+            E.scratch(9).reserve((size_t)sc * 3 * sizeof(uint32_t));    // {k_in, k_out}, then the spans' rays
+            E.scratch(15).reserve((size_t)sc * 4 * sizeof(float));      // t, f
+            if (want_normals) E.scratch(0).reserve((size_t)sc * 6 * sizeof(float));
+            int32_t* d_k = E.scratch(9).as<int32_t>();
+            uint32_t* d_ray_of = reinterpret_cast<uint32_t*>(d_k + 2 * (size_t)sc);
+            float* d_t = E.scratch(15).as<float>();
+            float* d_f = d_t + 2 * (size_t)sc;
+            float* d_n = want_normals ? E.scratch(0).as<float>() : nullptr;
+            if (ev[3]) IMPLI_HIP(hipEventRecord(ev[3], s));
+            launch_span_emit(nc, N, d_words, d_info, d_offsets, d_k, d_ray_of, s);
+            if (ev[4]) IMPLI_HIP(hipEventRecord(ev[4], s));
+            launch_span_refine(d_prog, prog_depth, d_tab, E.tab_range(), d_ts, d_org, d_dir, N, bisect, prune, sc, d_k, d_ray_of,
+                               d_t, d_f, d_n, s);
+            if (ev[5]) IMPLI_HIP(hipEventRecord(ev[5], s));
+            IMPLI_HIP(hipGetLastError());
+            const size_t at = (size_t)total, upto = (size_t)(total + sc);
+            g_spans.k.resize(upto * 2);
+            g_spans.t.resize(upto * 2);
+            g_spans.f.resize(upto * 2);
+            if (want_normals) g_spans.normals.resize(upto * 6);
+            IMPLI_HIP(hipMemcpyAsync(g_spans.k.data() + 2 * at, d_k, (size_t)sc * 8, hipMemcpyDeviceToHost, s));
+            IMPLI_HIP(hipMemcpyAsync(g_spans.t.data() + 2 * at, d_t, (size_t)sc * 8, hipMemcpyDeviceToHost, s));
+            IMPLI_HIP(hipMemcpyAsync(g_spans.f.data() + 2 * at, d_f, (size_t)sc * 8, hipMemcpyDeviceToHost, s));
+            if (want_normals) IMPLI_HIP(hipMemcpyAsync(g_spans.normals.data() + 6 * at, d_n, (size_t)sc * 24, hipMemcpyDeviceToHost, s));
+            IMPLI_HIP(hipStreamSynchronize(s));   // the next chunk's launches write the buffers these copies read
+        }
+        if (ev[0]) {
+            float a = 0.f, b = 0.f, c = 0.f, d = 0.f;
+            IMPLI_HIP(hipEventElapsedTime(&a, ev[0], ev[1]));
+            IMPLI_HIP(hipEventElapsedTime(&b, ev[1], ev[2]));
+            if (sc) {
+                IMPLI_HIP(hipEventElapsedTime(&c, ev[3], ev[4]));
+                IMPLI_HIP(hipEventElapsedTime(&d, ev[4], ev[5]));
+            }
+            g_span_ms[0] += a;
+            g_span_ms[1] += b + c;   // scan and tally, then emit
+            g_span_ms[2] += d;
+        }
+        total += sc;
+    }
+    span_offsets[n] = total;
+    SpanState h{};
+    IMPLI_HIP(hipMemcpyAsync(&h, d_state, sizeof h, hipMemcpyDeviceToHost, s));
+    IMPLI_HIP(hipStreamSynchronize(s));
+    if ((int64_t)h.spans != total) throw HipError("ray_spans: the tally and the scan disagree");
+    if (stats) {
+        stats[0] = n * (int64_t)nseg;
+        stats[1] = (int64_t)h.outside;
+        stats[2] = (int64_t)h.solid;
+        stats[3] = stats[0] - stats[1] - stats[2];   // the whole ray is walked
+        stats[4] = total;
+        stats[5] = (int64_t)h.rays;
+        stats[6] = (int64_t)h.inside;
+        stats[7] = chunks;
+    }
+    return total;
+}
+}  // namespace
+
+extern "C" {
+
+int64_t implisolid_ray_spans(const char* shape_json, int ignore_root_matrix, const float* origins, const float* dirs, int64_t n,
+                             float t0, float t1, int steps, int bisect, int want_normals, int64_t* span_offsets,
+                             int64_t stats[8]) {
+    last_error().clear();
+    g_spans.n = -1;   // whatever happens, the previous result is gone
+    if (!shape_json || !span_offsets || (n > 0 && (!origins || !dirs))) {
+        report("implisolid_ray_spans: bad arguments", false);
+        return -1;
+    }
+    return guard_device([&]() -> int64_t {
+        // the request first: bad input is refused before anything is compiled or reaches the device
+        if (n < 0 || n > kRayMaxRays) throw InputError("implisolid_ray_spans: n must be in [0, 2^24]");
+        if (bisect < 0 || bisect > kRayMaxBisect) throw InputError("implisolid_ray_spans: bisect must be in [0, 32]");
+        if (steps < 1 || steps > kRayMaxSteps) throw InputError("implisolid_ray_spans: steps must be in [1, 65536]");
+        std::vector<float> ts((size_t)steps + 1);
+        ray_params(t0, t1, steps, ts.data());
+        for (int64_t i = 0; i < 3 * n; ++i)
+            if (!std::isfinite(origins[i]) || !std::isfinite(dirs[i]))
+                throw InputError("implisolid_ray_spans: every origin and direction must be finite");
+        QueryShape q(shape_json, ignore_root_matrix);   // no rays: a bad shape is still reported
+        if (stats) std::fill(stats, stats + 8, (int64_t)0);
+        g_spans.has_normals = want_normals != 0;
+        if (n == 0) {                                   // ... and nothing creates the engine or a stream
+            span_offsets[0] = 0;
+            g_spans.n = 0;
+            return 0;
+        }
+        q.upload();
+        g_spans.n = span_rays(*q.E, q.s, q.d_prog, q.max_depth, q.d_tab, ts, origins, dirs, n, bisect, want_normals != 0,
+                              span_offsets, stats);
+        return g_spans.n;
+    });
+}
+
+int implisolid_ray_spans_copy(int32_t* k, float* t, float* f, float* normals) {
+    last_error().clear();
+    if (g_spans.n < 0) {
+        report("implisolid_ray_spans_copy: no spans to copy (the last implisolid_ray_spans failed, or none ran)", false);
+        return -1;
+    }
+    if (normals && !g_spans.has_normals) {
+        report("implisolid_ray_spans_copy: the call computed no normals (want_normals was 0)", false);
+        return -1;
+    }
+    if (g_spans.n > 0 && (!k || !t || !f)) {
+        report("implisolid_ray_spans_copy: bad arguments", false);
+        return -1;
+    }
+    if (g_spans.n > 0) {
+        const size_t S = (size_t)g_spans.n;
+        std::memcpy(k, g_spans.k.data(), S * 2 * sizeof(int32_t));
+        std::memcpy(t, g_spans.t.data(), S * 2 * sizeof(float));
+        std::memcpy(f, g_spans.f.data(), S * 2 * sizeof(float));
+        if (normals) std::memcpy(normals, g_spans.normals.data(), S * 6 * sizeof(float));
+    }
+    return 0;
+}
+
+int implisolid_debug_ray_spans_ms(int enable, double ms[3]) {
+    g_span_timing = enable != 0;
+    if (ms) {
+        ms[0] = g_span_ms[0];
+        ms[1] = g_span_ms[1];
+        ms[2] = g_span_ms[2];
+    }
+    return 0;
+}
+
+}  // extern "C"
+
 // ---- mass properties of the solid (implisolid_mass) ----------------------------------------------
 // mass.hip's passes on the current device: E lends its scratch buffers (10: state block, layer counts,
 // edge and sample tables; 11-14: the two lists, as compute_bounds takes them).  The only read-back is

@@ -207,6 +207,34 @@ void launch_ray_finish(const Program* d_prog, int prog_depth, const float* d_tab
                        const float* d_fhit, const uint32_t* d_work, float* d_t, float* d_f, float* d_normals,
                        RayState* d_state, hipStream_t s);
 
+// Solid spans along rays (implisolid_ray_spans; DESIGN "Solid spans along rays", rayspans.hip): per ray
+// every maximal run of solid samples of the table d_ts, with both ends refined.  One chunk = n rays; the
+// launches go on s in the order march, scan of d_counts (launch_scan_u32), tally, emit, refine; only the
+// chunk's span total (the scan's last entry) is read back between tally and emit, to size the outputs.
+struct SpanState {       // zeroed before the first chunk; the chunks add to it
+    unsigned long long outside, solid;       // segments proved outside / proved solid
+    unsigned long long spans, rays, inside;  // spans; rays with a span; rays whose first span has k_in == 0
+};
+// the chunk's (ray, segment) words: 64 MiB of device scratch.  A ray of nseg segments holds at most
+// 32 nseg + 1 spans, so a chunk's spans stay below 2^28 + 2^20 and the 32-bit scan cannot wrap
+constexpr uint64_t kSpanMaxWords = 1ull << 23;
+// march: one wave per ray over the whole ray.  d_words[r * nseg + j]: segment j's solidity word (bit i =
+// sample 64 j + 1 + i; 0 for a segment proved outside, its samples' mask for one proved solid); d_counts:
+// the ray's spans; d_info: segments proved outside | proved solid << 12 | sample 0 solid << 31
+void launch_span_march(const Program* d_prog, int prog_depth, const float* d_tab, float2 tab_range, const float* d_ts,
+                       const float* d_org, const float* d_dir, uint32_t n, int N, bool prune, uint64_t* d_words,
+                       uint32_t* d_counts, uint32_t* d_info, hipStream_t s);
+// tally: the chunk's work figures added to *d_state
+void launch_span_tally(uint32_t n, const uint32_t* d_counts, const uint32_t* d_info, SpanState* d_state, hipStream_t s);
+// emit: d_offsets = the exclusive scan of d_counts (n + 1 entries); d_k[2 i], d_k[2 i + 1] = span i's
+// {k_in, k_out}, d_ray_of[i] = its ray (chunk-local), rays in order and a ray's spans in increasing k_in
+void launch_span_emit(uint32_t n, int N, const uint64_t* d_words, const uint32_t* d_info, const uint32_t* d_offsets,
+                      int32_t* d_k, uint32_t* d_ray_of, hipStream_t s);
+// refine: one lane per span end; d_t, d_f: 2 n_spans floats {in, out}; d_normals (nullable): 6 n_spans
+void launch_span_refine(const Program* d_prog, int prog_depth, const float* d_tab, float2 tab_range, const float* d_ts,
+                        const float* d_org, const float* d_dir, int N, int B, bool prune, uint32_t n_spans, const int32_t* d_k,
+                        const uint32_t* d_ray_of, float* d_t, float* d_f, float* d_normals, hipStream_t s);
+
 // the min / max pyramid of one sdf_3d table inside an object's table arena (host.hpp SdfTable: the
 // padded table at tab_off, level L at lvl_off[L]); one launch per level, in order on s
 void launch_sdf3d_pyramid(float* d_arena, uint32_t tab_off, int sx, int sy, int sz, uint32_t level0, int n_levels,

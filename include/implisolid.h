@@ -453,6 +453,53 @@ int implisolid_ray_params(float t0, float t1, int steps, float* ts);
  * milliseconds summed over its chunks, -1 before any.  Returns 0 */
 int implisolid_debug_raycast_ms(int enable, double ms[2]);
 
+/* Additive: every solid span along each ray on the GPU -- entries, exits, the field and the normals at
+ * both (wall thickness along a direction, X-ray previews, dexels, picking through a part).
+ * Arguments, limits and checks are implisolid_raycast's: n in [0, 2^24], finite origins and directions,
+ * ts = implisolid_ray_params(t0, t1, steps), bisect B in [0, 32], everything checked before a launch;
+ * n = 0 returns 0 without a launch.  p(t), F(t) and "solid iff !(F < 0)" are implisolid_raycast's, points
+ * that are not finite included.  Let s[k] be the solidity of sample k, k = 0 .. N.
+ * A span is a maximal run of consecutive solid samples k_in .. k_out - 1: k_in in 0 .. N, k_out in
+ * 1 .. N + 1, and k_out = N + 1 means that the ray ends inside.  Per span:
+ *   entry, k_in == 0      t_in = ts[0], f_in = F(ts[0])
+ *   entry otherwise       implisolid_raycast's bisection on [ts[k_in - 1], ts[k_in]]: t_in = b, f_in = fb
+ *   exit, k_out == N + 1  t_out = ts[N], f_out = F(ts[N])
+ *   exit otherwise        the mirror: a = ts[k_out - 1], fa = F(a), b = ts[k_out]; B rounds of
+ *                         m = a + 0.5f * (b - a) (a round with m == a or m == b ends the rounds), fm = F(m),
+ *                         if !(fm < 0) then a = m, fa = fm, else b = m; then t_out = a, f_out = fa
+ * Both returned ends are solid points and t_in <= t_out.  f_in and f_out are field values, also where a
+ * proof (below) made every sample of the segment unnecessary.  Normals (want_normals != 0):
+ * implisolid_eval_normals' row at p(t_in) and at p(t_out).
+ *   span_offsets  n + 1 entries: ray r's spans are [span_offsets[r], span_offsets[r + 1]), in increasing k_in
+ *   stats         (may be NULL) [segments = n * ceil(N / 64), segments proved outside, segments proved
+ *                 solid, segments evaluated, spans, rays with at least one span, rays whose first span has
+ *                 k_in == 0, chunks].  The whole ray is walked: entries 1 + 2 + 3 equal entry 0.  At
+ *                 pruning level 0 entries 1 and 2 are 0
+ *   returns       S = span_offsets[n], or -1 with implisolid_last_error() (what implisolid_raycast refuses,
+ *                 or a total that reaches 2^31)
+ * The result stays in one library-owned host slot until the next implisolid_ray_spans call (a failed one
+ * empties it), like implisolid_slice's.
+ * At implisolid_set_pruning level >= 1 the box of a segment's two end points is bounded as in
+ * implisolid_raycast: hi < 0 proves the segment outside, lo >= 0 proves it solid; in both cases none of its
+ * samples is evaluated and it holds no crossing (the box holds every sample of the segment, both end samples
+ * included).  Any other bound -- NaN bounds, and every segment with an end point that is not finite (modes
+ * word 0) -- has the segment evaluated with the bound's modes word.  Neighbouring segments share their
+ * boundary sample, so no crossing falls between segments.  No result depends on the pruning level, the
+ * chunking or any atomic's order.
+ * Rays go in chunks of at most IMPLISOLID_SPAN_CHUNK rays (environment, read at each call; default and
+ * maximum 2^20, minimum 1), cut further so that chunk * ceil(N / 64) stays within 2^23 segment words (64 MiB
+ * of device scratch); offsets are global across chunks.  One device, the interpreter kernels. */
+int64_t implisolid_ray_spans(const char* shape_json, int ignore_root_matrix, const float* origins, const float* dirs,
+                             int64_t n, float t0, float t1, int steps, int bisect, int want_normals,
+                             int64_t* span_offsets, int64_t stats[8]);
+/* the last implisolid_ray_spans result: k = 2 S ints {k_in, k_out}; t, f = 2 S floats each {in, out};
+ * normals = 6 S floats {in, out} x {x, y, z}, or NULL.  Returns 0, or -1: no result, or normals asked for
+ * that the call did not compute */
+int implisolid_ray_spans_copy(int32_t* k, float* t, float* f, float* normals);
+/* diagnostics, as implisolid_debug_raycast_ms: ms (may be NULL) = the last timed call's {march, scan +
+ * tally + emit, refine} milliseconds summed over its chunks, -1 before any.  Returns 0 */
+int implisolid_debug_ray_spans_ms(int enable, double ms[3]);
+
 /* host-only: compile an MP5 tree to the node program; info = {n_instr, depth, n_mats, 0};
    mats_out receives n_mats inverse matrices (12 floats each, up to 256) */
 /* Additive, host only (no GPU): generate and hipRTC-compile the tree kernel for this shape.
