@@ -56,6 +56,7 @@ ABI_SYMBOLS = [
     "implisolid_slice", "implisolid_slice_copy", "implisolid_slice_coords", "implisolid_slice_loops",
     "implisolid_mass", "implisolid_mass_mids", "implisolid_mass_physical",
     "implisolid_raster", "implisolid_raster_coords",
+    "implisolid_islands", "implisolid_islands_copy", "implisolid_debug_islands_ms",
     "implisolid_raycast", "implisolid_ray_params", "implisolid_debug_raycast_ms",
     "implisolid_ray_spans", "implisolid_ray_spans_copy", "implisolid_debug_ray_spans_ms",
 ]
@@ -213,6 +214,10 @@ def lib():
         "implisolid_raster": ([c_char_p, c_int, fp, c_int, c_int, c_int, fp, c_int, ctypes.POINTER(ctypes.c_uint8),
                                ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)], c_int),
         "implisolid_raster_coords": ([fp, c_int, c_int, c_int, fp, fp], c_int),
+        "implisolid_islands": ([c_char_p, c_int, fp, c_int, c_int, c_int, fp, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_int64),
+                                ip, ctypes.POINTER(ctypes.c_int64)], ctypes.c_int64),
+        "implisolid_islands_copy": ([ip], c_int),
+        "implisolid_debug_islands_ms": ([c_int, ctypes.POINTER(ctypes.c_double)], c_int),
         "implisolid_raycast": ([c_char_p, c_int, fp, fp, ctypes.c_int64, ctypes.c_float, ctypes.c_float, c_int, c_int, ip, fp,
                                 fp, fp, ctypes.POINTER(ctypes.c_int64)], c_int),
         "implisolid_ray_params": ([ctypes.c_float, ctypes.c_float, c_int, fp], c_int),
@@ -847,6 +852,58 @@ def raster_coords(rect, width, height, supersample):
     if lib().implisolid_raster_coords(r.ctypes.data_as(fp), W, H, s, mx.ctypes.data_as(fp), my.ctypes.data_as(fp)) != 0:
         raise ImplisolidError(last_error())
     return mx, my
+
+
+COMP_DTYPE = np.dtype([(name, np.int32) for name in ("seed", "area", "below", "x0", "y0", "x1", "y1", "layer")])
+
+
+def layer_islands(shape, rect, width, height, z, supersample=1, threshold=1, connectivity=8, ignore_root_matrix=False,
+                  want_labels=False, return_stats=False):
+    """The connected regions of the solid's layers z = z[l] on the GPU, and which of them are islands
+    (include/implisolid.h implisolid_islands).  The images are raster_layers'; a pixel is solid iff its
+    coverage >= threshold (1 .. supersample^2); connectivity is 4 or 8.  Returns (comp_offsets int64 (L + 1,):
+    layer l's records are comps[comp_offsets[l]:comp_offsets[l + 1]], in increasing seed; comps, a structured
+    array (COMP_DTYPE) of {seed = the smallest py * width + px, area, below = its pixels solid in layer l - 1
+    (area for l = 0), x0, y0, x1, y1 = the inclusive bounding box, layer}), then with want_labels labels int32
+    (L, H, W) = the pixel's seed or -1, and with return_stats [raster_layers' five figures, components, islands,
+    solid pixels]."""
+    fp, lp = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64)
+    r = _rect4(rect, "layer_islands")
+    zz = np.ascontiguousarray(z, np.float32).reshape(-1)
+    W, H, s = int(width), int(height), int(supersample)
+    if not (1 <= W <= 16384 and 1 <= H <= 16384):
+        raise ImplisolidError("layer_islands: width and height must be in [1, 16384]")
+    offs = np.zeros(zz.size + 1, np.int64)
+    labels = np.empty((zz.size, H, W), np.int32) if want_labels else None
+    stats = (ctypes.c_int64 * 8)()
+    C = lib().implisolid_islands(_s(shape), int(bool(ignore_root_matrix)), r.ctypes.data_as(fp), W, H, s, zz.ctypes.data_as(fp),
+                                 int(zz.size), int(threshold), int(connectivity), offs.ctypes.data_as(lp),
+                                 labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if want_labels else None, stats)
+    if C < 0:
+        raise ImplisolidError(last_error())
+    comps = np.empty(C, COMP_DTYPE)
+    if lib().implisolid_islands_copy(comps.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))) != 0:
+        raise ImplisolidError(last_error())
+    out = (offs, comps)
+    if want_labels:
+        out += (labels,)
+    if return_stats:
+        out += ([int(v) for v in stats],)
+    return out
+
+
+def islands_of(comps):
+    """Host only: the records of layer_islands() that are islands (below == 0)."""
+    comps = np.asarray(comps)
+    return comps[comps["below"] == 0]
+
+
+def islands_kernel_ms(enable=True):
+    """Diagnostics: switch the event timing of layer_islands()'s kernels on or off; returns the last timed
+    call's (raster passes, tile pass, merge pass, seed rows + scan, records + tally) ms, -1 before any."""
+    ms = (ctypes.c_double * 5)()
+    lib().implisolid_debug_islands_ms(int(bool(enable)), ms)
+    return tuple(float(v) for v in ms)
 
 
 def ray_params(t0, t1, steps):

@@ -1,5 +1,5 @@
-// abi_queries.hip -- the field queries of the C ABI: the interval probes, bounds, slices, layer images,
-// rays and mass properties.  Each entry validates its request, compiles the shape (QueryShape), puts it
+// abi_queries.hip -- the field queries of the C ABI: the interval probes, bounds, slices, layer images and
+// their islands, rays and mass properties.  Each entry validates its request, compiles the shape (QueryShape), puts it
 // on the device and runs its passes; the scaffolding is abi_common.hpp's.
 #include <cmath>
 #include <cstring>
@@ -521,6 +521,231 @@ int implisolid_raster_coords(const float rect[4], int width, int height, int sup
         raster_coords(rect, width, height, supersample, mx, my);
         return 0;
     });
+}
+
+}  // extern "C"
+
+// ---- islands of the layers (implisolid_islands) -------------------------------------------------------
+// Layers go through raster.hip's passes and then islands.hip's in chunks of whole layers, at most
+// kIslandMaxChunk (layer, raster tile) pairs each: the image zeroed, classify, a read-back of the two lists'
+// lengths, evaluate, fill; then tiles, merge, rows, the scan, a read-back of the chunk's per-layer record
+// offsets (their last entry sizes the records), roots, tally, and the copies of the records into the host
+// slot and of the labels, when asked for, into the caller's array.  The image stays on the device: the last
+// layer of a chunk is copied to a carry buffer for the first layer of the next.  E lends its scratch: 9 - 13
+// and 15 as raster_layers takes them, 14 the row counts, their scan, its sums and the layer offsets, 0 the
+// labels, 1 the records, 2 the carried layer.
+namespace {
+struct IslandSlot {              // the last call's records; n < 0: none
+    PinnedVec<int32_t> comps;
+    int64_t n = -1;
+};
+IslandSlot g_islands;
+bool g_island_timing = false;    // implisolid_debug_islands_ms: HIP events around the launches
+double g_island_ms[5] = {-1.0, -1.0, -1.0, -1.0, -1.0};
+
+int64_t island_layers(Engine& E, hipStream_t s, const Program* d_prog, int prog_depth, const float* d_tab, int W, int H, int ss,
+                      const std::vector<float>& mx, const std::vector<float>& my, const float* z, int n_layers, int threshold,
+                      int connectivity, int64_t* comp_offsets, int32_t* labels, int64_t stats[8]) {
+    RasterGrid g;
+    g.W = W;
+    g.H = H;
+    g.s = ss;
+    g.ntx = (W + kRasterTile - 1) / kRasterTile;
+    g.nty = (H + kRasterTile - 1) / kRasterTile;
+    g.tpl = (uint32_t)g.ntx * (uint32_t)g.nty;
+    g.pitch = (uint32_t)(kRasterTile * g.ntx);
+    const IslandGrid ig = island_grid(W, H, g.pitch, threshold, connectivity);
+    const uint32_t chunk_layers = cabi::chunk_layers("IMPLISOLID_ISLANDS_CHUNK", kIslandMaxChunk, g.tpl, n_layers);
+    const uint32_t cap = chunk_layers * g.tpl;   // items per chunk: <= kIslandMaxChunk, or one layer's
+    const bool prune = Engine::pruning() >= 1;
+    const size_t layer_img = (size_t)H * g.pitch, layer_px = (size_t)H * (size_t)W;
+    const size_t rows_cap = (size_t)chunk_layers * (size_t)H;
+    // every reserve before any pointer is taken: a DevBuf that grows moves (the records' buffer, sized per
+    // chunk, holds nothing else)
+    E.scratch(10).reserve(kStateBytes + (mx.size() + my.size() + (size_t)n_layers) * sizeof(float));
+    E.scratch(11).reserve((size_t)cap * sizeof(uint32_t));                 // evaluate list
+    E.scratch(12).reserve((size_t)cap * sizeof(uint32_t));                 // fill list
+    E.scratch(13).reserve((size_t)cap * sizeof(uint64_t));                 // the listed tiles' modes
+    E.scratch(9).reserve((size_t)n_layers * sizeof(uint64_t));             // layer sums (the raster passes add them)
+    E.scratch(15).reserve((size_t)chunk_layers * layer_img);               // the chunk's image
+    E.scratch(14).reserve((2 * rows_cap + 1 + rows_cap / 4096 + 2 + (size_t)chunk_layers + 1) * sizeof(uint32_t));
+    E.scratch(0).reserve((size_t)chunk_layers * layer_px * sizeof(int32_t));   // labels
+    if (n_layers > (int)chunk_layers) E.scratch(2).reserve(layer_img);     // the carried layer
+    static_assert(sizeof(RasterState) + sizeof(IslandState) <= kStateBytes, "both states share the state block");
+    RasterState* d_state = E.scratch(10).as<RasterState>();
+    IslandState* d_istate = reinterpret_cast<IslandState*>(d_state + 1);
+    float* d_mx = behind_state<RasterState>(E.scratch(10));
+    float* d_my = d_mx + mx.size();
+    float* d_z = d_my + my.size();
+    uint32_t* d_list = E.scratch(11).as<uint32_t>();
+    uint32_t* d_fill = E.scratch(12).as<uint32_t>();
+    uint64_t* d_lmodes = E.scratch(13).as<uint64_t>();
+    unsigned long long* d_sums = E.scratch(9).as<unsigned long long>();
+    uint8_t* d_img = E.scratch(15).as<uint8_t>();
+    uint32_t* d_counts = E.scratch(14).as<uint32_t>();
+    uint32_t* d_offsets = d_counts + rows_cap;
+    uint32_t* d_scan_sums = d_offsets + rows_cap + 1;
+    uint32_t* d_loff = d_scan_sums + rows_cap / 4096 + 2;
+    int32_t* d_lab = E.scratch(0).as<int32_t>();
+    uint8_t* d_carry = n_layers > (int)chunk_layers ? E.scratch(2).as<uint8_t>() : nullptr;
+    IMPLI_HIP(hipMemcpyAsync(d_mx, mx.data(), mx.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    IMPLI_HIP(hipMemcpyAsync(d_my, my.data(), my.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    IMPLI_HIP(hipMemcpyAsync(d_z, z, (size_t)n_layers * sizeof(float), hipMemcpyHostToDevice, s));
+    IMPLI_HIP(hipMemsetAsync(d_sums, 0, (size_t)n_layers * sizeof(uint64_t), s));
+    IMPLI_HIP(hipMemsetAsync(d_istate, 0, sizeof(IslandState), s));
+    g_islands.comps.resize(0);
+    EventSet<9> ev;
+    if (g_island_timing) {
+        ev.create();
+        for (double& m : g_island_ms) m = 0.0;
+    }
+    int64_t total = 0, evaluated = 0, filled = 0, samples = 0, chunks = 0;
+    std::vector<uint32_t> loff((size_t)chunk_layers + 1);
+    for (int l0 = 0; l0 < n_layers; l0 += (int)chunk_layers, ++chunks) {
+        const uint32_t nl = (uint32_t)std::min<int64_t>(chunk_layers, n_layers - l0);
+        const uint32_t n = nl * g.tpl;
+        const int64_t first = (int64_t)l0 * g.tpl;
+        IMPLI_HIP(hipMemsetAsync(d_state, 0, sizeof(RasterState), s));
+        IMPLI_HIP(hipMemsetAsync(d_img, 0, (size_t)nl * layer_img, s));
+        if (ev[0]) IMPLI_HIP(hipEventRecord(ev[0], s));
+        launch_raster_classify(d_prog, prog_depth, d_tab, E.tab_range(), d_mx, d_my, d_z, g, first, n, prune, d_list, d_lmodes,
+                               d_fill, d_state, s);
+        if (ev[1]) IMPLI_HIP(hipEventRecord(ev[1], s));
+        IMPLI_HIP(hipGetLastError());
+        RasterState h{};
+        IMPLI_HIP(hipMemcpyAsync(&h, d_state, sizeof h, hipMemcpyDeviceToHost, s));
+        IMPLI_HIP(hipStreamSynchronize(s));
+        if (h.n_eval > n || h.n_fill > n || (uint64_t)h.n_eval + h.n_fill > n) throw HipError("islands: a tile list overran its chunk");
+        evaluated += h.n_eval;
+        filled += h.n_fill;
+        samples += (int64_t)h.samples;
+        if (ev[2]) IMPLI_HIP(hipEventRecord(ev[2], s));
+        launch_raster_eval(d_prog, prog_depth, d_tab, d_mx, d_my, d_z, g, first, l0, h.n_eval, d_list, d_lmodes, d_img, d_sums, s);
+        launch_raster_fill(g, first, l0, h.n_fill, d_fill, d_img, d_sums, s);
+        if (ev[3]) IMPLI_HIP(hipEventRecord(ev[3], s));
+        launch_island_tiles(ig, nl, d_img, d_lab, d_istate, s);
+        if (ev[4]) IMPLI_HIP(hipEventRecord(ev[4], s));
+        launch_island_merge(ig, nl, d_lab, s);
+        if (ev[5]) IMPLI_HIP(hipEventRecord(ev[5], s));
+        const uint32_t rows = nl * (uint32_t)H;
+        launch_island_rows(ig, nl, d_lab, d_counts, s);
+        launch_scan_u32(d_counts, d_offsets, rows, d_scan_sums, false, s);
+        launch_slice_layer_offsets(d_offsets, (uint32_t)H, nl, d_loff, s);   // every H-th entry and the total
+        if (ev[6]) IMPLI_HIP(hipEventRecord(ev[6], s));
+        IMPLI_HIP(hipGetLastError());
+        IMPLI_HIP(hipMemcpyAsync(loff.data(), d_loff, ((size_t)nl + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        IMPLI_HIP(hipStreamSynchronize(s));
+        const uint32_t cc = loff[nl];   // the chunk's components
+        if (total + (int64_t)cc >= ((int64_t)1 << 31)) throw InputError("implisolid_islands: the result reaches 2^31 components");
+        for (uint32_t k = 0; k < nl; ++k) comp_offsets[l0 + (int)k] = total + loff[k];
+        if (cc) {
+            E.scratch(1).reserve((size_t)cc * 8 * sizeof(int32_t));
+            int32_t* d_rec = E.scratch(1).as<int32_t>();
+            if (ev[7]) IMPLI_HIP(hipEventRecord(ev[7], s));
+            launch_island_roots(ig, nl, l0, d_lab, d_offsets, cc, d_rec, s);
+            launch_island_tally(ig, nl, l0, d_img, d_carry, d_lab, d_loff, d_rec, s);
+            if (ev[8]) IMPLI_HIP(hipEventRecord(ev[8], s));
+            IMPLI_HIP(hipGetLastError());
+            g_islands.comps.resize((size_t)(total + cc) * 8);
+            IMPLI_HIP(hipMemcpyAsync(g_islands.comps.data() + 8 * (size_t)total, d_rec, (size_t)cc * 8 * sizeof(int32_t),
+                                     hipMemcpyDeviceToHost, s));
+        }
+        // without a component no pixel is solid: the tile pass has written -1 everywhere
+        if (labels)
+            IMPLI_HIP(hipMemcpyAsync(labels + (size_t)l0 * layer_px, d_lab, (size_t)nl * layer_px * sizeof(int32_t),
+                                     hipMemcpyDeviceToHost, s));
+        if (l0 + (int)nl < n_layers)
+            IMPLI_HIP(hipMemcpyAsync(d_carry, d_img + (size_t)(nl - 1) * layer_img, layer_img, hipMemcpyDeviceToDevice, s));
+        IMPLI_HIP(hipStreamSynchronize(s));   // the next chunk's launches write the buffers these copies read
+        if (ev[0]) {
+            float a = 0.f, b = 0.f, c = 0.f, d = 0.f, e = 0.f, f = 0.f;
+            IMPLI_HIP(hipEventElapsedTime(&a, ev[0], ev[1]));
+            IMPLI_HIP(hipEventElapsedTime(&b, ev[2], ev[3]));
+            IMPLI_HIP(hipEventElapsedTime(&c, ev[3], ev[4]));
+            IMPLI_HIP(hipEventElapsedTime(&d, ev[4], ev[5]));
+            IMPLI_HIP(hipEventElapsedTime(&e, ev[5], ev[6]));
+            if (cc) IMPLI_HIP(hipEventElapsedTime(&f, ev[7], ev[8]));
+            g_island_ms[0] += a + b;
+            g_island_ms[1] += c;
+            g_island_ms[2] += d;
+            g_island_ms[3] += e;
+            g_island_ms[4] += f;
+        }
+        total += cc;
+    }
+    comp_offsets[n_layers] = total;
+    IslandState hi{};
+    IMPLI_HIP(hipMemcpyAsync(&hi, d_istate, sizeof hi, hipMemcpyDeviceToHost, s));
+    IMPLI_HIP(hipStreamSynchronize(s));
+    int64_t islands = 0, area = 0;
+    for (int64_t c = 0; c < total; ++c) {
+        const int32_t* r = g_islands.comps.data() + 8 * (size_t)c;
+        islands += r[2] == 0;
+        area += r[1];
+    }
+    if (area != (int64_t)hi.solid) throw HipError("islands: the records' areas and the solid pixels disagree");
+    if (stats) {
+        stats[0] = (int64_t)n_layers * g.tpl;
+        stats[1] = evaluated;
+        stats[2] = filled;
+        stats[3] = samples;
+        stats[4] = chunks;
+        stats[5] = total;
+        stats[6] = islands;
+        stats[7] = (int64_t)hi.solid;
+    }
+    return total;
+}
+}  // namespace
+
+extern "C" {
+
+int64_t implisolid_islands(const char* shape_json, int ignore_root_matrix, const float rect[4], int width, int height,
+                           int supersample, const float* z, int n_layers, int threshold, int connectivity, int64_t* comp_offsets,
+                           int32_t* labels, int64_t stats[8]) {
+    last_error().clear();
+    g_islands.n = -1;   // whatever happens, the previous result is gone
+    if (!shape_json || !rect || !z || !comp_offsets) {
+        report("implisolid_islands: bad arguments", false);
+        return -1;
+    }
+    return guard_device([&]() -> int64_t {
+        // the request first: bad input is refused before anything is compiled or reaches the device
+        if (n_layers < 1 || n_layers > kRasterMaxLayers) throw InputError("implisolid_islands: n_layers must be in [1, 65536]");
+        for (int l = 0; l < n_layers; ++l)
+            if (!std::isfinite(z[l])) throw InputError("implisolid_islands: every z must be finite");
+        if (width < 1 || width > kRasterMaxSide || height < 1 || height > kRasterMaxSide)
+            throw InputError("implisolid_islands: width and height must be in [1, 16384]");
+        if (supersample != 1 && supersample != 2 && supersample != 4) throw InputError("implisolid_islands: supersample must be 1, 2 or 4");
+        if (threshold < 1 || threshold > supersample * supersample)
+            throw InputError("implisolid_islands: threshold must be in [1, supersample^2]");
+        if (connectivity != 4 && connectivity != 8) throw InputError("implisolid_islands: connectivity must be 4 or 8");
+        std::vector<float> mx((size_t)width * supersample), my((size_t)height * supersample);
+        raster_coords(rect, width, height, supersample, mx.data(), my.data());
+        QueryShape q(shape_json, ignore_root_matrix);
+        q.upload();
+        g_islands.n = island_layers(*q.E, q.s, q.d_prog, q.max_depth, q.d_tab, width, height, supersample, mx, my, z, n_layers,
+                                    threshold, connectivity, comp_offsets, labels, stats);
+        return g_islands.n;
+    });
+}
+
+int implisolid_islands_copy(int32_t* comps) {
+    last_error().clear();
+    if (g_islands.n < 0 || (g_islands.n > 0 && !comps)) {
+        report(g_islands.n < 0 ? "implisolid_islands_copy: no records to copy (the last implisolid_islands failed, or none ran)"
+                               : "implisolid_islands_copy: bad arguments", false);
+        return -1;
+    }
+    if (g_islands.n > 0) std::memcpy(comps, g_islands.comps.data(), (size_t)g_islands.n * 8 * sizeof(int32_t));
+    return 0;
+}
+
+int implisolid_debug_islands_ms(int enable, double ms[5]) {
+    g_island_timing = enable != 0;
+    if (ms)
+        for (int k = 0; k < 5; ++k) ms[k] = g_island_ms[k];
+    return 0;
 }
 
 }  // extern "C"

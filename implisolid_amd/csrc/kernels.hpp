@@ -183,6 +183,43 @@ void launch_raster_eval(const Program* d_prog, int prog_depth, const float* d_ta
 void launch_raster_fill(RasterGrid g, int64_t first, int l0, uint32_t n_fill, const uint32_t* d_fill, uint8_t* d_img,
                         unsigned long long* d_sums, hipStream_t s);
 
+// Islands of the layers (implisolid_islands; DESIGN "Islands of the layers", islands.hip): the connected
+// components of the solid pixels (cov >= threshold) of a chunk's image, as launch_raster_eval and
+// launch_raster_fill left it (n_layers x H rows of `pitch` bytes, padding columns zero).  d_lab: int32
+// [n_layers][H][W], the pixel's component seed (the smallest py W + px of the component) or -1 where it is
+// not solid.  The launches go on s in the order tiles, merge, rows, scan of d_counts (launch_scan_u32),
+// roots, tally; only the chunk's per-layer offsets (every H-th entry of the scan and its last) are read
+// back, between the scan and roots, to size the records.
+struct IslandGrid {
+    int W, H;            // pixels per axis
+    int ntx, nty;        // label tiles per axis
+    uint32_t pitch;      // bytes per image row
+    int threshold, connectivity;
+};
+struct IslandState {     // zeroed before the first chunk; the chunks add to it
+    unsigned long long solid;     // solid pixels
+};
+constexpr int kIslandTileW = 64, kIslandTileH = 32;   // pixels per label tile
+constexpr uint32_t kIslandMaxChunk = 1u << 18;   // (layer, raster tile) pairs per chunk: 2^26 pixels, a 256 MiB label array
+constexpr uint64_t kIslandMaxPixels = 1ull << 28;   // what one launch takes: a chunk is never less than one layer
+IslandGrid island_grid(int W, int H, uint32_t pitch, int threshold, int connectivity);
+// tiles: one block per tile; the tile-local components, labelled with their smallest index, into d_lab (every
+// pixel is written), the solid pixels onto d_state->solid
+void launch_island_tiles(IslandGrid g, uint32_t n_layers, const uint8_t* d_img, int32_t* d_lab, IslandState* d_state, hipStream_t s);
+// merge: one lane per tile-border pixel; afterwards label == own index exactly at the seeds
+void launch_island_merge(IslandGrid g, uint32_t n_layers, int32_t* d_lab, hipStream_t s);
+// rows: d_counts[layer * H + py] = the seeds in the row
+void launch_island_rows(IslandGrid g, uint32_t n_layers, const int32_t* d_lab, uint32_t* d_counts, hipStream_t s);
+// roots: the records {seed, 0, 0, INT_MAX, seed / W, -1, -1, l0 + layer} in (layer, seed) order; d_offsets: the
+// exclusive scan of d_counts, total: its last entry (nothing is written at or past it)
+void launch_island_roots(IslandGrid g, uint32_t n_layers, int l0, const int32_t* d_lab, const uint32_t* d_offsets, uint32_t total,
+                         int32_t* d_rec, hipStream_t s);
+// tally: every label pointed at its seed; area, below and the extent added to the records.  d_layer_off:
+// n_layers + 1 record offsets; below of the chunk's first layer reads d_carry (the image of layer l0 - 1, one
+// layer of the same pitch; not read when l0 == 0: every pixel of layer 0 counts as supported)
+void launch_island_tally(IslandGrid g, uint32_t n_layers, int l0, const uint8_t* d_img, const uint8_t* d_carry, int32_t* d_lab,
+                         const uint32_t* d_layer_off, int32_t* d_rec, hipStream_t s);
+
 // Rays against the solid (implisolid_raycast; DESIGN "Rays against the solid", raycast.hip): per ray the
 // first solid sample of the table d_ts (host.hpp ray_params, N + 1 floats), the bisection inside its
 // bracket and the normal there.  One chunk = n rays (3 n floats of origins and directions each); both

@@ -395,6 +395,53 @@ int implisolid_raster(const char* shape_json, int ignore_root_matrix, const floa
  * supersample, rect, or a sample that left its sub-cell) */
 int implisolid_raster_coords(const float rect[4], int width, int height, int supersample, float* mx, float* my);
 
+/* Additive: the islands of the layers on the GPU -- the connected regions of every layer image and how
+ * much of each rests on the layer below, what a resin slicer looks for first (no reference counterpart).
+ * Arguments, limits and refusals are implisolid_raster's: shape_json, ignore_root_matrix, rect, width,
+ * height, supersample s in {1, 2, 4}, z, n_layers; further
+ *   threshold     in [1, s^2]
+ *   connectivity  4 or 8
+ * cov[l][py][px] is exactly implisolid_raster's: the same sample tables, the same rule !(F < 0), -0.0 and
+ * NaN solid.  A pixel is solid iff cov >= threshold.  Two solid pixels of one layer are adjacent if they
+ * differ by one step in x or in y (connectivity 4), or by at most one step in each (connectivity 8);
+ * adjacency holds inside the image only.  A component is a class of the transitive closure of adjacency.
+ * Layers are taken in the caller's order: the layer "below" layer l is entry l - 1 of z, whatever the
+ * heights are (repeated and unsorted planes are legal, as for implisolid_raster).
+ * One record per component, eight int32 {seed, area, below, x0, y0, x1, y1, layer}:
+ *   seed            the smallest py * W + px among the component's pixels
+ *   area            its pixel count
+ *   below           the number of its pixels that are solid at the same (px, py) in layer l - 1; for l = 0
+ *                   (on the build plate) below = area
+ *   x0, y0, x1, y1  the inclusive pixel bounding box
+ * An island is a component with below == 0.
+ *   comp_offsets  n_layers + 1 entries: layer l's records are [comp_offsets[l], comp_offsets[l + 1]), in
+ *                 increasing seed
+ *   labels        (may be NULL: none) int32 [n_layers][H][W], the caller's host buffer: the pixel's component
+ *                 seed, or -1 where the pixel is not solid
+ *   stats         (may be NULL) implisolid_raster's five figures, then the components, the islands and the
+ *                 solid pixels
+ *   returns       the total number of components C, or -1 with implisolid_last_error(): implisolid_raster's
+ *                 refusals, a bad threshold or connectivity, or 2^31 components or more; bad input is refused
+ *                 before anything is compiled or reaches a device
+ * The records stay in one library-owned host slot until the next implisolid_islands call; a failed call
+ * empties the slot.  implisolid_islands_copy copies them out (8 C int32): 0, or -1 when there is nothing to
+ * copy or comps is NULL with C > 0.
+ * Everything is an integer: no result depends on the pruning level, the chunking, the order in which atomics
+ * land or the launch geometry.  (As for implisolid_raster the solidity of a NaN sample is defined, but the
+ * tests do not pin a field's NaN on the GPU.)  The image never leaves the device: per chunk only the records
+ * come down, and the labels when asked for.  Layers are processed in chunks of whole layers of at most
+ * IMPLISOLID_ISLANDS_CHUNK (layer, 16 x 16 tile) pairs (environment, read at each call; default and maximum
+ * 2^18, at least one layer's tiles): 2^26 pixels, a 64 MiB image and a 256 MiB label array.  One device, the
+ * interpreter kernels. */
+int64_t implisolid_islands(const char* shape_json, int ignore_root_matrix, const float rect[4], int width, int height,
+                           int supersample, const float* z, int n_layers, int threshold, int connectivity,
+                           int64_t* comp_offsets, int32_t* labels, int64_t stats[8]);
+int implisolid_islands_copy(int32_t* comps);
+/* diagnostics: with enable != 0 the following implisolid_islands calls time their kernels with HIP events;
+ * ms (may be NULL) = the last timed call's {raster passes, tile pass, merge pass, seed rows and scan, records
+ * and tally} milliseconds summed over its chunks, -1 before any.  Returns 0 */
+int implisolid_debug_islands_ms(int enable, double ms[5]);
+
 /* Additive: rays cast at the solid on the GPU -- per ray the first hit, its distance, the field value
  * and the normal there (no reference counterpart: the reference front end ray-casts the mesh).
  *   origins, dirs  3 n floats each, n in [0, 2^24], every float finite.  A direction need not have unit
