@@ -37,6 +37,9 @@ __device__ __forceinline__ double cube_cr(double d) {
     const double pe = __fma_rn(d, d, -p);
     const double c = p * d;
     const double ce = __fma_rn(p, d, -c);
+    // a cube that is not finite (d infinite, as heart_T is once a squared coordinate overflows float, or the
+    // product overflowing) is pow's +-Inf; the error terms are Inf - Inf there.  A NaN stays one.
+    if (!(fabs(c) <= 1.7976931348623157e308)) return c;
     return c + (ce + pe * d);
 }
 

@@ -49,8 +49,14 @@ __device__ __forceinline__ Iv sqr(Iv a) {   // a * a with the same operand
 __device__ __forceinline__ Iv sqrt_iv(Iv a) { return Iv{sqrtf(fmax2(a.lo, 0.f)), sqrtf(fmax2(a.hi, 0.f))}; }
 __device__ __forceinline__ Iv min_iv(Iv a, Iv b) { return Iv{fmin2(a.lo, b.lo), fmin2(a.hi, b.hi)}; }
 __device__ __forceinline__ Iv hull(Iv a, Iv b) { return Iv{fmin2(a.lo, b.lo), fmax2(a.hi, b.hi)}; }
-// std::min(a, b) = (b < a) ? b : a  -- as an interval simply the endpoint-wise minimum
-__device__ __forceinline__ Iv stdmin_iv(Iv a, Iv b) { return min_iv(a, b); }
+// std::min(a, b) = (b < a) ? b : a  -- as an interval the endpoint-wise minimum.  An operand with a NaN
+// endpoint (Inf - Inf inside a primitive whose terms overflow, icone's f) bounds values that may be NaN, and
+// std::min returns a NaN first operand: fmin2 would drop that endpoint and leave the other operand's finite
+// one, so the result is the whole line instead
+__device__ __forceinline__ Iv stdmin_iv(Iv a, Iv b) {
+    if (!(a.lo <= a.hi) || !(b.lo <= b.hi)) return Iv{-INFINITY, INFINITY};
+    return min_iv(a, b);
+}
 
 __device__ __forceinline__ IvD addd(IvD a, IvD b) { return IvD{a.lo + b.lo, a.hi + b.hi}; }
 __device__ __forceinline__ IvD subd(IvD a, IvD b) { return IvD{a.lo - b.hi, a.hi - b.lo}; }
@@ -377,7 +383,13 @@ __device__ __forceinline__ Iv prim_iv(int t, const float* __restrict__ tab, floa
 //   union        f = (f1 > f2) ? f1 : f2
 //   intersection f = (f1 > f2) ? f2 : f1
 //   difference   f = (f1 < -f2) ? f1 : -f2
+// An operand that is the whole line is what settle() makes of a bound that is not finite: its values may be
+// NaN, which every select above keeps in one operand position (and a NaN is solid), so neither the other
+// operand's endpoint nor a decision may stand for the result.  The node stays undecided on the whole line.
+__device__ __forceinline__ bool whole_line(Iv a) { return a.lo == -INFINITY && a.hi == INFINITY; }
+
 __device__ __forceinline__ uint32_t csg_decide(int t, Iv a, Iv b, Iv& out) {
+    if (whole_line(a) || whole_line(b)) { out = Iv{-INFINITY, INFINITY}; return PM_BOTH; }
     if (t == NT_UNION) {
         if (a.lo > b.hi) { out = a; return PM_LEFT; }
         if (a.hi <= b.lo) { out = b; return PM_RIGHT; }

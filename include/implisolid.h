@@ -273,6 +273,9 @@ double implisolid_debug_bounds_ms(int enable);
  * endpoint lies on its edge, interpolated from the edge's lower sample a to its higher sample b:
  * mu = (0.f - a) / (b - a); on an x-edge at (i, j) x = xs[i] + mu * (xs[i + 1] - xs[i]), y = ys[j]; on a
  * y-edge x = xs[i], y = ys[j] + mu * (ys[j + 1] - ys[j]); every operation rounded to float on its own.
+ * Where a or b is not finite the endpoint is what these formulas give under IEEE arithmetic, with no special
+ * case: a NaN mu (a or b NaN, or both infinite) gives a NaN coordinate, a finite a beside an infinite b gives
+ * mu = +-0 and the lower sample's coordinate.  The keys do not depend on mu, so such contours still chain.
  * Both cells that share an edge compute the same bits, so a contour's segments chain by key.
  * Order: by layer, then by tile of 16 x 16 cells row-major (ty, tx), then by cell row-major inside
  * the tile (j, i), then the table's order.  The tile size is part of the interface.
@@ -427,8 +430,7 @@ int implisolid_raster_coords(const float rect[4], int width, int height, int sup
  * empties the slot.  implisolid_islands_copy copies them out (8 C int32): 0, or -1 when there is nothing to
  * copy or comps is NULL with C > 0.
  * Everything is an integer: no result depends on the pruning level, the chunking, the order in which atomics
- * land or the launch geometry.  (As for implisolid_raster the solidity of a NaN sample is defined, but the
- * tests do not pin a field's NaN on the GPU.)  The image never leaves the device: per chunk only the records
+ * land or the launch geometry.  The image never leaves the device: per chunk only the records
  * come down, and the labels when asked for.  Layers are processed in chunks of whole layers of at most
  * IMPLISOLID_ISLANDS_CHUNK (layer, 16 x 16 tile) pairs (environment, read at each call; default and maximum
  * 2^18, at least one layer's tiles): 2^26 pixels, a 64 MiB image and a 256 MiB label array.  One device, the

@@ -4,7 +4,9 @@ Written from the definition (include/implisolid.h implisolid_slice), independent
 compute it: the float32 sample coordinates, the marching-squares cases, the interpolated endpoints,
 the segment order (layer, tile of 16 x 16 cells row-major, cell row-major, table order), the layer
 offsets, and the chaining of one layer's keys into polylines.  The field values are an argument.
-One numpy ufunc call is one IEEE operation.
+One numpy ufunc call is one IEEE operation.  A sample that is not finite gets no special case: a NaN is solid, and
+an endpoint on an edge whose mu is NaN (a or b NaN, or both infinite) or +-0 (a finite beside b infinite) is what
+the header's formula gives under IEEE arithmetic.
 """
 import numpy as np
 

@@ -6,7 +6,7 @@ sdf_3d shape, as in test_gpu_raster.py), or the bit pattern itself for the paint
 tests/island_inputs.py.  comp_offsets, the records and the labels are integers and must equal it exactly,
 whatever the pruning level skips or fills, however the layers are chunked and wherever a component crosses
 the 64 x 32-pixel tiles of the label pass.  The preconditions of the cases are asserted without a GPU in
-test_cpu_islands.py.  NaN samples are not pinned here, as for the raster query.
+test_cpu_islands.py.  NaN and infinite samples are pinned in test_gpu_nonfinite.py.
 """
 import os
 import sys
