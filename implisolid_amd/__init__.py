@@ -57,6 +57,7 @@ ABI_SYMBOLS = [
     "implisolid_mass", "implisolid_mass_mids", "implisolid_mass_physical",
     "implisolid_raster", "implisolid_raster_coords",
     "implisolid_islands", "implisolid_islands_copy", "implisolid_debug_islands_ms",
+    "implisolid_layer_distance", "implisolid_debug_layer_distance_ms",
     "implisolid_raycast", "implisolid_ray_params", "implisolid_debug_raycast_ms",
     "implisolid_ray_spans", "implisolid_ray_spans_copy", "implisolid_debug_ray_spans_ms",
 ]
@@ -218,6 +219,9 @@ def lib():
                                 ip, ctypes.POINTER(ctypes.c_int64)], ctypes.c_int64),
         "implisolid_islands_copy": ([ip], c_int),
         "implisolid_debug_islands_ms": ([c_int, ctypes.POINTER(ctypes.c_double)], c_int),
+        "implisolid_layer_distance": ([c_char_p, c_int, fp, c_int, c_int, c_int, fp, c_int, c_int, ctypes.c_int64, ip,
+                                       ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)], c_int),
+        "implisolid_debug_layer_distance_ms": ([c_int, ctypes.POINTER(ctypes.c_double)], c_int),
         "implisolid_raycast": ([c_char_p, c_int, fp, fp, ctypes.c_int64, ctypes.c_float, ctypes.c_float, c_int, c_int, ip, fp,
                                 fp, fp, ctypes.POINTER(ctypes.c_int64)], c_int),
         "implisolid_ray_params": ([ctypes.c_float, ctypes.c_float, c_int, fp], c_int),
@@ -903,6 +907,72 @@ def islands_kernel_ms(enable=True):
     call's (raster passes, tile pass, merge pass, seed rows + scan, records + tally) ms, -1 before any."""
     ms = (ctypes.c_double * 5)()
     lib().implisolid_debug_islands_ms(int(bool(enable)), ms)
+    return tuple(float(v) for v in ms)
+
+
+DIST_DTYPE = np.dtype([(name, np.int64) for name in ("solid", "widest", "widest_at", "unsupported")])
+DIST_NONE = 1 << 30
+
+
+def layer_distance(shape, rect, width, height, z, supersample=1, threshold=1, reach2=0, ignore_root_matrix=False,
+                   want_dist=True, return_stats=False):
+    """The pixel distance field of the solid's layers z = z[l] on the GPU (include/implisolid.h
+    implisolid_layer_distance).  The images are raster_layers'; a pixel is solid iff its coverage >= threshold
+    (1 .. supersample^2).  Returns (dist int32 (L, H, W) = +D2 for a solid pixel and -D2 for an empty one, D2
+    the exact squared distance in pixels to the nearest pixel of the layer of the other class, DIST_NONE
+    where the layer has none -- or None with want_dist=False; records, a structured array (DIST_DTYPE) per
+    layer of {solid = its solid pixels, widest = the largest D2 over them (0 without any), widest_at = the
+    smallest py * width + px that attains it (-1 without any), unsupported = its solid pixels whose pixel in
+    layer l - 1 has dist < -reach2 (0 for l = 0)}), and with return_stats [raster_layers' five figures, solid
+    pixels, unsupported pixels, layers whose widest is DIST_NONE]."""
+    fp, lp = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64)
+    r = _rect4(rect, "layer_distance")
+    zz = np.ascontiguousarray(z, np.float32).reshape(-1)
+    W, H, s = int(width), int(height), int(supersample)
+    if not (1 <= W <= 16384 and 1 <= H <= 16384):
+        raise ImplisolidError("layer_distance: width and height must be in [1, 16384]")
+    if not -(1 << 63) <= int(reach2) < (1 << 63):
+        raise ImplisolidError("layer_distance: reach2 must be in [0, 2^30)")
+    dist = np.empty((zz.size, H, W), np.int32) if want_dist else None
+    records = np.zeros(zz.size, DIST_DTYPE)
+    stats = (ctypes.c_int64 * 8)()
+    rc = lib().implisolid_layer_distance(_s(shape), int(bool(ignore_root_matrix)), r.ctypes.data_as(fp), W, H, s,
+                                         zz.ctypes.data_as(fp), int(zz.size), int(threshold), int(reach2),
+                                         dist.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if want_dist else None,
+                                         records.ctypes.data_as(lp), stats)
+    if rc != 0:
+        raise ImplisolidError(last_error())
+    if return_stats:
+        return dist, records, [int(v) for v in stats]
+    return dist, records
+
+
+def offset_mask(dist, r2):
+    """Host only: a layer_distance() field grown or eroded by the disc of squared radius |r2| over pixel centres.
+    r2 >= 0 grows: the pixels within sqrt(r2) of a solid pixel (dist >= -r2, and not -DIST_NONE: an empty layer
+    stays empty), the dilation of the solid mask by that disc.  r2 < 0 erodes: the solid pixels farther than
+    sqrt(-r2) from every empty one (dist > -r2), the erosion by the same disc."""
+    dist = np.asarray(dist)
+    r2 = int(r2)
+    if r2 >= 0:
+        return (dist >= -r2) & (dist != -DIST_NONE)
+    return dist > -r2
+
+
+def overhang_mask(dist, reach2):
+    """Host only: the unsupported pixels of a layer_distance() stack (L, H, W): layer l's solid pixels whose pixel
+    in layer l - 1 has dist < -reach2; layer 0 all False.  Its sums per layer are the records' unsupported."""
+    dist = np.asarray(dist)
+    out = np.zeros(dist.shape, bool)
+    out[1:] = (dist[1:] > 0) & (dist[:-1] < -int(reach2))
+    return out
+
+
+def layer_distance_kernel_ms(enable=True):
+    """Diagnostics: switch the event timing of layer_distance()'s kernels on or off; returns the last timed
+    call's (raster passes, column pass, row pass + records) ms, -1 before any."""
+    ms = (ctypes.c_double * 3)()
+    lib().implisolid_debug_layer_distance_ms(int(bool(enable)), ms)
     return tuple(float(v) for v in ms)
 
 

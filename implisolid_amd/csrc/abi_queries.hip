@@ -1,5 +1,5 @@
 // abi_queries.hip -- the field queries of the C ABI: the interval probes, bounds, slices, layer images and
-// their islands, rays and mass properties.  Each entry validates its request, compiles the shape (QueryShape), puts it
+// their islands and distance fields, rays and mass properties.  Each entry validates its request, compiles the shape (QueryShape), puts it
 // on the device and runs its passes; the scaffolding is abi_common.hpp's.
 #include <cmath>
 #include <cstring>
@@ -745,6 +745,182 @@ int implisolid_debug_islands_ms(int enable, double ms[5]) {
     g_island_timing = enable != 0;
     if (ms)
         for (int k = 0; k < 5; ++k) ms[k] = g_island_ms[k];
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- pixel distance field of the layers (implisolid_layer_distance) --------------------------------------
+// Layers go through raster.hip's passes and then distance.hip's in chunks of whole layers, at most
+// kDistMaxChunk (layer, raster tile) pairs each: the image zeroed, classify, a read-back of the two lists'
+// lengths, evaluate, fill; then columns, rows, unsupported, and the copy of the distances, when asked for,
+// into the caller's array.  The image stays on the device; the last distance layer of a chunk is copied to a
+// carry buffer for the first layer of the next.  The records add up on the device over the chunks and come
+// down once.  E lends its scratch: 9 - 13 and 15 as raster_layers takes them, 0 the distances, 1 the records,
+// 2 the carried layer.
+namespace {
+bool g_dist_timing = false;      // implisolid_debug_layer_distance_ms: HIP events around the launches
+double g_dist_ms[3] = {-1.0, -1.0, -1.0};
+
+void distance_layers(Engine& E, hipStream_t s, const Program* d_prog, int prog_depth, const float* d_tab, int W, int H, int ss,
+                     const std::vector<float>& mx, const std::vector<float>& my, const float* z, int n_layers, int threshold,
+                     int64_t reach2, int32_t* dist, int64_t* layer_rec, int64_t stats[8]) {
+    RasterGrid g;
+    g.W = W;
+    g.H = H;
+    g.s = ss;
+    g.ntx = (W + kRasterTile - 1) / kRasterTile;
+    g.nty = (H + kRasterTile - 1) / kRasterTile;
+    g.tpl = (uint32_t)g.ntx * (uint32_t)g.nty;
+    g.pitch = (uint32_t)(kRasterTile * g.ntx);
+    const DistGrid dg = dist_grid(W, H, g.pitch, threshold);
+    const uint32_t chunk_layers = cabi::chunk_layers("IMPLISOLID_DISTANCE_CHUNK", kDistMaxChunk, g.tpl, n_layers);
+    const uint32_t cap = chunk_layers * g.tpl;   // items per chunk: <= kDistMaxChunk, or one layer's
+    const bool prune = Engine::pruning() >= 1;
+    const size_t layer_img = (size_t)H * g.pitch, layer_px = (size_t)H * (size_t)W;
+    // every reserve before any pointer is taken: a DevBuf that grows moves
+    E.scratch(10).reserve(kStateBytes + (mx.size() + my.size() + (size_t)n_layers) * sizeof(float));
+    E.scratch(11).reserve((size_t)cap * sizeof(uint32_t));                 // evaluate list
+    E.scratch(12).reserve((size_t)cap * sizeof(uint32_t));                 // fill list
+    E.scratch(13).reserve((size_t)cap * sizeof(uint64_t));                 // the listed tiles' modes
+    E.scratch(9).reserve((size_t)n_layers * sizeof(uint64_t));             // layer sums (the raster passes add them)
+    E.scratch(15).reserve((size_t)chunk_layers * layer_img);               // the chunk's image
+    E.scratch(0).reserve((size_t)chunk_layers * layer_px * sizeof(int32_t));   // distances
+    E.scratch(1).reserve((size_t)n_layers * 4 * sizeof(uint64_t));         // records
+    if (n_layers > (int)chunk_layers) E.scratch(2).reserve(layer_px * sizeof(int32_t));   // the carried layer
+    RasterState* d_state = E.scratch(10).as<RasterState>();
+    float* d_mx = behind_state<RasterState>(E.scratch(10));
+    float* d_my = d_mx + mx.size();
+    float* d_z = d_my + my.size();
+    uint32_t* d_list = E.scratch(11).as<uint32_t>();
+    uint32_t* d_fill = E.scratch(12).as<uint32_t>();
+    uint64_t* d_lmodes = E.scratch(13).as<uint64_t>();
+    unsigned long long* d_sums = E.scratch(9).as<unsigned long long>();
+    uint8_t* d_img = E.scratch(15).as<uint8_t>();
+    int32_t* d_dist = E.scratch(0).as<int32_t>();
+    unsigned long long* d_rec = E.scratch(1).as<unsigned long long>();
+    int32_t* d_carry = n_layers > (int)chunk_layers ? E.scratch(2).as<int32_t>() : nullptr;
+    IMPLI_HIP(hipMemcpyAsync(d_mx, mx.data(), mx.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    IMPLI_HIP(hipMemcpyAsync(d_my, my.data(), my.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    IMPLI_HIP(hipMemcpyAsync(d_z, z, (size_t)n_layers * sizeof(float), hipMemcpyHostToDevice, s));
+    IMPLI_HIP(hipMemsetAsync(d_sums, 0, (size_t)n_layers * sizeof(uint64_t), s));
+    IMPLI_HIP(hipMemsetAsync(d_rec, 0, (size_t)n_layers * 4 * sizeof(uint64_t), s));
+    EventSet<7> ev;
+    if (g_dist_timing) {
+        ev.create();
+        for (double& m : g_dist_ms) m = 0.0;
+    }
+    int64_t evaluated = 0, filled = 0, samples = 0, chunks = 0;
+    for (int l0 = 0; l0 < n_layers; l0 += (int)chunk_layers, ++chunks) {
+        const uint32_t nl = (uint32_t)std::min<int64_t>(chunk_layers, n_layers - l0);
+        const uint32_t n = nl * g.tpl;
+        const int64_t first = (int64_t)l0 * g.tpl;
+        IMPLI_HIP(hipMemsetAsync(d_state, 0, sizeof(RasterState), s));
+        IMPLI_HIP(hipMemsetAsync(d_img, 0, (size_t)nl * layer_img, s));
+        if (ev[0]) IMPLI_HIP(hipEventRecord(ev[0], s));
+        launch_raster_classify(d_prog, prog_depth, d_tab, E.tab_range(), d_mx, d_my, d_z, g, first, n, prune, d_list, d_lmodes,
+                               d_fill, d_state, s);
+        if (ev[1]) IMPLI_HIP(hipEventRecord(ev[1], s));
+        IMPLI_HIP(hipGetLastError());
+        RasterState h{};
+        IMPLI_HIP(hipMemcpyAsync(&h, d_state, sizeof h, hipMemcpyDeviceToHost, s));
+        IMPLI_HIP(hipStreamSynchronize(s));
+        if (h.n_eval > n || h.n_fill > n || (uint64_t)h.n_eval + h.n_fill > n) throw HipError("distance: a tile list overran its chunk");
+        evaluated += h.n_eval;
+        filled += h.n_fill;
+        samples += (int64_t)h.samples;
+        if (ev[2]) IMPLI_HIP(hipEventRecord(ev[2], s));
+        launch_raster_eval(d_prog, prog_depth, d_tab, d_mx, d_my, d_z, g, first, l0, h.n_eval, d_list, d_lmodes, d_img, d_sums, s);
+        launch_raster_fill(g, first, l0, h.n_fill, d_fill, d_img, d_sums, s);
+        if (ev[3]) IMPLI_HIP(hipEventRecord(ev[3], s));
+        launch_distance_columns(dg, nl, d_img, d_dist, s);
+        if (ev[4]) IMPLI_HIP(hipEventRecord(ev[4], s));
+        launch_distance_rows(dg, nl, l0, d_dist, d_rec, s);
+        launch_distance_unsupported(dg, nl, l0, reach2, d_dist, d_carry, d_rec, s);
+        if (ev[5]) IMPLI_HIP(hipEventRecord(ev[5], s));
+        IMPLI_HIP(hipGetLastError());
+        if (dist)
+            IMPLI_HIP(hipMemcpyAsync(dist + (size_t)l0 * layer_px, d_dist, (size_t)nl * layer_px * sizeof(int32_t),
+                                     hipMemcpyDeviceToHost, s));
+        if (l0 + (int)nl < n_layers)
+            IMPLI_HIP(hipMemcpyAsync(d_carry, d_dist + (size_t)(nl - 1) * layer_px, layer_px * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+        IMPLI_HIP(hipStreamSynchronize(s));   // the next chunk's launches write the buffers these copies read
+        if (ev[0]) {
+            float a = 0.f, b = 0.f, c = 0.f, d = 0.f;
+            IMPLI_HIP(hipEventElapsedTime(&a, ev[0], ev[1]));
+            IMPLI_HIP(hipEventElapsedTime(&b, ev[2], ev[3]));
+            IMPLI_HIP(hipEventElapsedTime(&c, ev[3], ev[4]));
+            IMPLI_HIP(hipEventElapsedTime(&d, ev[4], ev[5]));
+            g_dist_ms[0] += a + b;
+            g_dist_ms[1] += c;
+            g_dist_ms[2] += d;
+        }
+    }
+    std::vector<unsigned long long> rec((size_t)n_layers * 4);
+    IMPLI_HIP(hipMemcpyAsync(rec.data(), d_rec, rec.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    IMPLI_HIP(hipStreamSynchronize(s));
+    int64_t solid = 0, unsupported = 0, whole = 0;
+    for (int l = 0; l < n_layers; ++l) {
+        const unsigned long long* r = rec.data() + 4 * (size_t)l;
+        if ((r[0] == 0) != (r[1] == 0) || r[2] > r[0]) throw HipError("distance: a layer's record contradicts itself");
+        int64_t* o = layer_rec + 4 * (size_t)l;
+        o[0] = (int64_t)r[0];
+        o[1] = (int64_t)(r[1] >> 32);
+        o[2] = r[1] ? (int64_t)(0xFFFFFFFFull - (r[1] & 0xFFFFFFFFull)) : -1;
+        o[3] = (int64_t)r[2];
+        solid += o[0];
+        unsupported += o[3];
+        whole += o[1] == (int64_t)kDistNone;
+    }
+    if (stats) {
+        stats[0] = (int64_t)n_layers * g.tpl;
+        stats[1] = evaluated;
+        stats[2] = filled;
+        stats[3] = samples;
+        stats[4] = chunks;
+        stats[5] = solid;
+        stats[6] = unsupported;
+        stats[7] = whole;
+    }
+}
+}  // namespace
+
+extern "C" {
+
+int implisolid_layer_distance(const char* shape_json, int ignore_root_matrix, const float rect[4], int width, int height,
+                              int supersample, const float* z, int n_layers, int threshold, int64_t reach2, int32_t* dist,
+                              int64_t* layer_rec, int64_t stats[8]) {
+    last_error().clear();
+    if (!shape_json || !rect || !z || !layer_rec) {
+        report("implisolid_layer_distance: bad arguments", false);
+        return -1;
+    }
+    return guard_device([&] {
+        // the request first: bad input is refused before anything is compiled or reaches the device
+        if (n_layers < 1 || n_layers > kRasterMaxLayers) throw InputError("implisolid_layer_distance: n_layers must be in [1, 65536]");
+        for (int l = 0; l < n_layers; ++l)
+            if (!std::isfinite(z[l])) throw InputError("implisolid_layer_distance: every z must be finite");
+        if (width < 1 || width > kRasterMaxSide || height < 1 || height > kRasterMaxSide)
+            throw InputError("implisolid_layer_distance: width and height must be in [1, 16384]");
+        if (supersample != 1 && supersample != 2 && supersample != 4)
+            throw InputError("implisolid_layer_distance: supersample must be 1, 2 or 4");
+        if (threshold < 1 || threshold > supersample * supersample)
+            throw InputError("implisolid_layer_distance: threshold must be in [1, supersample^2]");
+        if (reach2 < 0 || reach2 >= (int64_t)kDistNone) throw InputError("implisolid_layer_distance: reach2 must be in [0, 2^30)");
+        std::vector<float> mx((size_t)width * supersample), my((size_t)height * supersample);
+        raster_coords(rect, width, height, supersample, mx.data(), my.data());
+        QueryShape q(shape_json, ignore_root_matrix);
+        q.upload();
+        distance_layers(*q.E, q.s, q.d_prog, q.max_depth, q.d_tab, width, height, supersample, mx, my, z, n_layers, threshold, reach2,
+                        dist, layer_rec, stats);
+        return 0;
+    });
+}
+
+int implisolid_debug_layer_distance_ms(int enable, double ms[3]) {
+    g_dist_timing = enable != 0;
+    if (ms)
+        for (int k = 0; k < 3; ++k) ms[k] = g_dist_ms[k];
     return 0;
 }
 

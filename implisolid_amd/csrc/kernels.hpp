@@ -220,6 +220,34 @@ void launch_island_roots(IslandGrid g, uint32_t n_layers, int l0, const int32_t*
 void launch_island_tally(IslandGrid g, uint32_t n_layers, int l0, const uint8_t* d_img, const uint8_t* d_carry, int32_t* d_lab,
                          const uint32_t* d_layer_off, int32_t* d_rec, hipStream_t s);
 
+// Pixel distance field of the layers (implisolid_layer_distance; DESIGN "Distance field of the layers",
+// distance.hip): the exact squared Euclidean distance of every pixel of a chunk's image (as launch_raster_eval
+// and launch_raster_fill left it) to the nearest pixel of the other class (solid: cov >= threshold), signed
+// by the pixel's own class.  d_dist: int32 [n_layers][H][W].  d_rec: four u64 per layer of the call {solid,
+// key, unsupported, unused}, zeroed before the first chunk; key = (D2 << 32) | (0xFFFFFFFF - index) of the
+// widest solid pixel, 0 when the layer has none.  The launches go on s in the order columns, rows, unsupported.
+struct DistGrid {
+    int W, H;            // pixels per axis
+    uint32_t pitch;      // bytes per image row
+    int threshold;
+};
+constexpr int kDistNone = 1 << 30;                // no pixel of the other class in the layer
+constexpr int kDistFar = 32768;                   // the column pass's "none in this column": kDistFar^2 == kDistNone
+constexpr uint32_t kDistMaxChunk = 1u << 18;      // (layer, raster tile) pairs per chunk, as kIslandMaxChunk
+constexpr uint64_t kDistMaxPixels = 1ull << 28;   // what one launch takes: a chunk is never less than one layer
+DistGrid dist_grid(int W, int H, uint32_t pitch, int threshold);
+// columns: one lane per (layer, column); d_dist = the signed vertical distance to the nearest pixel of the
+// other class in the column (+ solid, - empty), magnitude kDistFar where the column holds none
+void launch_distance_columns(DistGrid g, uint32_t n_layers, const uint8_t* d_img, int32_t* d_dist, hipStream_t s);
+// rows: one block per (layer, row); d_dist = +-D2 in place, the layer's solid pixels and widest key onto d_rec
+// (layer l0 + ll of the call)
+void launch_distance_rows(DistGrid g, uint32_t n_layers, int l0, int32_t* d_dist, unsigned long long* d_rec, hipStream_t s);
+// unsupported: the solid pixels of every layer but the call's first whose pixel in the distance layer below is
+// < -reach2, onto d_rec.  Below the chunk's first layer lies d_carry (the last distance layer of the chunk
+// before, H x W; not read when l0 == 0)
+void launch_distance_unsupported(DistGrid g, uint32_t n_layers, int l0, int64_t reach2, const int32_t* d_dist, const int32_t* d_carry,
+                                 unsigned long long* d_rec, hipStream_t s);
+
 // Rays against the solid (implisolid_raycast; DESIGN "Rays against the solid", raycast.hip): per ray the
 // first solid sample of the table d_ts (host.hpp ray_params, N + 1 floats), the bisection inside its
 // bracket and the normal there.  One chunk = n rays (3 n floats of origins and directions each); both

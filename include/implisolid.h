@@ -444,6 +444,48 @@ int implisolid_islands_copy(int32_t* comps);
  * and tally} milliseconds summed over its chunks, -1 before any.  Returns 0 */
 int implisolid_debug_islands_ms(int enable, double ms[5]);
 
+/* Additive: the pixel distance field of the layers on the GPU -- the exact squared Euclidean distance
+ * transform of every layer image, what XY compensation, wall thickness and overhang checks threshold (no
+ * reference counterpart).  Arguments, limits and refusals are implisolid_islands': shape_json,
+ * ignore_root_matrix, rect, width, height in [1, 16384], supersample s in {1, 2, 4}, z, n_layers, threshold
+ * in [1, s^2]; further
+ *   reach2        in [0, 2^30): the squared self-supporting reach, in pixels
+ * cov[l][py][px] is exactly implisolid_raster's.  A pixel is solid iff cov >= threshold.  Only the pixels of
+ * the image exist: there is no implicit border of either class.
+ * For pixel p of layer l let O be the pixels of layer l whose solidity differs from p's:
+ *   D2(p) = min over q in O of (px - qx)^2 + (py - qy)^2, and NONE = 2^30 when O is empty (the largest real
+ *           value, 2 * 16383^2, is below it)
+ *   dist[l][py][px] = +D2 for a solid pixel, -D2 for an empty one
+ * so dist is never 0, dist > 0 is exactly the solid mask and |dist| >= 1.
+ *   dist       (may be NULL: only the records come down) int32 [n_layers][H][W], the caller's host buffer
+ *   layer_rec  four int64 per layer {solid, widest, widest_at, unsupported}:
+ *     solid        the layer's solid pixels
+ *     widest       the largest D2 over the solid pixels: 0 when there are none, NONE for an all-solid layer;
+ *                  the squared radius, in pixels, of the largest inscribed disc, up to pixel sampling
+ *     widest_at    the smallest py * W + px that attains it, -1 when there is none
+ *     unsupported  for l >= 1 the solid pixels of layer l with dist[l - 1] < -reach2 at the same (px, py): the
+ *                  pixel is empty below and no solid pixel of the layer below lies within sqrt(reach2)
+ *                  pixels; 0 for l = 0.  "Below" is entry l - 1 of z, as for implisolid_islands; an empty
+ *                  layer below makes every solid pixel unsupported.  reach2 = 0 counts the pixels with
+ *                  nothing straight below
+ *   stats      (may be NULL) implisolid_raster's five figures, then the solid pixels, the unsupported pixels
+ *              and the layers whose widest is NONE
+ *   returns    0, or -1 with implisolid_last_error(): implisolid_raster's refusals, a bad threshold or reach2,
+ *              or layer_rec NULL; bad input is refused before anything is compiled or reaches a device
+ * There is no library-owned slot.  Everything is an integer: no result depends on the pruning level, the
+ * chunking, the order in which atomics land or the launch geometry.  The image never leaves the device.
+ * Layers are processed in chunks of whole layers of at most IMPLISOLID_DISTANCE_CHUNK (layer, 16 x 16 tile)
+ * pairs (environment, read at each call; default and maximum 2^18, at least one layer's tiles): 2^26 pixels,
+ * a 64 MiB image and a 256 MiB distance array; the last distance layer of a chunk stays on the device for the
+ * first layer of the next.  One device, the interpreter kernels. */
+int implisolid_layer_distance(const char* shape_json, int ignore_root_matrix, const float rect[4], int width, int height,
+                              int supersample, const float* z, int n_layers, int threshold, int64_t reach2,
+                              int32_t* dist, int64_t* layer_rec, int64_t stats[8]);
+/* diagnostics: with enable != 0 the following implisolid_layer_distance calls time their kernels with HIP
+ * events; ms (may be NULL) = the last timed call's {raster passes, column pass, row pass and records}
+ * milliseconds summed over its chunks, -1 before any.  Returns 0 */
+int implisolid_debug_layer_distance_ms(int enable, double ms[3]);
+
 /* Additive: rays cast at the solid on the GPU -- per ray the first hit, its distance, the field value
  * and the normal there (no reference counterpart: the reference front end ray-casts the mesh).
  *   origins, dirs  3 n floats each, n in [0, 2^24], every float finite.  A direction need not have unit
