@@ -744,6 +744,16 @@ def _rect4(rect, what):
     return r
 
 
+def _layer_args(what, rect, z, width, height, supersample):
+    """What raster_layers, layer_islands and layer_distance do with their arguments first: (rect, z, W, H, s)."""
+    r = _rect4(rect, what)
+    zz = np.ascontiguousarray(z, np.float32).reshape(-1)
+    W, H, s = int(width), int(height), int(supersample)
+    if not (1 <= W <= 16384 and 1 <= H <= 16384):
+        raise ImplisolidError("%s: width and height must be in [1, 16384]" % what)
+    return r, zz, W, H, s
+
+
 def slice_layers(shape, rect, resolution, z, ignore_root_matrix=False, return_stats=False):
     """The solid's outlines on the planes z = z[l], by marching squares on the GPU over `resolution`
     cells per axis of rect {xmin, xmax, ymin, ymax} (include/implisolid.h implisolid_slice).  Returns
@@ -825,11 +835,7 @@ def raster_layers(shape, rect, width, height, z, supersample=1, ignore_root_matr
     tiles filled whole, samples evaluated, chunks].  want_cov=False passes cov = NULL: cov is None and
     only the sums (and stats) are produced."""
     fp = ctypes.POINTER(ctypes.c_float)
-    r = _rect4(rect, "raster_layers")
-    zz = np.ascontiguousarray(z, np.float32).reshape(-1)
-    W, H, s = int(width), int(height), int(supersample)
-    if not (1 <= W <= 16384 and 1 <= H <= 16384):
-        raise ImplisolidError("raster_layers: width and height must be in [1, 16384]")
+    r, zz, W, H, s = _layer_args("raster_layers", rect, z, width, height, supersample)
     cov = np.empty((zz.size, H, W), np.uint8) if want_cov else None
     sums = np.zeros(zz.size, np.int64)
     stats = (ctypes.c_int64 * 5)()
@@ -872,11 +878,7 @@ def layer_islands(shape, rect, width, height, z, supersample=1, threshold=1, con
     (L, H, W) = the pixel's seed or -1, and with return_stats [raster_layers' five figures, components, islands,
     solid pixels]."""
     fp, lp = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64)
-    r = _rect4(rect, "layer_islands")
-    zz = np.ascontiguousarray(z, np.float32).reshape(-1)
-    W, H, s = int(width), int(height), int(supersample)
-    if not (1 <= W <= 16384 and 1 <= H <= 16384):
-        raise ImplisolidError("layer_islands: width and height must be in [1, 16384]")
+    r, zz, W, H, s = _layer_args("layer_islands", rect, z, width, height, supersample)
     offs = np.zeros(zz.size + 1, np.int64)
     labels = np.empty((zz.size, H, W), np.int32) if want_labels else None
     stats = (ctypes.c_int64 * 8)()
@@ -926,11 +928,7 @@ def layer_distance(shape, rect, width, height, z, supersample=1, threshold=1, re
     layer l - 1 has dist < -reach2 (0 for l = 0)}), and with return_stats [raster_layers' five figures, solid
     pixels, unsupported pixels, layers whose widest is DIST_NONE]."""
     fp, lp = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64)
-    r = _rect4(rect, "layer_distance")
-    zz = np.ascontiguousarray(z, np.float32).reshape(-1)
-    W, H, s = int(width), int(height), int(supersample)
-    if not (1 <= W <= 16384 and 1 <= H <= 16384):
-        raise ImplisolidError("layer_distance: width and height must be in [1, 16384]")
+    r, zz, W, H, s = _layer_args("layer_distance", rect, z, width, height, supersample)
     if not -(1 << 63) <= int(reach2) < (1 << 63):
         raise ImplisolidError("layer_distance: reach2 must be in [0, 2^30)")
     dist = np.empty((zz.size, H, W), np.int32) if want_dist else None

@@ -1,6 +1,8 @@
 // abi_queries.hip -- the field queries of the C ABI: the interval probes, bounds, slices, layer images and
-// their islands and distance fields, rays and mass properties.  Each entry validates its request, compiles the shape (QueryShape), puts it
-// on the device and runs its passes; the scaffolding is abi_common.hpp's.
+// their islands and distance fields, rays and mass properties.  Each entry validates its request, compiles
+// the shape (QueryShape), puts it on the device and runs its passes; the scaffolding is abi_common.hpp's.
+// The three layer queries share their request (LayerRequest) and the passes that make a chunk's image
+// (LayerImages): each reads as what it does with the image.  The two ray queries share ray_request.
 #include <cmath>
 #include <cstring>
 #include <stdexcept>
@@ -381,12 +383,148 @@ int64_t implisolid_slice_loops(const uint32_t* keys, int64_t n_segments, int64_t
 
 }  // extern "C"
 
+// ---- what the layer queries share: the request and the image (raster, islands, layer distance) ------------
+namespace {
+// The request of implisolid_<entry>, refused in this order: n_layers, z, width / height, supersample, threshold
+// (an entry without one passes 1, which every supersample admits).  The entry's own checks follow, then
+// sample(): the rect, which fills mx and my.
+struct LayerRequest {
+    const float* rect;
+    int W, H, ss;
+    const float* z;
+    int n_layers;
+    std::vector<float> mx, my;
+    LayerRequest(const std::string& entry, const float* rect, int width, int height, int supersample, const float* z, int n_layers,
+                 int threshold = 1)
+        : rect(rect), W(width), H(height), ss(supersample), z(z), n_layers(n_layers) {
+        const std::string who = "implisolid_" + entry + ": ";
+        if (n_layers < 1 || n_layers > kRasterMaxLayers) throw InputError(who + "n_layers must be in [1, 65536]");
+        for (int l = 0; l < n_layers; ++l)
+            if (!std::isfinite(z[l])) throw InputError(who + "every z must be finite");
+        if (W < 1 || W > kRasterMaxSide || H < 1 || H > kRasterMaxSide) throw InputError(who + "width and height must be in [1, 16384]");
+        if (ss != 1 && ss != 2 && ss != 4) throw InputError(who + "supersample must be 1, 2 or 4");
+        if (threshold < 1 || threshold > ss * ss) throw InputError(who + "threshold must be in [1, supersample^2]");
+    }
+    void sample() {
+        mx.resize((size_t)W * ss);
+        my.resize((size_t)H * ss);
+        raster_coords(rect, W, H, ss, mx.data(), my.data());
+    }
+};
+
+// The layers' images, chunk by chunk.  Layers go through raster.hip's passes in chunks of whole layers, at most
+// max_items (layer, tile) items each (chunk_env may lower that).  next() enqueues a chunk's head: the state
+// block and the image zeroed, classify, a read-back of the two lists' lengths (they size the grids), evaluate,
+// fill.  It leaves layers [l0, l0 + nl) in d_img, H rows of g.pitch bytes each, and their sums added to d_sums.
+// E lends its scratch: 10 the state block with mx, my and z behind it, 11 the evaluate list, 12 the fill list,
+// 13 the listed tiles' modes, 9 the layer sums, 15 the chunk's image.  Every reserve before any pointer is
+// taken (a DevBuf that grows moves): these are made here, and a query reserves only buffers of its own.
+struct LayerImages {
+    const QueryShape& q;
+    const LayerRequest& r;
+    const char* who;                 // the query's name in the overrun message
+    RasterGrid g;
+    uint32_t chunk_layers;
+    size_t layer_img, layer_px;      // a layer's bytes in d_img, its pixels
+    RasterState* d_state;
+    float *d_mx, *d_my, *d_z;
+    uint32_t *d_list, *d_fill;
+    uint64_t* d_lmodes;
+    unsigned long long* d_sums;
+    uint8_t* d_img;                  // null where no image is wanted (raster with cov == NULL)
+    int l0 = 0;                      // the chunk next() has enqueued
+    uint32_t nl = 0;
+    int64_t evaluated = 0, filled = 0, samples = 0, chunks = 0;
+    EventSet<4> ev;                  // with timing: around classify, and around evaluate + fill
+
+    LayerImages(const QueryShape& q, const LayerRequest& r, const char* who, const char* chunk_env, uint64_t max_items,
+                bool want_img, bool timing)
+        : q(q), r(r), who(who) {
+        Engine& E = *q.E;
+        g.W = r.W;
+        g.H = r.H;
+        g.s = r.ss;
+        g.ntx = (r.W + kRasterTile - 1) / kRasterTile;
+        g.nty = (r.H + kRasterTile - 1) / kRasterTile;
+        g.tpl = (uint32_t)g.ntx * (uint32_t)g.nty;   // <= 2^20
+        g.pitch = (uint32_t)(kRasterTile * g.ntx);
+        chunk_layers = cabi::chunk_layers(chunk_env, max_items, g.tpl, r.n_layers);
+        const uint32_t cap = chunk_layers * g.tpl;   // items per chunk: <= max_items, or one layer's
+        const size_t n_layers = (size_t)r.n_layers;
+        layer_img = (size_t)r.H * g.pitch;
+        layer_px = (size_t)r.H * (size_t)r.W;
+        E.scratch(10).reserve(kStateBytes + (r.mx.size() + r.my.size() + n_layers) * sizeof(float));
+        E.scratch(11).reserve((size_t)cap * sizeof(uint32_t));
+        E.scratch(12).reserve((size_t)cap * sizeof(uint32_t));
+        E.scratch(13).reserve((size_t)cap * sizeof(uint64_t));
+        E.scratch(9).reserve(n_layers * sizeof(uint64_t));
+        if (want_img) E.scratch(15).reserve((size_t)chunk_layers * layer_img);
+        d_state = E.scratch(10).as<RasterState>();
+        d_mx = behind_state<RasterState>(E.scratch(10));
+        d_my = d_mx + r.mx.size();
+        d_z = d_my + r.my.size();
+        d_list = E.scratch(11).as<uint32_t>();
+        d_fill = E.scratch(12).as<uint32_t>();
+        d_lmodes = E.scratch(13).as<uint64_t>();
+        d_sums = E.scratch(9).as<unsigned long long>();
+        d_img = want_img ? E.scratch(15).as<uint8_t>() : nullptr;
+        IMPLI_HIP(hipMemcpyAsync(d_mx, r.mx.data(), r.mx.size() * sizeof(float), hipMemcpyHostToDevice, q.s));
+        IMPLI_HIP(hipMemcpyAsync(d_my, r.my.data(), r.my.size() * sizeof(float), hipMemcpyHostToDevice, q.s));
+        IMPLI_HIP(hipMemcpyAsync(d_z, r.z, n_layers * sizeof(float), hipMemcpyHostToDevice, q.s));
+        IMPLI_HIP(hipMemsetAsync(d_sums, 0, n_layers * sizeof(uint64_t), q.s));
+        if (timing) ev.create();
+    }
+
+    // The next chunk's head, enqueued; false after the last.  It synchronises the stream once, at the read-back:
+    // whatever the query enqueued for the chunk before has finished when it returns.
+    bool next() {
+        l0 += (int)nl;
+        if (l0 >= r.n_layers) return false;
+        nl = (uint32_t)std::min<int64_t>(chunk_layers, r.n_layers - l0);
+        const uint32_t n = nl * g.tpl;
+        const int64_t first = (int64_t)l0 * g.tpl;
+        hipStream_t s = q.s;
+        IMPLI_HIP(hipMemsetAsync(d_state, 0, sizeof(RasterState), s));
+        if (d_img) IMPLI_HIP(hipMemsetAsync(d_img, 0, (size_t)nl * layer_img, s));   // ordered behind the last chunk's copies
+        if (ev[0]) IMPLI_HIP(hipEventRecord(ev[0], s));
+        launch_raster_classify(q.d_prog, q.max_depth, q.d_tab, q.E->tab_range(), d_mx, d_my, d_z, g, first, n,
+                               Engine::pruning() >= 1, d_list, d_lmodes, d_fill, d_state, s);
+        if (ev[1]) IMPLI_HIP(hipEventRecord(ev[1], s));
+        IMPLI_HIP(hipGetLastError());
+        RasterState h{};
+        IMPLI_HIP(hipMemcpyAsync(&h, d_state, sizeof h, hipMemcpyDeviceToHost, s));
+        IMPLI_HIP(hipStreamSynchronize(s));
+        if (h.n_eval > n || h.n_fill > n || (uint64_t)h.n_eval + h.n_fill > n)
+            throw HipError(std::string(who) + ": a tile list overran its chunk");
+        evaluated += h.n_eval;
+        filled += h.n_fill;
+        samples += (int64_t)h.samples;
+        if (ev[2]) IMPLI_HIP(hipEventRecord(ev[2], s));
+        launch_raster_eval(q.d_prog, q.max_depth, q.d_tab, d_mx, d_my, d_z, g, first, l0, h.n_eval, d_list, d_lmodes, d_img, d_sums, s);
+        launch_raster_fill(g, first, l0, h.n_fill, d_fill, d_img, d_sums, s);
+        if (ev[3]) IMPLI_HIP(hipEventRecord(ev[3], s));
+        ++chunks;
+        return true;
+    }
+    // with timing, after a synchronisation behind the chunk's fill: the ms of its raster passes
+    float raster_ms() const {
+        float a = 0.f, b = 0.f;
+        IMPLI_HIP(hipEventElapsedTime(&a, ev[0], ev[1]));
+        IMPLI_HIP(hipEventElapsedTime(&b, ev[2], ev[3]));
+        return a + b;
+    }
+    // stats[0..4] of every layer query: pairs, tiles evaluated, tiles filled, samples, chunks
+    void stats(int64_t* out) const {
+        const int64_t v[5] = {(int64_t)r.n_layers * g.tpl, evaluated, filled, samples, chunks};
+        std::copy(v, v + 5, out);
+    }
+};
+}  // namespace
+
 // ---- layer images of the solid (implisolid_raster) -------------------------------------------------
-// Layers go through raster.hip's passes in chunks of whole layers, at most kRasterMaxChunk (layer, tile)
-// items each: the image zeroed, classify, a read-back of the two lists' lengths (they size the grids),
-// evaluate, fill, and the pitched copy of the chunk's image into a pinned staging slot with the chunk's
-// layer sums behind it.  There are two slots: the host copies a chunk from its slot into the caller's
-// buffer while the device works on the next one.  E lends its scratch.
+// Per chunk, behind LayerImages' head: the pitched copy of the chunk's image into a pinned staging slot, with
+// the chunk's layer sums behind it.  There are two slots: the host copies a chunk from its slot into the
+// caller's buffer while the device works on the next one.
 namespace {
 struct RasterStage {             // the staging slots, kept until exit (grow-only)
     PinnedVec<uint8_t> img[2];
@@ -394,45 +532,13 @@ struct RasterStage {             // the staging slots, kept until exit (grow-onl
 };
 RasterStage g_raster;
 
-void raster_layers(Engine& E, hipStream_t s, const Program* d_prog, int prog_depth, const float* d_tab, int W, int H, int ss,
-                   const std::vector<float>& mx, const std::vector<float>& my, const float* z, int n_layers, uint8_t* cov,
-                   int64_t* layer_sum, int64_t stats[5]) {
-    RasterGrid g;
-    g.W = W;
-    g.H = H;
-    g.s = ss;
-    g.ntx = (W + kRasterTile - 1) / kRasterTile;
-    g.nty = (H + kRasterTile - 1) / kRasterTile;
-    g.tpl = (uint32_t)g.ntx * (uint32_t)g.nty;   // <= 2^20
-    g.pitch = (uint32_t)(kRasterTile * g.ntx);
-    const uint32_t chunk_layers = cabi::chunk_layers("IMPLISOLID_RASTER_CHUNK", kRasterMaxChunk, g.tpl, n_layers);
-    const uint32_t cap = chunk_layers * g.tpl;   // items per chunk, <= kRasterMaxChunk
-    const bool prune = Engine::pruning() >= 1;
-    const size_t layer_img = (size_t)H * g.pitch, layer_out = (size_t)H * (size_t)W;
-    // every reserve before any pointer is taken: a DevBuf that grows moves
-    E.scratch(10).reserve(kStateBytes + (mx.size() + my.size() + (size_t)n_layers) * sizeof(float));
-    E.scratch(11).reserve((size_t)cap * sizeof(uint32_t));                 // evaluate list
-    E.scratch(12).reserve((size_t)cap * sizeof(uint32_t));                 // fill list
-    E.scratch(13).reserve((size_t)cap * sizeof(uint64_t));                 // the listed tiles' modes
-    E.scratch(9).reserve((size_t)n_layers * sizeof(uint64_t));             // layer sums
-    if (cov) E.scratch(15).reserve((size_t)chunk_layers * layer_img);      // the chunk's image
-    RasterState* d_state = E.scratch(10).as<RasterState>();
-    float* d_mx = behind_state<RasterState>(E.scratch(10));
-    float* d_my = d_mx + mx.size();
-    float* d_z = d_my + my.size();
-    uint32_t* d_list = E.scratch(11).as<uint32_t>();
-    uint32_t* d_fill = E.scratch(12).as<uint32_t>();
-    uint64_t* d_lmodes = E.scratch(13).as<uint64_t>();
-    unsigned long long* d_sums = E.scratch(9).as<unsigned long long>();
-    uint8_t* d_img = cov ? E.scratch(15).as<uint8_t>() : nullptr;
-    IMPLI_HIP(hipMemcpyAsync(d_mx, mx.data(), mx.size() * sizeof(float), hipMemcpyHostToDevice, s));
-    IMPLI_HIP(hipMemcpyAsync(d_my, my.data(), my.size() * sizeof(float), hipMemcpyHostToDevice, s));
-    IMPLI_HIP(hipMemcpyAsync(d_z, z, (size_t)n_layers * sizeof(float), hipMemcpyHostToDevice, s));
-    IMPLI_HIP(hipMemsetAsync(d_sums, 0, (size_t)n_layers * sizeof(uint64_t), s));
-    g_raster.sums.resize((size_t)n_layers);
+void raster_layers(const QueryShape& q, const LayerRequest& r, uint8_t* cov, int64_t* layer_sum, int64_t stats[5]) {
+    hipStream_t s = q.s;
+    LayerImages im(q, r, "raster", "IMPLISOLID_RASTER_CHUNK", kRasterMaxChunk, cov != nullptr, false);
+    const size_t layer_out = im.layer_px;
+    g_raster.sums.resize((size_t)r.n_layers);
     if (cov)
-        for (int k = 0; k < (n_layers > (int)chunk_layers ? 2 : 1); ++k) g_raster.img[k].resize((size_t)chunk_layers * layer_out);
-    int64_t evaluated = 0, filled = 0, samples = 0, chunks = 0;
+        for (int k = 0; k < (r.n_layers > (int)im.chunk_layers ? 2 : 1); ++k) g_raster.img[k].resize((size_t)im.chunk_layers * layer_out);
     // the chunk whose image is on its way into a staging slot, not yet in cov
     int pend_l0 = 0;
     uint32_t pend_nl = 0;
@@ -440,35 +546,19 @@ void raster_layers(Engine& E, hipStream_t s, const Program* d_prog, int prog_dep
         if (pend_nl) std::memcpy(cov + (size_t)pend_l0 * layer_out, g_raster.img[slot].data(), (size_t)pend_nl * layer_out);
         pend_nl = 0;
     };
-    for (int l0 = 0; l0 < n_layers; l0 += (int)chunk_layers, ++chunks) {
-        const uint32_t nl = (uint32_t)std::min<int64_t>(chunk_layers, n_layers - l0);
-        const uint32_t n = nl * g.tpl;
-        const int64_t first = (int64_t)l0 * g.tpl;
-        const int slot = (int)(chunks & 1);
-        IMPLI_HIP(hipMemsetAsync(d_state, 0, sizeof(RasterState), s));
-        if (cov) IMPLI_HIP(hipMemsetAsync(d_img, 0, (size_t)nl * layer_img, s));   // ordered behind the last chunk's copy
-        launch_raster_classify(d_prog, prog_depth, d_tab, E.tab_range(), d_mx, d_my, d_z, g, first, n, prune, d_list, d_lmodes,
-                               d_fill, d_state, s);
-        IMPLI_HIP(hipGetLastError());
-        RasterState h{};
-        IMPLI_HIP(hipMemcpyAsync(&h, d_state, sizeof h, hipMemcpyDeviceToHost, s));
-        IMPLI_HIP(hipStreamSynchronize(s));   // the last chunk's image has landed in the other slot as well
-        if (h.n_eval > n || h.n_fill > n || (uint64_t)h.n_eval + h.n_fill > n) throw HipError("raster: a tile list overran its chunk");
-        evaluated += h.n_eval;
-        filled += h.n_fill;
-        samples += (int64_t)h.samples;
-        launch_raster_eval(d_prog, prog_depth, d_tab, d_mx, d_my, d_z, g, first, l0, h.n_eval, d_list, d_lmodes, d_img, d_sums, s);
-        launch_raster_fill(g, first, l0, h.n_fill, d_fill, d_img, d_sums, s);
+    while (im.next()) {   // its synchronisation: the last chunk's image has landed in the other slot
+        const int l0 = im.l0, slot = (int)((im.chunks - 1) & 1);
+        const uint32_t nl = im.nl;
         IMPLI_HIP(hipGetLastError());
         if (cov) {
             uint8_t* dst = g_raster.img[slot].data();
-            if (g.pitch == (uint32_t)W)
-                IMPLI_HIP(hipMemcpyAsync(dst, d_img, (size_t)nl * layer_out, hipMemcpyDeviceToHost, s));
+            if (im.g.pitch == (uint32_t)r.W)
+                IMPLI_HIP(hipMemcpyAsync(dst, im.d_img, (size_t)nl * layer_out, hipMemcpyDeviceToHost, s));
             else
-                IMPLI_HIP(hipMemcpy2DAsync(dst, (size_t)W, d_img, (size_t)g.pitch, (size_t)W, (size_t)nl * (size_t)H,
+                IMPLI_HIP(hipMemcpy2DAsync(dst, (size_t)r.W, im.d_img, (size_t)im.g.pitch, (size_t)r.W, (size_t)nl * (size_t)r.H,
                                            hipMemcpyDeviceToHost, s));
         }
-        IMPLI_HIP(hipMemcpyAsync(g_raster.sums.data() + l0, d_sums + l0, (size_t)nl * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        IMPLI_HIP(hipMemcpyAsync(g_raster.sums.data() + l0, im.d_sums + l0, (size_t)nl * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         if (cov) {
             drain(slot ^ 1);   // the chunk before this one, while the device works on this one
             pend_l0 = l0;
@@ -476,15 +566,9 @@ void raster_layers(Engine& E, hipStream_t s, const Program* d_prog, int prog_dep
         }
     }
     IMPLI_HIP(hipStreamSynchronize(s));
-    if (cov) drain((int)((chunks - 1) & 1));
-    for (int l = 0; l < n_layers; ++l) layer_sum[l] = g_raster.sums.data()[l];
-    if (stats) {
-        stats[0] = (int64_t)n_layers * g.tpl;
-        stats[1] = evaluated;
-        stats[2] = filled;
-        stats[3] = samples;
-        stats[4] = chunks;
-    }
+    if (cov) drain((int)((im.chunks - 1) & 1));
+    for (int l = 0; l < r.n_layers; ++l) layer_sum[l] = g_raster.sums.data()[l];
+    if (stats) im.stats(stats);
 }
 }  // namespace
 
@@ -499,18 +583,11 @@ int implisolid_raster(const char* shape_json, int ignore_root_matrix, const floa
     }
     return guard_device([&] {
         // the request first: bad input is refused before anything is compiled or reaches the device
-        if (n_layers < 1 || n_layers > kRasterMaxLayers) throw InputError("implisolid_raster: n_layers must be in [1, 65536]");
-        for (int l = 0; l < n_layers; ++l)
-            if (!std::isfinite(z[l])) throw InputError("implisolid_raster: every z must be finite");
-        if (width < 1 || width > kRasterMaxSide || height < 1 || height > kRasterMaxSide)
-            throw InputError("implisolid_raster: width and height must be in [1, 16384]");
-        if (supersample != 1 && supersample != 2 && supersample != 4) throw InputError("implisolid_raster: supersample must be 1, 2 or 4");
-        std::vector<float> mx((size_t)width * supersample), my((size_t)height * supersample);
-        raster_coords(rect, width, height, supersample, mx.data(), my.data());
+        LayerRequest r("raster", rect, width, height, supersample, z, n_layers);
+        r.sample();
         QueryShape q(shape_json, ignore_root_matrix);
         q.upload();
-        raster_layers(*q.E, q.s, q.d_prog, q.max_depth, q.d_tab, width, height, supersample, mx, my, z, n_layers, cov, layer_sum,
-                      stats);
+        raster_layers(q, r, cov, layer_sum, stats);
         return 0;
     });
 }
@@ -526,14 +603,12 @@ int implisolid_raster_coords(const float rect[4], int width, int height, int sup
 }  // extern "C"
 
 // ---- islands of the layers (implisolid_islands) -------------------------------------------------------
-// Layers go through raster.hip's passes and then islands.hip's in chunks of whole layers, at most
-// kIslandMaxChunk (layer, raster tile) pairs each: the image zeroed, classify, a read-back of the two lists'
-// lengths, evaluate, fill; then tiles, merge, rows, the scan, a read-back of the chunk's per-layer record
-// offsets (their last entry sizes the records), roots, tally, and the copies of the records into the host
-// slot and of the labels, when asked for, into the caller's array.  The image stays on the device: the last
-// layer of a chunk is copied to a carry buffer for the first layer of the next.  E lends its scratch: 9 - 13
-// and 15 as raster_layers takes them, 14 the row counts, their scan, its sums and the layer offsets, 0 the
-// labels, 1 the records, 2 the carried layer.
+// Per chunk, behind LayerImages' head, islands.hip's passes: tiles, merge, rows, the scan, a read-back of the
+// chunk's per-layer record offsets (their last entry sizes the records), roots, tally, and the copies of the
+// records into the host slot and of the labels, when asked for, into the caller's array.  The image stays on
+// the device: the last layer of a chunk is copied to a carry buffer for the first layer of the next.  Scratch
+// of its own: 14 the row counts, their scan, its sums and the layer offsets, 0 the labels, 1 the records, 2 the
+// carried layer.
 namespace {
 struct IslandSlot {              // the last call's records; n < 0: none
     PinnedVec<int32_t> comps;
@@ -543,95 +618,50 @@ IslandSlot g_islands;
 bool g_island_timing = false;    // implisolid_debug_islands_ms: HIP events around the launches
 double g_island_ms[5] = {-1.0, -1.0, -1.0, -1.0, -1.0};
 
-int64_t island_layers(Engine& E, hipStream_t s, const Program* d_prog, int prog_depth, const float* d_tab, int W, int H, int ss,
-                      const std::vector<float>& mx, const std::vector<float>& my, const float* z, int n_layers, int threshold,
-                      int connectivity, int64_t* comp_offsets, int32_t* labels, int64_t stats[8]) {
-    RasterGrid g;
-    g.W = W;
-    g.H = H;
-    g.s = ss;
-    g.ntx = (W + kRasterTile - 1) / kRasterTile;
-    g.nty = (H + kRasterTile - 1) / kRasterTile;
-    g.tpl = (uint32_t)g.ntx * (uint32_t)g.nty;
-    g.pitch = (uint32_t)(kRasterTile * g.ntx);
-    const IslandGrid ig = island_grid(W, H, g.pitch, threshold, connectivity);
-    const uint32_t chunk_layers = cabi::chunk_layers("IMPLISOLID_ISLANDS_CHUNK", kIslandMaxChunk, g.tpl, n_layers);
-    const uint32_t cap = chunk_layers * g.tpl;   // items per chunk: <= kIslandMaxChunk, or one layer's
-    const bool prune = Engine::pruning() >= 1;
-    const size_t layer_img = (size_t)H * g.pitch, layer_px = (size_t)H * (size_t)W;
+int64_t island_layers(const QueryShape& q, const LayerRequest& r, int threshold, int connectivity, int64_t* comp_offsets,
+                      int32_t* labels, int64_t stats[8]) {
+    Engine& E = *q.E;
+    hipStream_t s = q.s;
+    const int H = r.H, n_layers = r.n_layers;
+    LayerImages im(q, r, "islands", "IMPLISOLID_ISLANDS_CHUNK", kIslandMaxChunk, true, g_island_timing);
+    const IslandGrid ig = island_grid(r.W, H, im.g.pitch, threshold, connectivity);
+    const uint32_t chunk_layers = im.chunk_layers;
+    const size_t layer_img = im.layer_img, layer_px = im.layer_px;
     const size_t rows_cap = (size_t)chunk_layers * (size_t)H;
-    // every reserve before any pointer is taken: a DevBuf that grows moves (the records' buffer, sized per
-    // chunk, holds nothing else)
-    E.scratch(10).reserve(kStateBytes + (mx.size() + my.size() + (size_t)n_layers) * sizeof(float));
-    E.scratch(11).reserve((size_t)cap * sizeof(uint32_t));                 // evaluate list
-    E.scratch(12).reserve((size_t)cap * sizeof(uint32_t));                 // fill list
-    E.scratch(13).reserve((size_t)cap * sizeof(uint64_t));                 // the listed tiles' modes
-    E.scratch(9).reserve((size_t)n_layers * sizeof(uint64_t));             // layer sums (the raster passes add them)
-    E.scratch(15).reserve((size_t)chunk_layers * layer_img);               // the chunk's image
+    // every reserve before any pointer is taken (the records' buffer, sized per chunk, holds nothing else)
     E.scratch(14).reserve((2 * rows_cap + 1 + rows_cap / 4096 + 2 + (size_t)chunk_layers + 1) * sizeof(uint32_t));
     E.scratch(0).reserve((size_t)chunk_layers * layer_px * sizeof(int32_t));   // labels
     if (n_layers > (int)chunk_layers) E.scratch(2).reserve(layer_img);     // the carried layer
     static_assert(sizeof(RasterState) + sizeof(IslandState) <= kStateBytes, "both states share the state block");
-    RasterState* d_state = E.scratch(10).as<RasterState>();
-    IslandState* d_istate = reinterpret_cast<IslandState*>(d_state + 1);
-    float* d_mx = behind_state<RasterState>(E.scratch(10));
-    float* d_my = d_mx + mx.size();
-    float* d_z = d_my + my.size();
-    uint32_t* d_list = E.scratch(11).as<uint32_t>();
-    uint32_t* d_fill = E.scratch(12).as<uint32_t>();
-    uint64_t* d_lmodes = E.scratch(13).as<uint64_t>();
-    unsigned long long* d_sums = E.scratch(9).as<unsigned long long>();
-    uint8_t* d_img = E.scratch(15).as<uint8_t>();
+    IslandState* d_istate = reinterpret_cast<IslandState*>(im.d_state + 1);
+    uint8_t* d_img = im.d_img;
     uint32_t* d_counts = E.scratch(14).as<uint32_t>();
     uint32_t* d_offsets = d_counts + rows_cap;
     uint32_t* d_scan_sums = d_offsets + rows_cap + 1;
     uint32_t* d_loff = d_scan_sums + rows_cap / 4096 + 2;
     int32_t* d_lab = E.scratch(0).as<int32_t>();
     uint8_t* d_carry = n_layers > (int)chunk_layers ? E.scratch(2).as<uint8_t>() : nullptr;
-    IMPLI_HIP(hipMemcpyAsync(d_mx, mx.data(), mx.size() * sizeof(float), hipMemcpyHostToDevice, s));
-    IMPLI_HIP(hipMemcpyAsync(d_my, my.data(), my.size() * sizeof(float), hipMemcpyHostToDevice, s));
-    IMPLI_HIP(hipMemcpyAsync(d_z, z, (size_t)n_layers * sizeof(float), hipMemcpyHostToDevice, s));
-    IMPLI_HIP(hipMemsetAsync(d_sums, 0, (size_t)n_layers * sizeof(uint64_t), s));
     IMPLI_HIP(hipMemsetAsync(d_istate, 0, sizeof(IslandState), s));
     g_islands.comps.resize(0);
-    EventSet<9> ev;
+    EventSet<5> ev;   // behind im.ev[3], the end of the raster passes: tiles, merge, rows + scan; around roots + tally
     if (g_island_timing) {
         ev.create();
         for (double& m : g_island_ms) m = 0.0;
     }
-    int64_t total = 0, evaluated = 0, filled = 0, samples = 0, chunks = 0;
+    int64_t total = 0;
     std::vector<uint32_t> loff((size_t)chunk_layers + 1);
-    for (int l0 = 0; l0 < n_layers; l0 += (int)chunk_layers, ++chunks) {
-        const uint32_t nl = (uint32_t)std::min<int64_t>(chunk_layers, n_layers - l0);
-        const uint32_t n = nl * g.tpl;
-        const int64_t first = (int64_t)l0 * g.tpl;
-        IMPLI_HIP(hipMemsetAsync(d_state, 0, sizeof(RasterState), s));
-        IMPLI_HIP(hipMemsetAsync(d_img, 0, (size_t)nl * layer_img, s));
-        if (ev[0]) IMPLI_HIP(hipEventRecord(ev[0], s));
-        launch_raster_classify(d_prog, prog_depth, d_tab, E.tab_range(), d_mx, d_my, d_z, g, first, n, prune, d_list, d_lmodes,
-                               d_fill, d_state, s);
-        if (ev[1]) IMPLI_HIP(hipEventRecord(ev[1], s));
-        IMPLI_HIP(hipGetLastError());
-        RasterState h{};
-        IMPLI_HIP(hipMemcpyAsync(&h, d_state, sizeof h, hipMemcpyDeviceToHost, s));
-        IMPLI_HIP(hipStreamSynchronize(s));
-        if (h.n_eval > n || h.n_fill > n || (uint64_t)h.n_eval + h.n_fill > n) throw HipError("islands: a tile list overran its chunk");
-        evaluated += h.n_eval;
-        filled += h.n_fill;
-        samples += (int64_t)h.samples;
-        if (ev[2]) IMPLI_HIP(hipEventRecord(ev[2], s));
-        launch_raster_eval(d_prog, prog_depth, d_tab, d_mx, d_my, d_z, g, first, l0, h.n_eval, d_list, d_lmodes, d_img, d_sums, s);
-        launch_raster_fill(g, first, l0, h.n_fill, d_fill, d_img, d_sums, s);
-        if (ev[3]) IMPLI_HIP(hipEventRecord(ev[3], s));
+    while (im.next()) {
+        const int l0 = im.l0;
+        const uint32_t nl = im.nl;
         launch_island_tiles(ig, nl, d_img, d_lab, d_istate, s);
-        if (ev[4]) IMPLI_HIP(hipEventRecord(ev[4], s));
+        if (ev[0]) IMPLI_HIP(hipEventRecord(ev[0], s));
         launch_island_merge(ig, nl, d_lab, s);
-        if (ev[5]) IMPLI_HIP(hipEventRecord(ev[5], s));
+        if (ev[1]) IMPLI_HIP(hipEventRecord(ev[1], s));
         const uint32_t rows = nl * (uint32_t)H;
         launch_island_rows(ig, nl, d_lab, d_counts, s);
         launch_scan_u32(d_counts, d_offsets, rows, d_scan_sums, false, s);
         launch_slice_layer_offsets(d_offsets, (uint32_t)H, nl, d_loff, s);   // every H-th entry and the total
-        if (ev[6]) IMPLI_HIP(hipEventRecord(ev[6], s));
+        if (ev[2]) IMPLI_HIP(hipEventRecord(ev[2], s));
         IMPLI_HIP(hipGetLastError());
         IMPLI_HIP(hipMemcpyAsync(loff.data(), d_loff, ((size_t)nl + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         IMPLI_HIP(hipStreamSynchronize(s));
@@ -641,10 +671,10 @@ int64_t island_layers(Engine& E, hipStream_t s, const Program* d_prog, int prog_
         if (cc) {
             E.scratch(1).reserve((size_t)cc * 8 * sizeof(int32_t));
             int32_t* d_rec = E.scratch(1).as<int32_t>();
-            if (ev[7]) IMPLI_HIP(hipEventRecord(ev[7], s));
+            if (ev[3]) IMPLI_HIP(hipEventRecord(ev[3], s));
             launch_island_roots(ig, nl, l0, d_lab, d_offsets, cc, d_rec, s);
             launch_island_tally(ig, nl, l0, d_img, d_carry, d_lab, d_loff, d_rec, s);
-            if (ev[8]) IMPLI_HIP(hipEventRecord(ev[8], s));
+            if (ev[4]) IMPLI_HIP(hipEventRecord(ev[4], s));
             IMPLI_HIP(hipGetLastError());
             g_islands.comps.resize((size_t)(total + cc) * 8);
             IMPLI_HIP(hipMemcpyAsync(g_islands.comps.data() + 8 * (size_t)total, d_rec, (size_t)cc * 8 * sizeof(int32_t),
@@ -658,14 +688,12 @@ int64_t island_layers(Engine& E, hipStream_t s, const Program* d_prog, int prog_
             IMPLI_HIP(hipMemcpyAsync(d_carry, d_img + (size_t)(nl - 1) * layer_img, layer_img, hipMemcpyDeviceToDevice, s));
         IMPLI_HIP(hipStreamSynchronize(s));   // the next chunk's launches write the buffers these copies read
         if (ev[0]) {
-            float a = 0.f, b = 0.f, c = 0.f, d = 0.f, e = 0.f, f = 0.f;
-            IMPLI_HIP(hipEventElapsedTime(&a, ev[0], ev[1]));
-            IMPLI_HIP(hipEventElapsedTime(&b, ev[2], ev[3]));
-            IMPLI_HIP(hipEventElapsedTime(&c, ev[3], ev[4]));
-            IMPLI_HIP(hipEventElapsedTime(&d, ev[4], ev[5]));
-            IMPLI_HIP(hipEventElapsedTime(&e, ev[5], ev[6]));
-            if (cc) IMPLI_HIP(hipEventElapsedTime(&f, ev[7], ev[8]));
-            g_island_ms[0] += a + b;
+            float c = 0.f, d = 0.f, e = 0.f, f = 0.f;
+            IMPLI_HIP(hipEventElapsedTime(&c, im.ev[3], ev[0]));
+            IMPLI_HIP(hipEventElapsedTime(&d, ev[0], ev[1]));
+            IMPLI_HIP(hipEventElapsedTime(&e, ev[1], ev[2]));
+            if (cc) IMPLI_HIP(hipEventElapsedTime(&f, ev[3], ev[4]));
+            g_island_ms[0] += im.raster_ms();
             g_island_ms[1] += c;
             g_island_ms[2] += d;
             g_island_ms[3] += e;
@@ -679,17 +707,13 @@ int64_t island_layers(Engine& E, hipStream_t s, const Program* d_prog, int prog_
     IMPLI_HIP(hipStreamSynchronize(s));
     int64_t islands = 0, area = 0;
     for (int64_t c = 0; c < total; ++c) {
-        const int32_t* r = g_islands.comps.data() + 8 * (size_t)c;
-        islands += r[2] == 0;
-        area += r[1];
+        const int32_t* rec = g_islands.comps.data() + 8 * (size_t)c;
+        islands += rec[2] == 0;
+        area += rec[1];
     }
     if (area != (int64_t)hi.solid) throw HipError("islands: the records' areas and the solid pixels disagree");
     if (stats) {
-        stats[0] = (int64_t)n_layers * g.tpl;
-        stats[1] = evaluated;
-        stats[2] = filled;
-        stats[3] = samples;
-        stats[4] = chunks;
+        im.stats(stats);
         stats[5] = total;
         stats[6] = islands;
         stats[7] = (int64_t)hi.solid;
@@ -711,21 +735,12 @@ int64_t implisolid_islands(const char* shape_json, int ignore_root_matrix, const
     }
     return guard_device([&]() -> int64_t {
         // the request first: bad input is refused before anything is compiled or reaches the device
-        if (n_layers < 1 || n_layers > kRasterMaxLayers) throw InputError("implisolid_islands: n_layers must be in [1, 65536]");
-        for (int l = 0; l < n_layers; ++l)
-            if (!std::isfinite(z[l])) throw InputError("implisolid_islands: every z must be finite");
-        if (width < 1 || width > kRasterMaxSide || height < 1 || height > kRasterMaxSide)
-            throw InputError("implisolid_islands: width and height must be in [1, 16384]");
-        if (supersample != 1 && supersample != 2 && supersample != 4) throw InputError("implisolid_islands: supersample must be 1, 2 or 4");
-        if (threshold < 1 || threshold > supersample * supersample)
-            throw InputError("implisolid_islands: threshold must be in [1, supersample^2]");
+        LayerRequest r("islands", rect, width, height, supersample, z, n_layers, threshold);
         if (connectivity != 4 && connectivity != 8) throw InputError("implisolid_islands: connectivity must be 4 or 8");
-        std::vector<float> mx((size_t)width * supersample), my((size_t)height * supersample);
-        raster_coords(rect, width, height, supersample, mx.data(), my.data());
+        r.sample();
         QueryShape q(shape_json, ignore_root_matrix);
         q.upload();
-        g_islands.n = island_layers(*q.E, q.s, q.d_prog, q.max_depth, q.d_tab, width, height, supersample, mx, my, z, n_layers,
-                                    threshold, connectivity, comp_offsets, labels, stats);
+        g_islands.n = island_layers(q, r, threshold, connectivity, comp_offsets, labels, stats);
         return g_islands.n;
     });
 }
@@ -751,93 +766,44 @@ int implisolid_debug_islands_ms(int enable, double ms[5]) {
 }  // extern "C"
 
 // ---- pixel distance field of the layers (implisolid_layer_distance) --------------------------------------
-// Layers go through raster.hip's passes and then distance.hip's in chunks of whole layers, at most
-// kDistMaxChunk (layer, raster tile) pairs each: the image zeroed, classify, a read-back of the two lists'
-// lengths, evaluate, fill; then columns, rows, unsupported, and the copy of the distances, when asked for,
-// into the caller's array.  The image stays on the device; the last distance layer of a chunk is copied to a
-// carry buffer for the first layer of the next.  The records add up on the device over the chunks and come
-// down once.  E lends its scratch: 9 - 13 and 15 as raster_layers takes them, 0 the distances, 1 the records,
-// 2 the carried layer.
+// Per chunk, behind LayerImages' head, distance.hip's passes: columns, rows, unsupported, and the copy of the
+// distances, when asked for, into the caller's array.  The image stays on the device; the last distance layer
+// of a chunk is copied to a carry buffer for the first layer of the next.  The records add up on the device
+// over the chunks and come down once.  Scratch of its own: 0 the distances, 1 the records, 2 the carried layer.
 namespace {
 bool g_dist_timing = false;      // implisolid_debug_layer_distance_ms: HIP events around the launches
 double g_dist_ms[3] = {-1.0, -1.0, -1.0};
 
-void distance_layers(Engine& E, hipStream_t s, const Program* d_prog, int prog_depth, const float* d_tab, int W, int H, int ss,
-                     const std::vector<float>& mx, const std::vector<float>& my, const float* z, int n_layers, int threshold,
-                     int64_t reach2, int32_t* dist, int64_t* layer_rec, int64_t stats[8]) {
-    RasterGrid g;
-    g.W = W;
-    g.H = H;
-    g.s = ss;
-    g.ntx = (W + kRasterTile - 1) / kRasterTile;
-    g.nty = (H + kRasterTile - 1) / kRasterTile;
-    g.tpl = (uint32_t)g.ntx * (uint32_t)g.nty;
-    g.pitch = (uint32_t)(kRasterTile * g.ntx);
-    const DistGrid dg = dist_grid(W, H, g.pitch, threshold);
-    const uint32_t chunk_layers = cabi::chunk_layers("IMPLISOLID_DISTANCE_CHUNK", kDistMaxChunk, g.tpl, n_layers);
-    const uint32_t cap = chunk_layers * g.tpl;   // items per chunk: <= kDistMaxChunk, or one layer's
-    const bool prune = Engine::pruning() >= 1;
-    const size_t layer_img = (size_t)H * g.pitch, layer_px = (size_t)H * (size_t)W;
-    // every reserve before any pointer is taken: a DevBuf that grows moves
-    E.scratch(10).reserve(kStateBytes + (mx.size() + my.size() + (size_t)n_layers) * sizeof(float));
-    E.scratch(11).reserve((size_t)cap * sizeof(uint32_t));                 // evaluate list
-    E.scratch(12).reserve((size_t)cap * sizeof(uint32_t));                 // fill list
-    E.scratch(13).reserve((size_t)cap * sizeof(uint64_t));                 // the listed tiles' modes
-    E.scratch(9).reserve((size_t)n_layers * sizeof(uint64_t));             // layer sums (the raster passes add them)
-    E.scratch(15).reserve((size_t)chunk_layers * layer_img);               // the chunk's image
+void distance_layers(const QueryShape& q, const LayerRequest& r, int threshold, int64_t reach2, int32_t* dist, int64_t* layer_rec,
+                     int64_t stats[8]) {
+    Engine& E = *q.E;
+    hipStream_t s = q.s;
+    const int n_layers = r.n_layers;
+    LayerImages im(q, r, "distance", "IMPLISOLID_DISTANCE_CHUNK", kDistMaxChunk, true, g_dist_timing);
+    const DistGrid dg = dist_grid(r.W, r.H, im.g.pitch, threshold);
+    const uint32_t chunk_layers = im.chunk_layers;
+    const size_t layer_px = im.layer_px;
+    // every reserve before any pointer is taken
     E.scratch(0).reserve((size_t)chunk_layers * layer_px * sizeof(int32_t));   // distances
     E.scratch(1).reserve((size_t)n_layers * 4 * sizeof(uint64_t));         // records
     if (n_layers > (int)chunk_layers) E.scratch(2).reserve(layer_px * sizeof(int32_t));   // the carried layer
-    RasterState* d_state = E.scratch(10).as<RasterState>();
-    float* d_mx = behind_state<RasterState>(E.scratch(10));
-    float* d_my = d_mx + mx.size();
-    float* d_z = d_my + my.size();
-    uint32_t* d_list = E.scratch(11).as<uint32_t>();
-    uint32_t* d_fill = E.scratch(12).as<uint32_t>();
-    uint64_t* d_lmodes = E.scratch(13).as<uint64_t>();
-    unsigned long long* d_sums = E.scratch(9).as<unsigned long long>();
-    uint8_t* d_img = E.scratch(15).as<uint8_t>();
     int32_t* d_dist = E.scratch(0).as<int32_t>();
     unsigned long long* d_rec = E.scratch(1).as<unsigned long long>();
     int32_t* d_carry = n_layers > (int)chunk_layers ? E.scratch(2).as<int32_t>() : nullptr;
-    IMPLI_HIP(hipMemcpyAsync(d_mx, mx.data(), mx.size() * sizeof(float), hipMemcpyHostToDevice, s));
-    IMPLI_HIP(hipMemcpyAsync(d_my, my.data(), my.size() * sizeof(float), hipMemcpyHostToDevice, s));
-    IMPLI_HIP(hipMemcpyAsync(d_z, z, (size_t)n_layers * sizeof(float), hipMemcpyHostToDevice, s));
-    IMPLI_HIP(hipMemsetAsync(d_sums, 0, (size_t)n_layers * sizeof(uint64_t), s));
     IMPLI_HIP(hipMemsetAsync(d_rec, 0, (size_t)n_layers * 4 * sizeof(uint64_t), s));
-    EventSet<7> ev;
+    EventSet<2> ev;   // behind im.ev[3], the end of the raster passes: columns, rows + unsupported
     if (g_dist_timing) {
         ev.create();
         for (double& m : g_dist_ms) m = 0.0;
     }
-    int64_t evaluated = 0, filled = 0, samples = 0, chunks = 0;
-    for (int l0 = 0; l0 < n_layers; l0 += (int)chunk_layers, ++chunks) {
-        const uint32_t nl = (uint32_t)std::min<int64_t>(chunk_layers, n_layers - l0);
-        const uint32_t n = nl * g.tpl;
-        const int64_t first = (int64_t)l0 * g.tpl;
-        IMPLI_HIP(hipMemsetAsync(d_state, 0, sizeof(RasterState), s));
-        IMPLI_HIP(hipMemsetAsync(d_img, 0, (size_t)nl * layer_img, s));
+    while (im.next()) {
+        const int l0 = im.l0;
+        const uint32_t nl = im.nl;
+        launch_distance_columns(dg, nl, im.d_img, d_dist, s);
         if (ev[0]) IMPLI_HIP(hipEventRecord(ev[0], s));
-        launch_raster_classify(d_prog, prog_depth, d_tab, E.tab_range(), d_mx, d_my, d_z, g, first, n, prune, d_list, d_lmodes,
-                               d_fill, d_state, s);
-        if (ev[1]) IMPLI_HIP(hipEventRecord(ev[1], s));
-        IMPLI_HIP(hipGetLastError());
-        RasterState h{};
-        IMPLI_HIP(hipMemcpyAsync(&h, d_state, sizeof h, hipMemcpyDeviceToHost, s));
-        IMPLI_HIP(hipStreamSynchronize(s));
-        if (h.n_eval > n || h.n_fill > n || (uint64_t)h.n_eval + h.n_fill > n) throw HipError("distance: a tile list overran its chunk");
-        evaluated += h.n_eval;
-        filled += h.n_fill;
-        samples += (int64_t)h.samples;
-        if (ev[2]) IMPLI_HIP(hipEventRecord(ev[2], s));
-        launch_raster_eval(d_prog, prog_depth, d_tab, d_mx, d_my, d_z, g, first, l0, h.n_eval, d_list, d_lmodes, d_img, d_sums, s);
-        launch_raster_fill(g, first, l0, h.n_fill, d_fill, d_img, d_sums, s);
-        if (ev[3]) IMPLI_HIP(hipEventRecord(ev[3], s));
-        launch_distance_columns(dg, nl, d_img, d_dist, s);
-        if (ev[4]) IMPLI_HIP(hipEventRecord(ev[4], s));
         launch_distance_rows(dg, nl, l0, d_dist, d_rec, s);
         launch_distance_unsupported(dg, nl, l0, reach2, d_dist, d_carry, d_rec, s);
-        if (ev[5]) IMPLI_HIP(hipEventRecord(ev[5], s));
+        if (ev[1]) IMPLI_HIP(hipEventRecord(ev[1], s));
         IMPLI_HIP(hipGetLastError());
         if (dist)
             IMPLI_HIP(hipMemcpyAsync(dist + (size_t)l0 * layer_px, d_dist, (size_t)nl * layer_px * sizeof(int32_t),
@@ -846,12 +812,10 @@ void distance_layers(Engine& E, hipStream_t s, const Program* d_prog, int prog_d
             IMPLI_HIP(hipMemcpyAsync(d_carry, d_dist + (size_t)(nl - 1) * layer_px, layer_px * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
         IMPLI_HIP(hipStreamSynchronize(s));   // the next chunk's launches write the buffers these copies read
         if (ev[0]) {
-            float a = 0.f, b = 0.f, c = 0.f, d = 0.f;
-            IMPLI_HIP(hipEventElapsedTime(&a, ev[0], ev[1]));
-            IMPLI_HIP(hipEventElapsedTime(&b, ev[2], ev[3]));
-            IMPLI_HIP(hipEventElapsedTime(&c, ev[3], ev[4]));
-            IMPLI_HIP(hipEventElapsedTime(&d, ev[4], ev[5]));
-            g_dist_ms[0] += a + b;
+            float c = 0.f, d = 0.f;
+            IMPLI_HIP(hipEventElapsedTime(&c, im.ev[3], ev[0]));
+            IMPLI_HIP(hipEventElapsedTime(&d, ev[0], ev[1]));
+            g_dist_ms[0] += im.raster_ms();
             g_dist_ms[1] += c;
             g_dist_ms[2] += d;
         }
@@ -861,23 +825,19 @@ void distance_layers(Engine& E, hipStream_t s, const Program* d_prog, int prog_d
     IMPLI_HIP(hipStreamSynchronize(s));
     int64_t solid = 0, unsupported = 0, whole = 0;
     for (int l = 0; l < n_layers; ++l) {
-        const unsigned long long* r = rec.data() + 4 * (size_t)l;
-        if ((r[0] == 0) != (r[1] == 0) || r[2] > r[0]) throw HipError("distance: a layer's record contradicts itself");
+        const unsigned long long* in = rec.data() + 4 * (size_t)l;
+        if ((in[0] == 0) != (in[1] == 0) || in[2] > in[0]) throw HipError("distance: a layer's record contradicts itself");
         int64_t* o = layer_rec + 4 * (size_t)l;
-        o[0] = (int64_t)r[0];
-        o[1] = (int64_t)(r[1] >> 32);
-        o[2] = r[1] ? (int64_t)(0xFFFFFFFFull - (r[1] & 0xFFFFFFFFull)) : -1;
-        o[3] = (int64_t)r[2];
+        o[0] = (int64_t)in[0];
+        o[1] = (int64_t)(in[1] >> 32);
+        o[2] = in[1] ? (int64_t)(0xFFFFFFFFull - (in[1] & 0xFFFFFFFFull)) : -1;
+        o[3] = (int64_t)in[2];
         solid += o[0];
         unsupported += o[3];
         whole += o[1] == (int64_t)kDistNone;
     }
     if (stats) {
-        stats[0] = (int64_t)n_layers * g.tpl;
-        stats[1] = evaluated;
-        stats[2] = filled;
-        stats[3] = samples;
-        stats[4] = chunks;
+        im.stats(stats);
         stats[5] = solid;
         stats[6] = unsupported;
         stats[7] = whole;
@@ -897,22 +857,12 @@ int implisolid_layer_distance(const char* shape_json, int ignore_root_matrix, co
     }
     return guard_device([&] {
         // the request first: bad input is refused before anything is compiled or reaches the device
-        if (n_layers < 1 || n_layers > kRasterMaxLayers) throw InputError("implisolid_layer_distance: n_layers must be in [1, 65536]");
-        for (int l = 0; l < n_layers; ++l)
-            if (!std::isfinite(z[l])) throw InputError("implisolid_layer_distance: every z must be finite");
-        if (width < 1 || width > kRasterMaxSide || height < 1 || height > kRasterMaxSide)
-            throw InputError("implisolid_layer_distance: width and height must be in [1, 16384]");
-        if (supersample != 1 && supersample != 2 && supersample != 4)
-            throw InputError("implisolid_layer_distance: supersample must be 1, 2 or 4");
-        if (threshold < 1 || threshold > supersample * supersample)
-            throw InputError("implisolid_layer_distance: threshold must be in [1, supersample^2]");
+        LayerRequest r("layer_distance", rect, width, height, supersample, z, n_layers, threshold);
         if (reach2 < 0 || reach2 >= (int64_t)kDistNone) throw InputError("implisolid_layer_distance: reach2 must be in [0, 2^30)");
-        std::vector<float> mx((size_t)width * supersample), my((size_t)height * supersample);
-        raster_coords(rect, width, height, supersample, mx.data(), my.data());
+        r.sample();
         QueryShape q(shape_json, ignore_root_matrix);
         q.upload();
-        distance_layers(*q.E, q.s, q.d_prog, q.max_depth, q.d_tab, width, height, supersample, mx, my, z, n_layers, threshold, reach2,
-                        dist, layer_rec, stats);
+        distance_layers(q, r, threshold, reach2, dist, layer_rec, stats);
         return 0;
     });
 }
@@ -931,6 +881,21 @@ int implisolid_debug_layer_distance_ms(int enable, double ms[3]) {
 // and directions uploaded, march, finish, and the results copied into the caller's arrays.  The work
 // figures add up on the device over the chunks and are read back once.  E lends its scratch.
 namespace {
+// The request implisolid_raycast and implisolid_ray_spans share, refused in this order: n, bisect, steps, the
+// range (ray_params), the origins and directions.  Returns the sample parameters.
+std::vector<float> ray_request(const std::string& entry, const float* origins, const float* dirs, int64_t n, float t0, float t1,
+                               int steps, int bisect) {
+    const std::string who = "implisolid_" + entry + ": ";
+    if (n < 0 || n > kRayMaxRays) throw InputError(who + "n must be in [0, 2^24]");
+    if (bisect < 0 || bisect > kRayMaxBisect) throw InputError(who + "bisect must be in [0, 32]");
+    if (steps < 1 || steps > kRayMaxSteps) throw InputError(who + "steps must be in [1, 65536]");
+    std::vector<float> ts((size_t)steps + 1);
+    ray_params(t0, t1, steps, ts.data());
+    for (int64_t i = 0; i < 3 * n; ++i)
+        if (!std::isfinite(origins[i]) || !std::isfinite(dirs[i])) throw InputError(who + "every origin and direction must be finite");
+    return ts;
+}
+
 bool g_ray_timing = false;       // implisolid_debug_raycast_ms: HIP events around the two launches
 double g_ray_ms[2] = {-1.0, -1.0};
 
@@ -1017,14 +982,7 @@ int implisolid_raycast(const char* shape_json, int ignore_root_matrix, const flo
     }
     return guard_device([&] {
         // the request first: bad input is refused before anything is compiled or reaches the device
-        if (n < 0 || n > kRayMaxRays) throw InputError("implisolid_raycast: n must be in [0, 2^24]");
-        if (bisect < 0 || bisect > kRayMaxBisect) throw InputError("implisolid_raycast: bisect must be in [0, 32]");
-        if (steps < 1 || steps > kRayMaxSteps) throw InputError("implisolid_raycast: steps must be in [1, 65536]");
-        std::vector<float> ts((size_t)steps + 1);
-        ray_params(t0, t1, steps, ts.data());
-        for (int64_t i = 0; i < 3 * n; ++i)
-            if (!std::isfinite(origins[i]) || !std::isfinite(dirs[i]))
-                throw InputError("implisolid_raycast: every origin and direction must be finite");
+        const std::vector<float> ts = ray_request("raycast", origins, dirs, n, t0, t1, steps, bisect);
         QueryShape q(shape_json, ignore_root_matrix);   // no rays: a bad shape is still reported
         if (stats) std::fill(stats, stats + 6, (int64_t)0);
         if (n == 0) return 0;                           // ... and nothing creates the engine or a stream
@@ -1194,14 +1152,7 @@ int64_t implisolid_ray_spans(const char* shape_json, int ignore_root_matrix, con
     }
     return guard_device([&]() -> int64_t {
         // the request first: bad input is refused before anything is compiled or reaches the device
-        if (n < 0 || n > kRayMaxRays) throw InputError("implisolid_ray_spans: n must be in [0, 2^24]");
-        if (bisect < 0 || bisect > kRayMaxBisect) throw InputError("implisolid_ray_spans: bisect must be in [0, 32]");
-        if (steps < 1 || steps > kRayMaxSteps) throw InputError("implisolid_ray_spans: steps must be in [1, 65536]");
-        std::vector<float> ts((size_t)steps + 1);
-        ray_params(t0, t1, steps, ts.data());
-        for (int64_t i = 0; i < 3 * n; ++i)
-            if (!std::isfinite(origins[i]) || !std::isfinite(dirs[i]))
-                throw InputError("implisolid_ray_spans: every origin and direction must be finite");
+        const std::vector<float> ts = ray_request("ray_spans", origins, dirs, n, t0, t1, steps, bisect);
         QueryShape q(shape_json, ignore_root_matrix);   // no rays: a bad shape is still reported
         if (stats) std::fill(stats, stats + 8, (int64_t)0);
         g_spans.has_normals = want_normals != 0;

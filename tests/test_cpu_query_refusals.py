@@ -1,8 +1,10 @@
-"""The refusal paths of the field queries (bounds, slice, raster, raycast, mass, their host-only
-companions and the two interval probes): the return value and the exact implisolid_last_error() text
-of every request that is refused before anything reaches a device, and that the library answers the
-next call.  The literals in EXPECTED were recorded from the library before the queries moved to
-csrc/abi_queries.hip; they pin that the move changed no error path.  No GPU."""
+"""The refusal paths of the field queries (bounds, slice, raster, islands, layer distance, raycast, ray
+spans, mass, their host-only companions and the two interval probes): the return value and the exact
+implisolid_last_error() text of every request that is refused before anything reaches a device, and
+that the library answers the next call.  The literals in EXPECTED were recorded from the library before
+the queries moved to csrc/abi_queries.hip, and those of the layer and ray entries before these came to
+share their request checks (LayerRequest, ray_request): they pin that neither changed an error path, nor
+which of two faults at once is reported.  No GPU."""
 import ctypes
 
 import numpy as np
@@ -68,6 +70,12 @@ ENTRY = {
                    cov=np.zeros(128, np.uint8), sums=i64(2), stats=i64(5)),
     "raycast": Args("implisolid_raycast", shape=SPHERE, irm=0, origins=RAYS, dirs=DIRS, n=2, t0=0.0, t1=4.0, steps=8, bisect=4,
                     hit=np.zeros(2, np.int32), t=F(0, 0), f=F(0, 0), normals=F(*[0] * 6), stats=i64(6)),
+    "islands": Args("implisolid_islands", shape=SPHERE, irm=0, rect=RECT, width=8, height=8, supersample=2, z=Z2, n_layers=2,
+                    threshold=1, connectivity=8, offsets=i64(3), labels=np.zeros(128, np.int32), stats=i64(8)),
+    "distance": Args("implisolid_layer_distance", shape=SPHERE, irm=0, rect=RECT, width=8, height=8, supersample=2, z=Z2,
+                     n_layers=2, threshold=1, reach2=0, dist=np.zeros(128, np.int32), rec=i64(8), stats=i64(8)),
+    "ray_spans": Args("implisolid_ray_spans", shape=SPHERE, irm=0, origins=RAYS, dirs=DIRS, n=2, t0=0.0, t1=4.0, steps=8, bisect=4,
+                      want_normals=0, offsets=i64(3), stats=i64(8)),
     "intervals": Args("implisolid_debug_intervals", shape=SPHERE, irm=0, variant=0, boxes=F(*BOX), modes_in=None, n=1,
                       iv=F(0, 0), modes_out=np.zeros(1, np.uint64)),
     "eval_modes": Args("implisolid_debug_eval_modes", shape=SPHERE, irm=0, xyz=F(0, 0, 0), modes=np.zeros(1, np.uint64), n=1,
@@ -91,6 +99,8 @@ ENTRY = {
 REVERSED_BOX = F(1, -1, -1, 1, -1, 1)
 NAN_BOX = F(-1, 1, -1, NAN, -1, 1)
 MANY_Z = np.zeros(65537, np.float32)
+REVERSED_RECT = F(1, -1, -1, 1)
+NAN_ORIGIN = F(-2, 0, 0, -2, NAN, 0)
 
 # (entry, what the case changes in the entry's valid request)
 CASES = {
@@ -156,6 +166,85 @@ CASES = {
     "raster truncated shape, supersample 3": ("raster", dict(shape=TRUNCATED, supersample=3)),
     "raster unknown type, width 0": ("raster", dict(shape=NO_SUCH_TYPE, width=0)),
     "raster truncated shape, 65537 layers": ("raster", dict(shape=TRUNCATED, z=MANY_Z, n_layers=65537, sums=i64(65537), cov=None)),
+    # two faults at once, across each step of the order: pointers, n_layers, z, width / height, supersample, rect, shape
+    "raster null rect, 0 layers": ("raster", dict(rect=None, n_layers=0)),
+    "raster 0 layers, nan z": ("raster", dict(n_layers=0, z=F(NAN, 0))),
+    "raster nan z, width 0": ("raster", dict(z=F(NAN, 0), width=0)),
+    "raster height 0, supersample 3": ("raster", dict(height=0, supersample=3)),
+    "raster supersample 3, reversed rect": ("raster", dict(supersample=3, rect=REVERSED_RECT)),
+    "raster unknown type, reversed rect": ("raster", dict(shape=NO_SUCH_TYPE, rect=REVERSED_RECT)),
+    # ---- islands: the checks it shares with raster, its own between supersample and the rect ---------------
+    "islands null shape": ("islands", dict(shape=None)),
+    "islands null rect": ("islands", dict(rect=None)),
+    "islands null z": ("islands", dict(z=None)),
+    "islands null offsets": ("islands", dict(offsets=None)),
+    "islands 0 layers": ("islands", dict(n_layers=0)),
+    "islands 65537 layers": ("islands", dict(z=MANY_Z, n_layers=65537, offsets=i64(65538), labels=None)),
+    "islands inf z": ("islands", dict(z=F(-INF, 0))),
+    "islands nan z": ("islands", dict(z=F(0, NAN))),
+    "islands width 0": ("islands", dict(width=0)),
+    "islands width 16385": ("islands", dict(width=16385)),
+    "islands height 0": ("islands", dict(height=0)),
+    "islands height 16385": ("islands", dict(height=16385)),
+    "islands supersample 3": ("islands", dict(supersample=3)),
+    "islands supersample 0": ("islands", dict(supersample=0)),
+    "islands threshold 0": ("islands", dict(threshold=0)),
+    "islands threshold 5": ("islands", dict(threshold=5)),
+    "islands supersample 1, threshold 2": ("islands", dict(supersample=1, threshold=2)),
+    "islands connectivity 6": ("islands", dict(connectivity=6)),
+    "islands reversed rect": ("islands", dict(rect=REVERSED_RECT)),
+    "islands nan rect": ("islands", dict(rect=F(-1, 1, NAN, 1))),
+    "islands truncated shape": ("islands", dict(shape=TRUNCATED)),
+    "islands unknown type": ("islands", dict(shape=NO_SUCH_TYPE)),
+    "islands null z, 0 layers": ("islands", dict(z=None, n_layers=0)),
+    "islands 0 layers, nan z": ("islands", dict(n_layers=0, z=F(NAN, 0))),
+    "islands nan z, width 0": ("islands", dict(z=F(NAN, 0), width=0)),
+    "islands height 16385, supersample 3": ("islands", dict(height=16385, supersample=3)),
+    "islands supersample 3, threshold 0": ("islands", dict(supersample=3, threshold=0)),
+    "islands supersample 0, connectivity 6": ("islands", dict(supersample=0, connectivity=6)),
+    "islands threshold 5, connectivity 6": ("islands", dict(threshold=5, connectivity=6)),
+    "islands threshold 0, reversed rect": ("islands", dict(threshold=0, rect=REVERSED_RECT)),
+    "islands connectivity 6, reversed rect": ("islands", dict(connectivity=6, rect=REVERSED_RECT)),
+    "islands unknown type, reversed rect": ("islands", dict(shape=NO_SUCH_TYPE, rect=REVERSED_RECT)),
+    "islands truncated shape, connectivity 6": ("islands", dict(shape=TRUNCATED, connectivity=6)),
+    "islands truncated shape, threshold 0": ("islands", dict(shape=TRUNCATED, threshold=0)),
+    "islands unknown type, 65537 layers": ("islands", dict(shape=NO_SUCH_TYPE, z=MANY_Z, n_layers=65537, offsets=i64(65538), labels=None)),
+    # ---- distance: the checks it shares with raster, its own between supersample and the rect ---------------
+    "distance null shape": ("distance", dict(shape=None)),
+    "distance null rect": ("distance", dict(rect=None)),
+    "distance null z": ("distance", dict(z=None)),
+    "distance null rec": ("distance", dict(rec=None)),
+    "distance 0 layers": ("distance", dict(n_layers=0)),
+    "distance 65537 layers": ("distance", dict(z=MANY_Z, n_layers=65537, rec=i64(4 * 65537), dist=None)),
+    "distance inf z": ("distance", dict(z=F(-INF, 0))),
+    "distance nan z": ("distance", dict(z=F(0, NAN))),
+    "distance width 0": ("distance", dict(width=0)),
+    "distance width 16385": ("distance", dict(width=16385)),
+    "distance height 0": ("distance", dict(height=0)),
+    "distance height 16385": ("distance", dict(height=16385)),
+    "distance supersample 3": ("distance", dict(supersample=3)),
+    "distance supersample 0": ("distance", dict(supersample=0)),
+    "distance threshold 0": ("distance", dict(threshold=0)),
+    "distance threshold 5": ("distance", dict(threshold=5)),
+    "distance supersample 1, threshold 2": ("distance", dict(supersample=1, threshold=2)),
+    "distance reach2 -1": ("distance", dict(reach2=-1)),
+    "distance reversed rect": ("distance", dict(rect=REVERSED_RECT)),
+    "distance nan rect": ("distance", dict(rect=F(-1, 1, NAN, 1))),
+    "distance truncated shape": ("distance", dict(shape=TRUNCATED)),
+    "distance unknown type": ("distance", dict(shape=NO_SUCH_TYPE)),
+    "distance null z, 0 layers": ("distance", dict(z=None, n_layers=0)),
+    "distance 0 layers, nan z": ("distance", dict(n_layers=0, z=F(NAN, 0))),
+    "distance nan z, width 0": ("distance", dict(z=F(NAN, 0), width=0)),
+    "distance height 16385, supersample 3": ("distance", dict(height=16385, supersample=3)),
+    "distance supersample 3, threshold 0": ("distance", dict(supersample=3, threshold=0)),
+    "distance supersample 0, reach2 -1": ("distance", dict(supersample=0, reach2=-1)),
+    "distance threshold 5, reach2 -1": ("distance", dict(threshold=5, reach2=-1)),
+    "distance threshold 0, reversed rect": ("distance", dict(threshold=0, rect=REVERSED_RECT)),
+    "distance reach2 -1, reversed rect": ("distance", dict(reach2=-1, rect=REVERSED_RECT)),
+    "distance unknown type, reversed rect": ("distance", dict(shape=NO_SUCH_TYPE, rect=REVERSED_RECT)),
+    "distance truncated shape, reach2 -1": ("distance", dict(shape=TRUNCATED, reach2=-1)),
+    "distance truncated shape, threshold 0": ("distance", dict(shape=TRUNCATED, threshold=0)),
+    "distance unknown type, 65537 layers": ("distance", dict(shape=NO_SUCH_TYPE, z=MANY_Z, n_layers=65537, rec=i64(4 * 65537), dist=None)),
     # ---- raycast ----------------------------------------------------------------------------------
     "raycast null shape": ("raycast", dict(shape=None)),
     "raycast null origins": ("raycast", dict(origins=None)),
@@ -170,18 +259,51 @@ CASES = {
     "raycast bisect -1": ("raycast", dict(bisect=-1)),
     "raycast bisect 33": ("raycast", dict(bisect=33)),
     "raycast empty range": ("raycast", dict(t0=1.0, t1=1.0)),
-    "raycast nan origin": ("raycast", dict(origins=F(-2, 0, 0, -2, NAN, 0))),
+    "raycast nan origin": ("raycast", dict(origins=NAN_ORIGIN)),
     "raycast inf direction": ("raycast", dict(dirs=F(1, 0, 0, INF, 0, 0))),
     "raycast truncated shape": ("raycast", dict(shape=TRUNCATED)),
     "raycast unknown type": ("raycast", dict(shape=NO_SUCH_TYPE)),
     "raycast truncated shape, bisect 33": ("raycast", dict(shape=TRUNCATED, bisect=33)),
     "raycast unknown type, steps 0": ("raycast", dict(shape=NO_SUCH_TYPE, steps=0)),
-    "raycast truncated shape, nan origin": ("raycast", dict(shape=TRUNCATED, origins=F(-2, 0, 0, -2, NAN, 0))),
+    "raycast truncated shape, nan origin": ("raycast", dict(shape=TRUNCATED, origins=NAN_ORIGIN)),
     "raycast unknown type, n -1": ("raycast", dict(shape=NO_SUCH_TYPE, n=-1)),
     "raycast no rays, truncated shape": ("raycast", dict(shape=TRUNCATED, n=0)),
     "raycast no rays, unknown type, null arrays": ("raycast", dict(shape=NO_SUCH_TYPE, n=0, origins=None, dirs=None, hit=None,
                                                                    t=None, f=None, normals=None)),
     "raycast no rays, steps 0": ("raycast", dict(n=0, steps=0)),
+    "raycast n -1, bisect 33": ("raycast", dict(n=-1, bisect=33)),
+    "raycast bisect 33, steps 0": ("raycast", dict(bisect=33, steps=0)),
+    "raycast steps 0, empty range": ("raycast", dict(steps=0, t0=1.0, t1=1.0)),
+    "raycast empty range, nan origin": ("raycast", dict(t0=1.0, t1=1.0, origins=NAN_ORIGIN)),
+    # ---- ray_spans: the checks it shares with raycast ------------------------------------------------------
+    "ray_spans null shape": ("ray_spans", dict(shape=None)),
+    "ray_spans null origins": ("ray_spans", dict(origins=None)),
+    "ray_spans null dirs": ("ray_spans", dict(dirs=None)),
+    "ray_spans null offsets": ("ray_spans", dict(offsets=None)),
+    "ray_spans n -1": ("ray_spans", dict(n=-1)),
+    "ray_spans n 2^24 + 1": ("ray_spans", dict(n=(1 << 24) + 1)),
+    "ray_spans bisect -1": ("ray_spans", dict(bisect=-1)),
+    "ray_spans bisect 33": ("ray_spans", dict(bisect=33)),
+    "ray_spans steps 0": ("ray_spans", dict(steps=0)),
+    "ray_spans steps 65537": ("ray_spans", dict(steps=65537)),
+    "ray_spans empty range": ("ray_spans", dict(t0=1.0, t1=1.0)),
+    "ray_spans nan t1": ("ray_spans", dict(t1=NAN)),
+    "ray_spans nan origin": ("ray_spans", dict(origins=NAN_ORIGIN)),
+    "ray_spans inf direction": ("ray_spans", dict(dirs=F(1, 0, 0, INF, 0, 0))),
+    "ray_spans truncated shape": ("ray_spans", dict(shape=TRUNCATED)),
+    "ray_spans unknown type": ("ray_spans", dict(shape=NO_SUCH_TYPE)),
+    "ray_spans null offsets, n -1": ("ray_spans", dict(offsets=None, n=-1)),
+    "ray_spans n -1, bisect 33": ("ray_spans", dict(n=-1, bisect=33)),
+    "ray_spans bisect 33, steps 0": ("ray_spans", dict(bisect=33, steps=0)),
+    "ray_spans steps 0, empty range": ("ray_spans", dict(steps=0, t0=1.0, t1=1.0)),
+    "ray_spans steps 0, nan origin": ("ray_spans", dict(steps=0, origins=NAN_ORIGIN)),
+    "ray_spans empty range, nan origin": ("ray_spans", dict(t0=1.0, t1=1.0, origins=NAN_ORIGIN)),
+    "ray_spans truncated shape, nan origin": ("ray_spans", dict(shape=TRUNCATED, origins=NAN_ORIGIN)),
+    "ray_spans unknown type, empty range": ("ray_spans", dict(shape=NO_SUCH_TYPE, t0=1.0, t1=1.0)),
+    "ray_spans no rays, truncated shape": ("ray_spans", dict(shape=TRUNCATED, n=0)),
+    "ray_spans no rays, unknown type, null arrays": ("ray_spans", dict(shape=NO_SUCH_TYPE, n=0, origins=None, dirs=None)),
+    "ray_spans no rays, steps 0": ("ray_spans", dict(n=0, steps=0)),
+    "ray_spans no rays, empty range": ("ray_spans", dict(n=0, t0=1.0, t1=1.0)),
     # ---- the interval probes ----------------------------------------------------------------------
     "intervals null shape": ("intervals", dict(shape=None)),
     "intervals variant 3": ("intervals", dict(variant=3)),
@@ -352,6 +474,115 @@ EXPECTED = {
     'mass_physical null out': (-1, 'implisolid_mass_physical: bad arguments'),
     'mass_physical depth 11': (-1, 'mass: depth must be in [3, 10]'),
     'mass_physical reversed box': (-1, 'mass: the box must be finite with min < max on every axis'),
+    # recorded before the layer entries and the ray entries came to share their request checks
+    'raster null rect, 0 layers': (-1, 'implisolid_raster: bad arguments'),
+    'raster 0 layers, nan z': (-1, 'implisolid_raster: n_layers must be in [1, 65536]'),
+    'raster nan z, width 0': (-1, 'implisolid_raster: every z must be finite'),
+    'raster height 0, supersample 3': (-1, 'implisolid_raster: width and height must be in [1, 16384]'),
+    'raster supersample 3, reversed rect': (-1, 'implisolid_raster: supersample must be 1, 2 or 4'),
+    'raster unknown type, reversed rect': (-1, 'raster: the rect must be finite with min < max on both axes'),
+    'islands null shape': (-1, 'implisolid_islands: bad arguments'),
+    'islands null rect': (-1, 'implisolid_islands: bad arguments'),
+    'islands null z': (-1, 'implisolid_islands: bad arguments'),
+    'islands null offsets': (-1, 'implisolid_islands: bad arguments'),
+    'islands 0 layers': (-1, 'implisolid_islands: n_layers must be in [1, 65536]'),
+    'islands 65537 layers': (-1, 'implisolid_islands: n_layers must be in [1, 65536]'),
+    'islands inf z': (-1, 'implisolid_islands: every z must be finite'),
+    'islands nan z': (-1, 'implisolid_islands: every z must be finite'),
+    'islands width 0': (-1, 'implisolid_islands: width and height must be in [1, 16384]'),
+    'islands width 16385': (-1, 'implisolid_islands: width and height must be in [1, 16384]'),
+    'islands height 0': (-1, 'implisolid_islands: width and height must be in [1, 16384]'),
+    'islands height 16385': (-1, 'implisolid_islands: width and height must be in [1, 16384]'),
+    'islands supersample 3': (-1, 'implisolid_islands: supersample must be 1, 2 or 4'),
+    'islands supersample 0': (-1, 'implisolid_islands: supersample must be 1, 2 or 4'),
+    'islands threshold 0': (-1, 'implisolid_islands: threshold must be in [1, supersample^2]'),
+    'islands threshold 5': (-1, 'implisolid_islands: threshold must be in [1, supersample^2]'),
+    'islands supersample 1, threshold 2': (-1, 'implisolid_islands: threshold must be in [1, supersample^2]'),
+    'islands connectivity 6': (-1, 'implisolid_islands: connectivity must be 4 or 8'),
+    'islands reversed rect': (-1, 'raster: the rect must be finite with min < max on both axes'),
+    'islands nan rect': (-1, 'raster: the rect must be finite with min < max on both axes'),
+    'islands truncated shape': (-1, 'JSON parse error: expected , or ]'),
+    'islands unknown type': (-1, 'Invalid object you asked for: "no_such_solid"'),
+    'islands null z, 0 layers': (-1, 'implisolid_islands: bad arguments'),
+    'islands 0 layers, nan z': (-1, 'implisolid_islands: n_layers must be in [1, 65536]'),
+    'islands nan z, width 0': (-1, 'implisolid_islands: every z must be finite'),
+    'islands height 16385, supersample 3': (-1, 'implisolid_islands: width and height must be in [1, 16384]'),
+    'islands supersample 3, threshold 0': (-1, 'implisolid_islands: supersample must be 1, 2 or 4'),
+    'islands supersample 0, connectivity 6': (-1, 'implisolid_islands: supersample must be 1, 2 or 4'),
+    'islands threshold 5, connectivity 6': (-1, 'implisolid_islands: threshold must be in [1, supersample^2]'),
+    'islands threshold 0, reversed rect': (-1, 'implisolid_islands: threshold must be in [1, supersample^2]'),
+    'islands connectivity 6, reversed rect': (-1, 'implisolid_islands: connectivity must be 4 or 8'),
+    'islands unknown type, reversed rect': (-1, 'raster: the rect must be finite with min < max on both axes'),
+    'islands truncated shape, connectivity 6': (-1, 'implisolid_islands: connectivity must be 4 or 8'),
+    'islands truncated shape, threshold 0': (-1, 'implisolid_islands: threshold must be in [1, supersample^2]'),
+    'islands unknown type, 65537 layers': (-1, 'implisolid_islands: n_layers must be in [1, 65536]'),
+    'distance null shape': (-1, 'implisolid_layer_distance: bad arguments'),
+    'distance null rect': (-1, 'implisolid_layer_distance: bad arguments'),
+    'distance null z': (-1, 'implisolid_layer_distance: bad arguments'),
+    'distance null rec': (-1, 'implisolid_layer_distance: bad arguments'),
+    'distance 0 layers': (-1, 'implisolid_layer_distance: n_layers must be in [1, 65536]'),
+    'distance 65537 layers': (-1, 'implisolid_layer_distance: n_layers must be in [1, 65536]'),
+    'distance inf z': (-1, 'implisolid_layer_distance: every z must be finite'),
+    'distance nan z': (-1, 'implisolid_layer_distance: every z must be finite'),
+    'distance width 0': (-1, 'implisolid_layer_distance: width and height must be in [1, 16384]'),
+    'distance width 16385': (-1, 'implisolid_layer_distance: width and height must be in [1, 16384]'),
+    'distance height 0': (-1, 'implisolid_layer_distance: width and height must be in [1, 16384]'),
+    'distance height 16385': (-1, 'implisolid_layer_distance: width and height must be in [1, 16384]'),
+    'distance supersample 3': (-1, 'implisolid_layer_distance: supersample must be 1, 2 or 4'),
+    'distance supersample 0': (-1, 'implisolid_layer_distance: supersample must be 1, 2 or 4'),
+    'distance threshold 0': (-1, 'implisolid_layer_distance: threshold must be in [1, supersample^2]'),
+    'distance threshold 5': (-1, 'implisolid_layer_distance: threshold must be in [1, supersample^2]'),
+    'distance supersample 1, threshold 2': (-1, 'implisolid_layer_distance: threshold must be in [1, supersample^2]'),
+    'distance reach2 -1': (-1, 'implisolid_layer_distance: reach2 must be in [0, 2^30)'),
+    'distance reversed rect': (-1, 'raster: the rect must be finite with min < max on both axes'),
+    'distance nan rect': (-1, 'raster: the rect must be finite with min < max on both axes'),
+    'distance truncated shape': (-1, 'JSON parse error: expected , or ]'),
+    'distance unknown type': (-1, 'Invalid object you asked for: "no_such_solid"'),
+    'distance null z, 0 layers': (-1, 'implisolid_layer_distance: bad arguments'),
+    'distance 0 layers, nan z': (-1, 'implisolid_layer_distance: n_layers must be in [1, 65536]'),
+    'distance nan z, width 0': (-1, 'implisolid_layer_distance: every z must be finite'),
+    'distance height 16385, supersample 3': (-1, 'implisolid_layer_distance: width and height must be in [1, 16384]'),
+    'distance supersample 3, threshold 0': (-1, 'implisolid_layer_distance: supersample must be 1, 2 or 4'),
+    'distance supersample 0, reach2 -1': (-1, 'implisolid_layer_distance: supersample must be 1, 2 or 4'),
+    'distance threshold 5, reach2 -1': (-1, 'implisolid_layer_distance: threshold must be in [1, supersample^2]'),
+    'distance threshold 0, reversed rect': (-1, 'implisolid_layer_distance: threshold must be in [1, supersample^2]'),
+    'distance reach2 -1, reversed rect': (-1, 'implisolid_layer_distance: reach2 must be in [0, 2^30)'),
+    'distance unknown type, reversed rect': (-1, 'raster: the rect must be finite with min < max on both axes'),
+    'distance truncated shape, reach2 -1': (-1, 'implisolid_layer_distance: reach2 must be in [0, 2^30)'),
+    'distance truncated shape, threshold 0': (-1, 'implisolid_layer_distance: threshold must be in [1, supersample^2]'),
+    'distance unknown type, 65537 layers': (-1, 'implisolid_layer_distance: n_layers must be in [1, 65536]'),
+    'raycast n -1, bisect 33': (-1, 'implisolid_raycast: n must be in [0, 2^24]'),
+    'raycast bisect 33, steps 0': (-1, 'implisolid_raycast: bisect must be in [0, 32]'),
+    'raycast steps 0, empty range': (-1, 'implisolid_raycast: steps must be in [1, 65536]'),
+    'raycast empty range, nan origin': (-1, 'raycast: the range must be finite with t0 < t1'),
+    'ray_spans null shape': (-1, 'implisolid_ray_spans: bad arguments'),
+    'ray_spans null origins': (-1, 'implisolid_ray_spans: bad arguments'),
+    'ray_spans null dirs': (-1, 'implisolid_ray_spans: bad arguments'),
+    'ray_spans null offsets': (-1, 'implisolid_ray_spans: bad arguments'),
+    'ray_spans n -1': (-1, 'implisolid_ray_spans: n must be in [0, 2^24]'),
+    'ray_spans n 2^24 + 1': (-1, 'implisolid_ray_spans: n must be in [0, 2^24]'),
+    'ray_spans bisect -1': (-1, 'implisolid_ray_spans: bisect must be in [0, 32]'),
+    'ray_spans bisect 33': (-1, 'implisolid_ray_spans: bisect must be in [0, 32]'),
+    'ray_spans steps 0': (-1, 'implisolid_ray_spans: steps must be in [1, 65536]'),
+    'ray_spans steps 65537': (-1, 'implisolid_ray_spans: steps must be in [1, 65536]'),
+    'ray_spans empty range': (-1, 'raycast: the range must be finite with t0 < t1'),
+    'ray_spans nan t1': (-1, 'raycast: the range must be finite with t0 < t1'),
+    'ray_spans nan origin': (-1, 'implisolid_ray_spans: every origin and direction must be finite'),
+    'ray_spans inf direction': (-1, 'implisolid_ray_spans: every origin and direction must be finite'),
+    'ray_spans truncated shape': (-1, 'JSON parse error: expected , or ]'),
+    'ray_spans unknown type': (-1, 'Invalid object you asked for: "no_such_solid"'),
+    'ray_spans null offsets, n -1': (-1, 'implisolid_ray_spans: bad arguments'),
+    'ray_spans n -1, bisect 33': (-1, 'implisolid_ray_spans: n must be in [0, 2^24]'),
+    'ray_spans bisect 33, steps 0': (-1, 'implisolid_ray_spans: bisect must be in [0, 32]'),
+    'ray_spans steps 0, empty range': (-1, 'implisolid_ray_spans: steps must be in [1, 65536]'),
+    'ray_spans steps 0, nan origin': (-1, 'implisolid_ray_spans: steps must be in [1, 65536]'),
+    'ray_spans empty range, nan origin': (-1, 'raycast: the range must be finite with t0 < t1'),
+    'ray_spans truncated shape, nan origin': (-1, 'implisolid_ray_spans: every origin and direction must be finite'),
+    'ray_spans unknown type, empty range': (-1, 'raycast: the range must be finite with t0 < t1'),
+    'ray_spans no rays, truncated shape': (-1, 'JSON parse error: expected , or ]'),
+    'ray_spans no rays, unknown type, null arrays': (-1, 'Invalid object you asked for: "no_such_solid"'),
+    'ray_spans no rays, steps 0': (-1, 'implisolid_ray_spans: steps must be in [1, 65536]'),
+    'ray_spans no rays, empty range': (-1, 'raycast: the range must be finite with t0 < t1'),
 }
 
 
@@ -407,6 +638,19 @@ def test_raycast_without_rays_compiles_the_shape_and_zeroes_the_stats(impli):
     rc, msg = observe(L, "raycast no rays, truncated shape")
     assert (rc, msg) == EXPECTED["raycast no rays, truncated shape"]
     assert ENTRY["raycast"](L, n=0, shape=TRUNCATED, stats=stats) == -1 and stats.tolist() == [7] * 6, "stats untouched"
+    next_call_works(impli)
+
+
+def test_ray_spans_without_rays_compiles_the_shape_zeroes_the_stats_and_fills_the_slot(impli):
+    L = impli.lib()
+    stats, offs = np.full(8, 7, np.int64), np.full(1, 7, np.int64)
+    assert ENTRY["ray_spans"](L, n=0, origins=None, dirs=None, offsets=offs, stats=stats) == 0 and impli.last_error() == ""
+    assert stats.tolist() == [0] * 8 and offs.tolist() == [0]
+    assert L.implisolid_ray_spans_copy(None, None, None, None) == 0, "an empty result is a result"
+    stats[:], offs[:] = 7, 7
+    assert ENTRY["ray_spans"](L, n=0, shape=TRUNCATED, offsets=offs, stats=stats) == -1
+    assert stats.tolist() == [7] * 8 and offs.tolist() == [7], "stats and offsets untouched"
+    assert L.implisolid_ray_spans_copy(None, None, None, None) == -1, "and the slot is empty"
     next_call_works(impli)
 
 
