@@ -58,6 +58,7 @@ ABI_SYMBOLS = [
     "implisolid_raster", "implisolid_raster_coords",
     "implisolid_islands", "implisolid_islands_copy", "implisolid_debug_islands_ms",
     "implisolid_layer_distance", "implisolid_debug_layer_distance_ms",
+    "implisolid_layer_runs", "implisolid_layer_runs_copy", "implisolid_debug_layer_runs_ms",
     "implisolid_raycast", "implisolid_ray_params", "implisolid_debug_raycast_ms",
     "implisolid_ray_spans", "implisolid_ray_spans_copy", "implisolid_debug_ray_spans_ms",
 ]
@@ -222,6 +223,10 @@ def lib():
         "implisolid_layer_distance": ([c_char_p, c_int, fp, c_int, c_int, c_int, fp, c_int, c_int, ctypes.c_int64, ip,
                                        ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)], c_int),
         "implisolid_debug_layer_distance_ms": ([c_int, ctypes.POINTER(ctypes.c_double)], c_int),
+        "implisolid_layer_runs": ([c_char_p, c_int, fp, c_int, c_int, c_int, fp, c_int, c_int, ctypes.POINTER(ctypes.c_int64),
+                                   ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)], ctypes.c_int64),
+        "implisolid_layer_runs_copy": ([up, ctypes.POINTER(ctypes.c_uint8)], c_int),
+        "implisolid_debug_layer_runs_ms": ([c_int, ctypes.POINTER(ctypes.c_double)], c_int),
         "implisolid_raycast": ([c_char_p, c_int, fp, fp, ctypes.c_int64, ctypes.c_float, ctypes.c_float, c_int, c_int, ip, fp,
                                 fp, fp, ctypes.POINTER(ctypes.c_int64)], c_int),
         "implisolid_ray_params": ([ctypes.c_float, ctypes.c_float, c_int, fp], c_int),
@@ -745,7 +750,7 @@ def _rect4(rect, what):
 
 
 def _layer_args(what, rect, z, width, height, supersample):
-    """What raster_layers, layer_islands and layer_distance do with their arguments first: (rect, z, W, H, s)."""
+    """What raster_layers, layer_islands, layer_distance and layer_runs do with their arguments first: (rect, z, W, H, s)."""
     r = _rect4(rect, what)
     zz = np.ascontiguousarray(z, np.float32).reshape(-1)
     W, H, s = int(width), int(height), int(supersample)
@@ -971,6 +976,64 @@ def layer_distance_kernel_ms(enable=True):
     call's (raster passes, column pass, row pass + records) ms, -1 before any."""
     ms = (ctypes.c_double * 3)()
     lib().implisolid_debug_layer_distance_ms(int(bool(enable)), ms)
+    return tuple(float(v) for v in ms)
+
+
+def layer_runs(shape, rect, width, height, z, supersample=1, threshold=0, ignore_root_matrix=False, return_stats=False):
+    """The solid's layers z = z[l] as run-length streams on the GPU (include/implisolid.h implisolid_layer_runs).
+    The images are raster_layers'; a pixel's value is its coverage (threshold 0, the grey mode) or coverage >=
+    threshold as 0 / 1 (threshold in 1 .. supersample^2).  A layer is the row-major stream p = py * width + px;
+    a run starts at p = 0 and wherever the value changes, across row ends too.  Returns (run_offsets int64
+    (L + 1,): layer l's runs are [run_offsets[l], run_offsets[l + 1]); start uint32 (R,) = each run's first p, in
+    increasing order within its layer; value uint8 (R,); layer_sum int64 (L,) = raster_layers' sums), and with
+    return_stats also [raster_layers' five figures, runs, runs with value != 0]."""
+    fp, lp = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64)
+    r, zz, W, H, s = _layer_args("layer_runs", rect, z, width, height, supersample)
+    offs = np.zeros(zz.size + 1, np.int64)
+    sums = np.zeros(zz.size, np.int64)
+    stats = (ctypes.c_int64 * 7)()
+    n = lib().implisolid_layer_runs(_s(shape), int(bool(ignore_root_matrix)), r.ctypes.data_as(fp), W, H, s, zz.ctypes.data_as(fp),
+                                    int(zz.size), int(threshold), offs.ctypes.data_as(lp), sums.ctypes.data_as(lp), stats)
+    if n < 0:
+        raise ImplisolidError(last_error())
+    start = np.empty(n, np.uint32)
+    value = np.empty(n, np.uint8)
+    if lib().implisolid_layer_runs_copy(start.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                        value.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))) != 0:
+        raise ImplisolidError(last_error())
+    if return_stats:
+        return offs, start, value, sums, [int(v) for v in stats]
+    return offs, start, value, sums
+
+
+def run_lengths(run_offsets, start, layer_pixels):
+    """Host only: the lengths int64 (R,) of layer_runs()'s runs: the next run's start minus the run's own, and
+    layer_pixels (= width * height) minus the start for the last run of a layer."""
+    offs = np.asarray(run_offsets, np.int64).reshape(-1)
+    st = np.asarray(start).astype(np.int64).reshape(-1)
+    if offs.size < 1 or offs[0] != 0 or offs[-1] != st.size or (np.diff(offs) < 1).any():
+        raise ValueError("run_lengths: run_offsets must run from 0 to len(start) with a run in every layer at least")
+    end = np.empty_like(st)
+    end[:-1] = st[1:]
+    end[offs[1:] - 1] = int(layer_pixels)
+    return end - st
+
+
+def runs_decode(run_offsets, start, value, width, height):
+    """Host only: the images of layer_runs()'s runs, uint8 (L, height, width)."""
+    W, H = int(width), int(height)
+    offs = np.asarray(run_offsets, np.int64).reshape(-1)
+    lengths = run_lengths(offs, start, W * H)
+    if (lengths < 1).any() or (np.asarray(start)[offs[:-1]] != 0).any():
+        raise ValueError("runs_decode: every layer's starts must begin at 0 and increase below width * height")
+    return np.repeat(np.asarray(value, np.uint8).reshape(-1), lengths).reshape(offs.size - 1, H, W)
+
+
+def layer_runs_kernel_ms(enable=True):
+    """Diagnostics: switch the event timing of layer_runs()'s kernels on or off; returns the last timed call's
+    (raster passes, count pass + scan, emit pass) ms, -1 before any."""
+    ms = (ctypes.c_double * 3)()
+    lib().implisolid_debug_layer_runs_ms(int(bool(enable)), ms)
     return tuple(float(v) for v in ms)
 
 

@@ -1,7 +1,7 @@
 // abi_queries.hip -- the field queries of the C ABI: the interval probes, bounds, slices, layer images and
-// their islands and distance fields, rays and mass properties.  Each entry validates its request, compiles
+// their islands, distance fields and run-length streams, rays and mass properties.  Each entry validates its request, compiles
 // the shape (QueryShape), puts it on the device and runs its passes; the scaffolding is abi_common.hpp's.
-// The three layer queries share their request (LayerRequest) and the passes that make a chunk's image
+// The four layer queries share their request (LayerRequest) and the passes that make a chunk's image
 // (LayerImages): each reads as what it does with the image.  The two ray queries share ray_request.
 #include <cmath>
 #include <cstring>
@@ -383,7 +383,7 @@ int64_t implisolid_slice_loops(const uint32_t* keys, int64_t n_segments, int64_t
 
 }  // extern "C"
 
-// ---- what the layer queries share: the request and the image (raster, islands, layer distance) ------------
+// ---- what the layer queries share: the request and the image (raster, islands, layer distance, runs) ------
 namespace {
 // The request of implisolid_<entry>, refused in this order: n_layers, z, width / height, supersample, threshold
 // (an entry without one passes 1, which every supersample admits).  The entry's own checks follow, then
@@ -871,6 +871,184 @@ int implisolid_debug_layer_distance_ms(int enable, double ms[3]) {
     g_dist_timing = enable != 0;
     if (ms)
         for (int k = 0; k < 3; ++k) ms[k] = g_dist_ms[k];
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- run-length layer images (implisolid_layer_runs) ---------------------------------------------------------
+// Per chunk, behind LayerImages' head, runs.hip's passes: count, the scan, a read-back of the chunk's per-layer
+// run offsets (their last entry sizes the records), emit, and the copy of the records into a pinned staging
+// slot.  There are two slots: the host appends a chunk from its slot to the result slot while the device works
+// on the next one.  The image stays on the device; runs never cross layers, so nothing is carried between
+// chunks.  Scratch of its own: 14 the row counts, their scan, its sums and the layer offsets, 0 the starts,
+// 1 the values.
+namespace {
+struct RunSlot {                 // the last call's runs; n < 0: none
+    PinnedVec<uint32_t> start;
+    PinnedVec<uint8_t> value;
+    int64_t n = -1;
+};
+RunSlot g_runs;
+struct RunStage {                // the staging slots, kept until exit (grow-only)
+    PinnedVec<uint32_t> start[2];
+    PinnedVec<uint8_t> value[2];
+    PinnedVec<int64_t> sums;
+};
+RunStage g_run_stage;
+bool g_run_timing = false;       // implisolid_debug_layer_runs_ms: HIP events around the launches
+double g_run_ms[3] = {-1.0, -1.0, -1.0};
+
+int64_t run_layers(const QueryShape& q, const LayerRequest& r, int threshold, int64_t* run_offsets, int64_t* layer_sum,
+                   int64_t stats[7]) {
+    Engine& E = *q.E;
+    hipStream_t s = q.s;
+    const int H = r.H, n_layers = r.n_layers;
+    LayerImages im(q, r, "runs", "IMPLISOLID_RUNS_CHUNK", kRunMaxChunk, true, g_run_timing);
+    const RunGrid rg = run_grid(r.W, H, im.g.pitch, threshold);
+    const uint32_t chunk_layers = im.chunk_layers;
+    const size_t rows_cap = (size_t)chunk_layers * (size_t)H;
+    // every reserve before any pointer is taken (the records' buffers, sized per chunk, hold nothing else)
+    E.scratch(14).reserve((2 * rows_cap + 1 + rows_cap / 4096 + 2 + (size_t)chunk_layers + 1) * sizeof(uint32_t));
+    uint32_t* d_counts = E.scratch(14).as<uint32_t>();
+    uint32_t* d_offsets = d_counts + rows_cap;
+    uint32_t* d_scan_sums = d_offsets + rows_cap + 1;
+    uint32_t* d_loff = d_scan_sums + rows_cap / 4096 + 2;
+    g_runs.start.resize(0);
+    g_runs.value.resize(0);
+    g_run_stage.sums.resize((size_t)n_layers);
+    EventSet<3> ev;   // behind im.ev[3], the end of the raster passes: count + scan; around emit
+    if (g_run_timing) {
+        ev.create();
+        for (double& m : g_run_ms) m = 0.0;
+    }
+    int64_t total = 0;
+    // the chunk whose records are on their way into a staging slot, not yet in the result slot
+    uint32_t pend = 0;
+    auto drain = [&](int slot) {   // after a synchronisation that covers the pending copy
+        if (pend) {
+            const size_t at = g_runs.start.size();
+            g_runs.start.resize(at + pend);
+            g_runs.value.resize(at + pend);
+            std::memcpy(g_runs.start.data() + at, g_run_stage.start[slot].data(), (size_t)pend * sizeof(uint32_t));
+            std::memcpy(g_runs.value.data() + at, g_run_stage.value[slot].data(), (size_t)pend);
+        }
+        pend = 0;
+    };
+    std::vector<uint32_t> loff((size_t)chunk_layers + 1);
+    while (im.next()) {   // its synchronisation: the last chunk's records have landed in the other slot
+        const int l0 = im.l0, slot = (int)((im.chunks - 1) & 1);
+        const uint32_t nl = im.nl;
+        const uint32_t rows = nl * (uint32_t)H;
+        launch_run_count(rg, nl, im.d_img, d_counts, s);
+        launch_scan_u32(d_counts, d_offsets, rows, d_scan_sums, false, s);
+        launch_slice_layer_offsets(d_offsets, (uint32_t)H, nl, d_loff, s);   // every H-th entry and the total
+        if (ev[0]) IMPLI_HIP(hipEventRecord(ev[0], s));
+        IMPLI_HIP(hipGetLastError());
+        IMPLI_HIP(hipMemcpyAsync(loff.data(), d_loff, ((size_t)nl + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        IMPLI_HIP(hipStreamSynchronize(s));
+        const uint32_t cc = loff[nl];   // the chunk's runs: one a layer at least
+        if (cc < nl) throw HipError("runs: a layer without a run");
+        if (total + (int64_t)cc >= ((int64_t)1 << 31)) throw InputError("implisolid_layer_runs: the result reaches 2^31 runs");
+        for (uint32_t k = 0; k < nl; ++k) run_offsets[l0 + (int)k] = total + loff[k];
+        E.scratch(0).reserve((size_t)cc * sizeof(uint32_t));
+        E.scratch(1).reserve((size_t)cc);
+        uint32_t* d_start = E.scratch(0).as<uint32_t>();
+        uint8_t* d_value = E.scratch(1).as<uint8_t>();
+        if (ev[1]) IMPLI_HIP(hipEventRecord(ev[1], s));
+        launch_run_emit(rg, nl, im.d_img, d_offsets, cc, d_start, d_value, s);
+        if (ev[2]) IMPLI_HIP(hipEventRecord(ev[2], s));
+        IMPLI_HIP(hipGetLastError());
+        g_run_stage.start[slot].resize(0);   // nothing of the chunk before last is kept
+        g_run_stage.value[slot].resize(0);
+        g_run_stage.start[slot].resize(cc);
+        g_run_stage.value[slot].resize(cc);
+        IMPLI_HIP(hipMemcpyAsync(g_run_stage.start[slot].data(), d_start, (size_t)cc * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        IMPLI_HIP(hipMemcpyAsync(g_run_stage.value[slot].data(), d_value, (size_t)cc, hipMemcpyDeviceToHost, s));
+        IMPLI_HIP(hipMemcpyAsync(g_run_stage.sums.data() + l0, im.d_sums + l0, (size_t)nl * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        drain(slot ^ 1);   // the chunk before this one, while the device works on this one
+        pend = cc;
+        total += cc;
+        if (ev[0]) {
+            float c = 0.f, d = 0.f;
+            IMPLI_HIP(hipStreamSynchronize(s));
+            IMPLI_HIP(hipEventElapsedTime(&c, im.ev[3], ev[0]));
+            IMPLI_HIP(hipEventElapsedTime(&d, ev[1], ev[2]));
+            g_run_ms[0] += im.raster_ms();
+            g_run_ms[1] += c;
+            g_run_ms[2] += d;
+        }
+    }
+    IMPLI_HIP(hipStreamSynchronize(s));
+    drain((int)((im.chunks - 1) & 1));
+    run_offsets[n_layers] = total;
+    // the records against their definition, and in grey mode against the device's sums
+    const int64_t layer_px = (int64_t)im.layer_px;
+    int64_t lit = 0;
+    for (int l = 0; l < n_layers; ++l) {
+        layer_sum[l] = g_run_stage.sums.data()[l];
+        const uint32_t* st = g_runs.start.data() + run_offsets[l];
+        const uint8_t* va = g_runs.value.data() + run_offsets[l];
+        const int64_t n = run_offsets[l + 1] - run_offsets[l];
+        if (n < 1 || st[0] != 0u) throw HipError("runs: a layer's first run does not start at pixel 0");
+        int64_t sum = 0;
+        for (int64_t k = 0; k < n; ++k) {
+            const int64_t end = k + 1 < n ? (int64_t)st[k + 1] : layer_px;
+            if (end <= (int64_t)st[k] || end > layer_px) throw HipError("runs: a layer's starts do not increase inside the layer");
+            sum += (int64_t)va[k] * (end - (int64_t)st[k]);
+            lit += va[k] != 0;
+        }
+        if (threshold == 0 && sum != layer_sum[l]) throw HipError("runs: the runs' coverage and the layer's sum disagree");
+    }
+    if (stats) {
+        im.stats(stats);
+        stats[5] = total;
+        stats[6] = lit;
+    }
+    return total;
+}
+}  // namespace
+
+extern "C" {
+
+int64_t implisolid_layer_runs(const char* shape_json, int ignore_root_matrix, const float rect[4], int width, int height,
+                              int supersample, const float* z, int n_layers, int threshold, int64_t* run_offsets,
+                              int64_t* layer_sum, int64_t stats[7]) {
+    last_error().clear();
+    g_runs.n = -1;   // whatever happens, the previous result is gone
+    if (!shape_json || !rect || !z || !run_offsets || !layer_sum) {
+        report("implisolid_layer_runs: bad arguments", false);
+        return -1;
+    }
+    return guard_device([&]() -> int64_t {
+        // the request first: bad input is refused before anything is compiled or reaches the device
+        LayerRequest r("layer_runs", rect, width, height, supersample, z, n_layers);
+        if (threshold < 0 || threshold > supersample * supersample)
+            throw InputError("implisolid_layer_runs: threshold must be 0 (grey) or in [1, supersample^2]");
+        r.sample();
+        QueryShape q(shape_json, ignore_root_matrix);
+        q.upload();
+        g_runs.n = run_layers(q, r, threshold, run_offsets, layer_sum, stats);
+        return g_runs.n;
+    });
+}
+
+int implisolid_layer_runs_copy(uint32_t* start, uint8_t* value) {
+    last_error().clear();
+    if (g_runs.n < 0 || !start || !value) {
+        report(g_runs.n < 0 ? "implisolid_layer_runs_copy: no runs to copy (the last implisolid_layer_runs failed, or none ran)"
+                            : "implisolid_layer_runs_copy: bad arguments", false);
+        return -1;
+    }
+    std::memcpy(start, g_runs.start.data(), (size_t)g_runs.n * sizeof(uint32_t));
+    std::memcpy(value, g_runs.value.data(), (size_t)g_runs.n);
+    return 0;
+}
+
+int implisolid_debug_layer_runs_ms(int enable, double ms[3]) {
+    g_run_timing = enable != 0;
+    if (ms)
+        for (int k = 0; k < 3; ++k) ms[k] = g_run_ms[k];
     return 0;
 }
 

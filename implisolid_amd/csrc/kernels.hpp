@@ -248,6 +248,28 @@ void launch_distance_rows(DistGrid g, uint32_t n_layers, int l0, int32_t* d_dist
 void launch_distance_unsupported(DistGrid g, uint32_t n_layers, int l0, int64_t reach2, const int32_t* d_dist, const int32_t* d_carry,
                                  unsigned long long* d_rec, hipStream_t s);
 
+// Run-length layer images (implisolid_layer_runs; DESIGN "Run-length layer images", runs.hip): the runs of
+// every layer's row-major stream p = py W + px over the real pixels of a chunk's image (as launch_raster_eval
+// and launch_raster_fill left it: n_layers x H rows of `pitch` bytes, pitch a multiple of 16).  A pixel's value
+// is its coverage byte (threshold 0) or cov >= threshold as 0 / 1; a run starts at p = 0 and wherever the value
+// differs from the stream's pixel before, across row ends too.  The launches go on s in the order count, scan of
+// d_counts (launch_scan_u32), launch_slice_layer_offsets with tpl = H, emit; only the chunk's per-layer offsets
+// are read back, between the scan and emit, to size the records.
+struct RunGrid {
+    int W, H;            // pixels per axis
+    uint32_t pitch;      // bytes per image row
+    int threshold;       // 0: the value is the coverage byte
+};
+constexpr uint32_t kRunMaxChunk = 1u << 20;       // (layer, raster tile) pairs per chunk, as kRasterMaxChunk: a 256 MiB image
+constexpr uint64_t kRunMaxPixels = 1ull << 28;    // what one launch takes: a chunk is never less than one layer
+RunGrid run_grid(int W, int H, uint32_t pitch, int threshold);
+// count: d_counts[layer * H + py] = the runs that start in the row
+void launch_run_count(RunGrid g, uint32_t n_layers, const uint8_t* d_img, uint32_t* d_counts, hipStream_t s);
+// emit: per run its start (p within its layer) and value, in (layer, start) order; d_offsets: the exclusive scan
+// of d_counts, total: its last entry (nothing is written at or past it)
+void launch_run_emit(RunGrid g, uint32_t n_layers, const uint8_t* d_img, const uint32_t* d_offsets, uint32_t total,
+                     uint32_t* d_start, uint8_t* d_value, hipStream_t s);
+
 // Rays against the solid (implisolid_raycast; DESIGN "Rays against the solid", raycast.hip): per ray the
 // first solid sample of the table d_ts (host.hpp ray_params, N + 1 floats), the bisection inside its
 // bracket and the normal there.  One chunk = n rays (3 n floats of origins and directions each); both

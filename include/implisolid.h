@@ -486,6 +486,53 @@ int implisolid_layer_distance(const char* shape_json, int ignore_root_matrix, co
  * milliseconds summed over its chunks, -1 before any.  Returns 0 */
 int implisolid_debug_layer_distance_ms(int enable, double ms[3]);
 
+/* Additive: the layer images as run-length streams on the GPU -- what a resin printer's file formats store
+ * and what a slicer finally hands over, without downloading a pixel (no reference counterpart).  Arguments,
+ * limits and refusals are implisolid_raster's, in the same order: shape_json, ignore_root_matrix, rect, width,
+ * height in [1, 16384], supersample s in {1, 2, 4}, z, n_layers; further
+ *   threshold     0, or in [1, s^2]; anything else is refused
+ * cov[l][py][px] is exactly implisolid_raster's: the same sample tables, the same rule !(F < 0), -0.0 and NaN
+ * solid.  The pixel's value v is
+ *   threshold == 0        the grey mode: v = cov, a byte in 0 .. s^2
+ *   threshold in [1, s^2] the binary mode: v = (cov >= threshold) ? 1 : 0
+ * A layer is the stream of its W H pixels in row-major order, p = py * W + px for p in [0, W H): the W pixels of
+ * row 0 (the row at ymin), then those of row 1, and so on; nothing stands between a row's last pixel and the
+ * next row's first.  A run starts at p = 0 and at every p > 0 with v[p] != v[p - 1]; it ends in front of the
+ * next start, or at W H.  Runs therefore cross row ends (the pixel before (0, py) is (W - 1, py - 1)), runs of
+ * value 0 are listed like any other, the runs partition the layer, and every layer has at least one run.  Runs
+ * never cross layers.  Layers are taken in the caller's order (repeated and unsorted planes are legal).
+ * One record per run:
+ *   start   uint32, the run's first p (W H <= 2^28)
+ *   value   uint8, its v
+ * in increasing start.  A run's length is the next run's start minus its own, or W H - start for the last run
+ * of its layer.
+ *   run_offsets  n_layers + 1 entries: layer l's runs are [run_offsets[l], run_offsets[l + 1])
+ *   layer_sum    implisolid_raster's: the sum of cov[l] (n_layers entries; required).  In the grey mode it
+ *                equals the sum of value * length over the layer's runs
+ *   stats        (may be NULL) implisolid_raster's five figures, then the runs and the runs with value != 0
+ *   returns      the total number of runs, or -1 with implisolid_last_error(): implisolid_raster's refusals, a
+ *                bad threshold, run_offsets or layer_sum NULL, or 2^31 runs or more; bad input is refused
+ *                before anything is compiled or reaches a device
+ * The runs stay in one library-owned host slot until the next implisolid_layer_runs call; a failed call empties
+ * the slot.  implisolid_layer_runs_copy copies them out (start: that many uint32, value: that many bytes): 0,
+ * or -1 when there is nothing to copy or a pointer is NULL.
+ * Everything is an integer: no result depends on the pruning level, the chunking or the launch geometry, and
+ * there is no atomic on the way from the image to the runs.  The image never leaves the device: per chunk only
+ * the runs come down, through two pinned staging slots; before returning the library checks that every layer's
+ * first start is 0, that its starts increase strictly below W H and, in the grey mode, that the runs add up to
+ * layer_sum.  Layers are processed in chunks of whole layers of at most IMPLISOLID_RUNS_CHUNK (layer, 16 x 16
+ * tile) pairs (environment, read at each call; default and maximum 2^20, at least one layer's tiles): 2^28
+ * pixels, a 256 MiB image, and 5 bytes of device and staging memory per run of the chunk.  One device, the
+ * interpreter kernels. */
+int64_t implisolid_layer_runs(const char* shape_json, int ignore_root_matrix, const float rect[4], int width, int height,
+                              int supersample, const float* z, int n_layers, int threshold, int64_t* run_offsets,
+                              int64_t* layer_sum, int64_t stats[7]);
+int implisolid_layer_runs_copy(uint32_t* start, uint8_t* value);
+/* diagnostics: with enable != 0 the following implisolid_layer_runs calls time their kernels with HIP events;
+ * ms (may be NULL) = the last timed call's {raster passes, count pass and scan, emit pass} milliseconds summed
+ * over its chunks, -1 before any.  Returns 0 */
+int implisolid_debug_layer_runs_ms(int enable, double ms[3]);
+
 /* Additive: rays cast at the solid on the GPU -- per ray the first hit, its distance, the field value
  * and the normal there (no reference counterpart: the reference front end ray-casts the mesh).
  *   origins, dirs  3 n floats each, n in [0, 2^24], every float finite.  A direction need not have unit
