@@ -909,12 +909,21 @@ def islands_of(comps):
     return comps[comps["below"] == 0]
 
 
+def _pass_ms(query, n, enable):
+    """implisolid_debug_<query>_ms: sets the timing switch and returns the last timed call's n figures as a tuple
+    (n None: the entry returns its one figure itself)."""
+    fn = getattr(lib(), "implisolid_debug_%s_ms" % query)
+    if n is None:
+        return float(fn(int(bool(enable))))
+    ms = (ctypes.c_double * n)()
+    fn(int(bool(enable)), ms)
+    return tuple(float(v) for v in ms)
+
+
 def islands_kernel_ms(enable=True):
     """Diagnostics: switch the event timing of layer_islands()'s kernels on or off; returns the last timed
     call's (raster passes, tile pass, merge pass, seed rows + scan, records + tally) ms, -1 before any."""
-    ms = (ctypes.c_double * 5)()
-    lib().implisolid_debug_islands_ms(int(bool(enable)), ms)
-    return tuple(float(v) for v in ms)
+    return _pass_ms("islands", 5, enable)
 
 
 DIST_DTYPE = np.dtype([(name, np.int64) for name in ("solid", "widest", "widest_at", "unsupported")])
@@ -974,9 +983,7 @@ def overhang_mask(dist, reach2):
 def layer_distance_kernel_ms(enable=True):
     """Diagnostics: switch the event timing of layer_distance()'s kernels on or off; returns the last timed
     call's (raster passes, column pass, row pass + records) ms, -1 before any."""
-    ms = (ctypes.c_double * 3)()
-    lib().implisolid_debug_layer_distance_ms(int(bool(enable)), ms)
-    return tuple(float(v) for v in ms)
+    return _pass_ms("layer_distance", 3, enable)
 
 
 def layer_runs(shape, rect, width, height, z, supersample=1, threshold=0, ignore_root_matrix=False, return_stats=False):
@@ -1032,9 +1039,7 @@ def runs_decode(run_offsets, start, value, width, height):
 def layer_runs_kernel_ms(enable=True):
     """Diagnostics: switch the event timing of layer_runs()'s kernels on or off; returns the last timed call's
     (raster passes, count pass + scan, emit pass) ms, -1 before any."""
-    ms = (ctypes.c_double * 3)()
-    lib().implisolid_debug_layer_runs_ms(int(bool(enable)), ms)
-    return tuple(float(v) for v in ms)
+    return _pass_ms("layer_runs", 3, enable)
 
 
 def ray_params(t0, t1, steps):
@@ -1148,9 +1153,7 @@ def render_view(shape, eye, target, up, width, height, t0, t1, steps, bisect=16,
 def raycast_kernel_ms(enable=True):
     """Diagnostics: switch the event timing of raycast()'s kernels on or off; returns the last timed
     call's (march ms, finish ms), -1 before any."""
-    ms = (ctypes.c_double * 2)()
-    lib().implisolid_debug_raycast_ms(int(bool(enable)), ms)
-    return float(ms[0]), float(ms[1])
+    return _pass_ms("raycast", 2, enable)
 
 
 def ray_spans(shape, origins, dirs, t0, t1, steps, bisect=16, ignore_root_matrix=False, want_normals=False, return_stats=False):
@@ -1216,9 +1219,7 @@ def xray_view(shape, eye, target, up, width, height, t0, t1, steps, bisect=16, f
 def ray_spans_kernel_ms(enable=True):
     """Diagnostics: switch the event timing of ray_spans()'s kernels on or off; returns the last timed
     call's (march ms, scan + tally + emit ms, refine ms), -1 before any."""
-    ms = (ctypes.c_double * 3)()
-    lib().implisolid_debug_ray_spans_ms(int(bool(enable)), ms)
-    return float(ms[0]), float(ms[1]), float(ms[2])
+    return _pass_ms("ray_spans", 3, enable)
 
 
 def mass_mids(box, depth):
@@ -1304,7 +1305,7 @@ def last_fit_box():
 def debug_bounds_ms(enable=True):
     """Diagnostics: switch HIP-event timing of the bounds descent's level launches on or off; returns
     the last timed descent's milliseconds (-1.0: none yet)."""
-    return float(lib().implisolid_debug_bounds_ms(int(bool(enable))))
+    return _pass_ms("bounds", None, enable)
 
 
 def debug_eval_modes(shape, pts, modes, ignore_root_matrix=False):

@@ -150,6 +150,114 @@ struct EventSet {
     hipEvent_t operator[](int k) const { return e[k]; }   // null unless created
 };
 
+// What follows to the state block is the queries' own host scaffolding: in an unnamed namespace, so that none of
+// it adds to the library's exported symbols.
+namespace {
+
+// ---- a query's pass timer (implisolid_debug_<query>_ms) ---------------------------------------------------
+// The contract: the figures are -1 before any timed call; a timed call zeroes them at its start and adds each
+// chunk's intervals; an untimed call leaves the last timed call's figures; the switch is read at the start of
+// a call.  PassTimer is the query's global: the switch and the N figures.  Timed is a call's own: its E events,
+// null in an untimed call, where mark() does nothing and the call, tested as a bool, skips its add()s.
+template <int N>
+struct PassTimer {
+    bool on = false;
+    double ms[N];
+    PassTimer() { std::fill(ms, ms + N, -1.0); }
+    int entry(int enable, double* out) {   // the debug entry: sets the switch, copies the last figures out
+        on = enable != 0;
+        if (out) std::copy(ms, ms + N, out);
+        return 0;
+    }
+};
+template <int N, int E>
+struct Timed {
+    PassTimer<N>& t;
+    EventSet<E> ev;
+    explicit Timed(PassTimer<N>& t, bool zero = true) : t(t) {
+        if (!t.on) return;
+        ev.create();
+        if (zero) std::fill(t.ms, t.ms + N, 0.0);
+    }
+    explicit operator bool() const { return ev[0] != nullptr; }
+    void mark(int k, hipStream_t s) {
+        if (ev[k]) IMPLI_HIP(hipEventRecord(ev[k], s));
+    }
+    static float elapsed(hipEvent_t a, hipEvent_t b) {   // both recorded, and the stream synchronised behind b
+        float ms = 0.f;
+        IMPLI_HIP(hipEventElapsedTime(&ms, a, b));
+        return ms;
+    }
+    void add(int k, hipEvent_t a, hipEvent_t b) { t.ms[k] += elapsed(a, b); }
+    void add(int k, float ms) { t.ms[k] += ms; }
+};
+
+// ---- a counted output: per-item counts -> offsets -> records ------------------------------------------------
+// A chunk's items (tiles, rows, rays) each count their records; the exclusive scan of the counts places them,
+// and the host needs the offset of every group of `stride` items (a layer's tiles or rows) and the chunk's
+// total, which sizes the records.  stride 0: every item is a group of its own (a ray), and the offsets are read
+// back as they are, with no gather.  The constructor carves the scan's buffers for at most cap items out of b,
+// which holds nothing else: the counts unless the query keeps them elsewhere, cap + 1 offsets, launch_scan_u32's
+// sums, and with a stride the group offsets.
+struct CountedOutput {
+    uint32_t *d_counts, *d_offsets, *d_sums, *d_groups;
+    uint32_t stride;
+    std::vector<uint32_t> off;   // the chunk's group offsets and its total, read back
+
+    CountedOutput(DevBuf& b, size_t cap, uint32_t stride, uint32_t* counts_elsewhere = nullptr) : stride(stride) {
+        const size_t counts = counts_elsewhere ? 0 : cap, sums = cap / 4096 + 2, groups = stride ? cap / stride + 1 : 0;
+        b.reserve((counts + cap + 1 + sums + groups) * sizeof(uint32_t));
+        d_counts = counts_elsewhere ? counts_elsewhere : b.as<uint32_t>();
+        d_offsets = b.as<uint32_t>() + counts;
+        d_sums = d_offsets + cap + 1;
+        d_groups = stride ? d_sums + sums : d_offsets;
+        off.resize(stride ? groups : cap + 1);
+    }
+
+    // Behind the launch that filled d_counts for `groups` groups: enqueues the scan (and the gather of every
+    // stride-th offset, with a stride), then behind() -- what the query enqueues ahead of the read-back --, reads the group
+    // offsets back and synchronises the stream.  A result of total + the chunk's records >= 2^31 is refused with
+    // `limit`; else out[k] = total + the offset of group k, and the chunk's records are returned.
+    template <class Behind>
+    uint32_t place(uint32_t groups, hipStream_t s, int64_t total, const char* limit, int64_t* out, Behind&& behind) {
+        launch_scan_u32(d_counts, d_offsets, (int64_t)groups * (stride ? stride : 1), d_sums, false, s);
+        if (stride) launch_slice_layer_offsets(d_offsets, stride, groups, d_groups, s);
+        behind();
+        IMPLI_HIP(hipGetLastError());
+        IMPLI_HIP(hipMemcpyAsync(off.data(), d_groups, ((size_t)groups + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        IMPLI_HIP(hipStreamSynchronize(s));
+        const uint32_t* h = off.data();   // a local: the loop below runs over a million rays
+        const uint32_t records = h[groups];
+        if (total + (int64_t)records >= ((int64_t)1 << 31)) throw InputError(limit);
+        for (uint32_t k = 0; k < groups; ++k) out[k] = total + h[k];
+        return records;
+    }
+    uint32_t place(uint32_t groups, hipStream_t s, int64_t total, const char* limit, int64_t* out) {
+        return place(groups, s, total, limit, out, [] {});
+    }
+};
+
+// ---- the result slot of a query whose records the caller fetches with implisolid_<entry>_copy ----------------
+// n < 0: none.  The entry resets the slot before anything else -- whatever happens, the previous result is gone
+// -- and publishes the count behind the last pass.  A query's slot adds its pinned arrays.
+struct ResultSlot {
+    int64_t n = -1;
+    void reset() { n = -1; }
+    int64_t publish(int64_t count) { return n = count; }
+    // The head of implisolid_<entry>_copy: clears the last error; true, with the refusal reported, where there
+    // is no result or the caller's pointers do not serve (have_pointers: as the entry requires them).
+    bool refuses_copy(const std::string& entry, const char* noun, bool have_pointers) const {
+        last_error().clear();
+        if (n >= 0 && have_pointers) return false;
+        const std::string who = "implisolid_" + entry;
+        report(n < 0 ? who + "_copy: no " + noun + " to copy (the last " + who + " failed, or none ran)" : who + "_copy: bad arguments",
+               false);
+        return true;
+    }
+};
+
+}  // namespace
+
 // ---- the state block of a query's passes ------------------------------------------------------------------
 // kStateBytes at the head of a scratch buffer hold the passes' State; the query's tables follow
 constexpr size_t kStateBytes = 256;

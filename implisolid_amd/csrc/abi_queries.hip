@@ -2,7 +2,9 @@
 // their islands, distance fields and run-length streams, rays and mass properties.  Each entry validates its request, compiles
 // the shape (QueryShape), puts it on the device and runs its passes; the scaffolding is abi_common.hpp's.
 // The four layer queries share their request (LayerRequest) and the passes that make a chunk's image
-// (LayerImages): each reads as what it does with the image.  The two ray queries share ray_request.
+// (LayerImages): each reads as what it does with the image.  The two ray queries share ray_request.  Slice,
+// islands, runs and ray spans place their records with abi_common.hpp's CountedOutput and keep them in a
+// ResultSlot; the timed queries keep their figures in a PassTimer.
 #include <cmath>
 #include <cstring>
 #include <stdexcept>
@@ -111,8 +113,7 @@ int implisolid_debug_eval_modes(const char* shape_json, int ignore_root_matrix, 
 // `search` (else out = search); stats (nullable): boxes bounded, boxes skipped as inside the running
 // bounds, longest list, reruns after overflow.
 namespace {
-bool g_bounds_timing = false;   // implisolid_debug_bounds_ms: HIP events around the level launches
-double g_bounds_ms = -1.0;
+PassTimer<1> g_bounds_timer;   // implisolid_debug_bounds_ms: HIP events around the level launches
 }  // namespace
 
 bool impli::cabi::compute_bounds(Engine& E, hipStream_t s, const Program* d_prog, int prog_depth, const float* d_tab,
@@ -128,8 +129,7 @@ bool impli::cabi::compute_bounds(Engine& E, hipStream_t s, const Program* d_prog
     uint32_t cap = list_capacity("IMPLISOLID_BOUNDS_LIST", depth);
     int64_t reruns = 0;
     BoundsState h{};
-    EventSet<2> ev;
-    if (g_bounds_timing) ev.create();
+    Timed<1, 2> tm(g_bounds_timer, false);   // the last descent's figure is assigned, not added up
     for (;;) {
         uint32_t* d_box[2];
         uint64_t* d_modes[2];
@@ -139,21 +139,17 @@ bool impli::cabi::compute_bounds(Engine& E, hipStream_t s, const Program* d_prog
             d_box[k] = E.scratch(11 + k).as<uint32_t>();
             d_modes[k] = E.scratch(13 + k).as<uint64_t>();
         }
-        if (ev[0]) IMPLI_HIP(hipEventRecord(ev[0], s));
+        tm.mark(0, s);
         launch_bounds_levels(d_prog, prog_depth, d_tab, E.tab_range(), d_edges, depth, d_box, d_modes, cap, d_state, s);
         IMPLI_HIP(hipGetLastError());
-        if (ev[1]) IMPLI_HIP(hipEventRecord(ev[1], s));
+        tm.mark(1, s);
         IMPLI_HIP(hipMemcpyAsync(&h, d_state, sizeof h, hipMemcpyDeviceToHost, s));
         IMPLI_HIP(hipStreamSynchronize(s));
         if (!h.overflow) break;
         cap = grown_capacity("bounds", cap, h.count, kBoundsMinDepth, depth);
         ++reruns;
     }
-    if (ev[0]) {
-        float ms = 0.f;
-        IMPLI_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        g_bounds_ms = ms;
-    }
+    if (tm) g_bounds_timer.ms[0] = tm.elapsed(tm.ev[0], tm.ev[1]);
     const bool found = h.key[0] != 0xffffffffu;
     for (int a = 0; a < 6; ++a) {
         const uint32_t bits = bounds_key_bits(h.key[a]);
@@ -194,8 +190,8 @@ int implisolid_bounds(const char* shape_json, int ignore_root_matrix, const floa
 }
 
 double implisolid_debug_bounds_ms(int enable) {
-    g_bounds_timing = enable != 0;
-    return g_bounds_ms;
+    g_bounds_timer.on = enable != 0;
+    return g_bounds_timer.ms[0];
 }
 
 int implisolid_bounds_edges(const float search[6], int depth, float* edges) {
@@ -222,16 +218,16 @@ int implisolid_fit_box(const float search[6], const float bounds[6], int resolut
 // and emit grids), march, scan, a read-back of the chunk's per-layer offsets and total (they size
 // the output), emit, and the copy into the host slot at the running offset.  E lends its scratch.
 namespace {
-struct SliceSlot {               // the last slice's result; n < 0: none
+struct SliceSlot : ResultSlot {  // the last slice's result
     PinnedVec<float> xy;
     PinnedVec<uint32_t> keys;
-    int64_t n = -1;
 };
 SliceSlot g_slice;
 
-int64_t slice_layers(Engine& E, hipStream_t s, const Program* d_prog, int prog_depth, const float* d_tab, int R,
-                     const std::vector<float>& xs, const std::vector<float>& ys, const float* z, int n_layers,
-                     int64_t* layer_offsets, int64_t stats[4]) {
+int64_t slice_layers(const QueryShape& q, int R, const std::vector<float>& xs, const std::vector<float>& ys, const float* z,
+                     int n_layers, int64_t* layer_offsets, int64_t stats[4]) {
+    Engine& E = *q.E;
+    hipStream_t s = q.s;
     SliceGrid g;
     g.R = R;
     g.ntx = (R + kSliceTile - 1) / kSliceTile;
@@ -245,8 +241,6 @@ int64_t slice_layers(Engine& E, hipStream_t s, const Program* d_prog, int prog_d
     E.scratch(11).reserve((size_t)cap * sizeof(uint32_t));                        // list
     E.scratch(12).reserve((size_t)cap * sizeof(uint32_t));                        // counts
     E.scratch(13).reserve((size_t)cap * sizeof(uint64_t));                        // the listed tiles' modes
-    E.scratch(14).reserve(((size_t)cap + 1 + cap / 4096 + 2) * sizeof(uint32_t)); // offsets, then the scan's sums
-    E.scratch(9).reserve(((size_t)chunk_layers + 1) * sizeof(uint32_t));          // per-layer offsets
     SliceState* d_state = E.scratch(10).as<SliceState>();
     float* d_xs = behind_state<SliceState>(E.scratch(10));
     float* d_ys = d_xs + W;
@@ -254,23 +248,20 @@ int64_t slice_layers(Engine& E, hipStream_t s, const Program* d_prog, int prog_d
     uint32_t* d_list = E.scratch(11).as<uint32_t>();
     uint32_t* d_counts = E.scratch(12).as<uint32_t>();
     uint64_t* d_lmodes = E.scratch(13).as<uint64_t>();
-    uint32_t* d_offsets = E.scratch(14).as<uint32_t>();
-    uint32_t* d_sums = d_offsets + cap + 1;
-    uint32_t* d_loff = E.scratch(9).as<uint32_t>();
+    CountedOutput segments(E.scratch(14), cap, g.tpl, d_counts);   // a tile's segments, a layer's offset
     IMPLI_HIP(hipMemcpyAsync(d_xs, xs.data(), W * sizeof(float), hipMemcpyHostToDevice, s));
     IMPLI_HIP(hipMemcpyAsync(d_ys, ys.data(), W * sizeof(float), hipMemcpyHostToDevice, s));
     IMPLI_HIP(hipMemcpyAsync(d_z, z, (size_t)n_layers * sizeof(float), hipMemcpyHostToDevice, s));
     g_slice.xy.resize(0);
     g_slice.keys.resize(0);
     int64_t total = 0, listed = 0, samples = 0, chunks = 0;
-    std::vector<uint32_t> loff((size_t)chunk_layers + 1);
     for (int l0 = 0; l0 < n_layers; l0 += (int)chunk_layers, ++chunks) {
         const uint32_t nl = (uint32_t)std::min<int64_t>(chunk_layers, n_layers - l0);
         const uint32_t n = nl * g.tpl;
         const int64_t first = (int64_t)l0 * g.tpl;
         IMPLI_HIP(hipMemsetAsync(d_state, 0, sizeof(SliceState), s));
         IMPLI_HIP(hipMemsetAsync(d_counts, 0, (size_t)n * sizeof(uint32_t), s));
-        launch_slice_classify(d_prog, prog_depth, d_tab, E.tab_range(), d_xs, d_ys, d_z, g, first, n, prune, d_list, d_lmodes,
+        launch_slice_classify(q.d_prog, q.max_depth, q.d_tab, E.tab_range(), d_xs, d_ys, d_z, g, first, n, prune, d_list, d_lmodes,
                               d_state, s);
         IMPLI_HIP(hipGetLastError());
         SliceState h{};
@@ -283,19 +274,13 @@ int64_t slice_layers(Engine& E, hipStream_t s, const Program* d_prog, int prog_d
         if (h.n_listed) {
             E.scratch(15).reserve((size_t)h.n_listed * kSliceSamples * sizeof(float));
             float* d_samples = E.scratch(15).as<float>();
-            launch_slice_march(d_prog, prog_depth, d_tab, d_xs, d_ys, d_z, g, first, h.n_listed, d_list, d_lmodes, d_samples,
+            launch_slice_march(q.d_prog, q.max_depth, q.d_tab, d_xs, d_ys, d_z, g, first, h.n_listed, d_list, d_lmodes, d_samples,
                                d_counts, s);
-            launch_scan_u32(d_counts, d_offsets, n, d_sums, false, s);
-            launch_slice_layer_offsets(d_offsets, g.tpl, nl, d_loff, s);
-            IMPLI_HIP(hipGetLastError());
-            IMPLI_HIP(hipMemcpyAsync(loff.data(), d_loff, ((size_t)nl + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            IMPLI_HIP(hipStreamSynchronize(s));
-            chunk_total = loff[nl];
-            if (total + (int64_t)chunk_total >= ((int64_t)1 << 31)) throw InputError("implisolid_slice: the slice reaches 2^31 segments");
+            chunk_total = segments.place(nl, s, total, "implisolid_slice: the slice reaches 2^31 segments", layer_offsets + l0);
             if (chunk_total) {
                 E.scratch(0).reserve((size_t)chunk_total * 4 * sizeof(float));
                 E.scratch(1).reserve((size_t)chunk_total * 2 * sizeof(uint32_t));
-                launch_slice_emit(d_xs, d_ys, g, first, h.n_listed, d_list, d_samples, d_offsets, chunk_total,
+                launch_slice_emit(d_xs, d_ys, g, first, h.n_listed, d_list, d_samples, segments.d_offsets, chunk_total,
                                   E.scratch(0).as<float>(), E.scratch(1).as<uint32_t>(), s);
                 IMPLI_HIP(hipGetLastError());
                 g_slice.xy.resize((size_t)(total + chunk_total) * 4);
@@ -307,9 +292,8 @@ int64_t slice_layers(Engine& E, hipStream_t s, const Program* d_prog, int prog_d
                 IMPLI_HIP(hipStreamSynchronize(s));
             }
         } else {
-            std::fill(loff.begin(), loff.end(), 0u);
+            std::fill(layer_offsets + l0, layer_offsets + l0 + nl, total);   // nothing listed: no scan, no segments
         }
-        for (uint32_t k = 0; k < nl; ++k) layer_offsets[l0 + (int)k] = total + loff[k];
         total += chunk_total;
     }
     layer_offsets[n_layers] = total;
@@ -328,7 +312,7 @@ extern "C" {
 int64_t implisolid_slice(const char* shape_json, int ignore_root_matrix, const float rect[4], int resolution, const float* z,
                          int n_layers, int64_t* layer_offsets, int64_t stats[4]) {
     last_error().clear();
-    g_slice.n = -1;   // whatever happens, the previous result is gone
+    g_slice.reset();
     if (!shape_json || !rect || !z || !layer_offsets) {
         report("implisolid_slice: bad arguments", false);
         return -1;
@@ -343,18 +327,12 @@ int64_t implisolid_slice(const char* shape_json, int ignore_root_matrix, const f
         slice_coords(rect, resolution, xs.data(), ys.data());
         QueryShape q(shape_json, ignore_root_matrix);
         q.upload();
-        g_slice.n = slice_layers(*q.E, q.s, q.d_prog, q.max_depth, q.d_tab, resolution, xs, ys, z, n_layers, layer_offsets, stats);
-        return g_slice.n;
+        return g_slice.publish(slice_layers(q, resolution, xs, ys, z, n_layers, layer_offsets, stats));
     });
 }
 
 int implisolid_slice_copy(float* xy, uint32_t* keys) {
-    last_error().clear();
-    if (g_slice.n < 0 || (g_slice.n > 0 && (!xy || !keys))) {
-        report(g_slice.n < 0 ? "implisolid_slice_copy: no slice to copy (the last implisolid_slice failed, or none ran)"
-                             : "implisolid_slice_copy: bad arguments", false);
-        return -1;
-    }
+    if (g_slice.refuses_copy("slice", "slice", g_slice.n == 0 || (xy && keys))) return -1;
     if (g_slice.n > 0) {
         std::memcpy(xy, g_slice.xy.data(), (size_t)g_slice.n * 4 * sizeof(float));
         std::memcpy(keys, g_slice.keys.data(), (size_t)g_slice.n * 2 * sizeof(uint32_t));
@@ -607,74 +585,53 @@ int implisolid_raster_coords(const float rect[4], int width, int height, int sup
 // chunk's per-layer record offsets (their last entry sizes the records), roots, tally, and the copies of the
 // records into the host slot and of the labels, when asked for, into the caller's array.  The image stays on
 // the device: the last layer of a chunk is copied to a carry buffer for the first layer of the next.  Scratch
-// of its own: 14 the row counts, their scan, its sums and the layer offsets, 0 the labels, 1 the records, 2 the
-// carried layer.
+// of its own: 14 the counted output over the rows, 0 the labels, 1 the records, 2 the carried layer.
 namespace {
-struct IslandSlot {              // the last call's records; n < 0: none
+struct IslandSlot : ResultSlot {   // the last call's records
     PinnedVec<int32_t> comps;
-    int64_t n = -1;
 };
 IslandSlot g_islands;
-bool g_island_timing = false;    // implisolid_debug_islands_ms: HIP events around the launches
-double g_island_ms[5] = {-1.0, -1.0, -1.0, -1.0, -1.0};
+PassTimer<5> g_island_timer;     // implisolid_debug_islands_ms: HIP events around the launches
 
 int64_t island_layers(const QueryShape& q, const LayerRequest& r, int threshold, int connectivity, int64_t* comp_offsets,
                       int32_t* labels, int64_t stats[8]) {
     Engine& E = *q.E;
     hipStream_t s = q.s;
     const int H = r.H, n_layers = r.n_layers;
-    LayerImages im(q, r, "islands", "IMPLISOLID_ISLANDS_CHUNK", kIslandMaxChunk, true, g_island_timing);
+    LayerImages im(q, r, "islands", "IMPLISOLID_ISLANDS_CHUNK", kIslandMaxChunk, true, g_island_timer.on);
     const IslandGrid ig = island_grid(r.W, H, im.g.pitch, threshold, connectivity);
     const uint32_t chunk_layers = im.chunk_layers;
     const size_t layer_img = im.layer_img, layer_px = im.layer_px;
-    const size_t rows_cap = (size_t)chunk_layers * (size_t)H;
     // every reserve before any pointer is taken (the records' buffer, sized per chunk, holds nothing else)
-    E.scratch(14).reserve((2 * rows_cap + 1 + rows_cap / 4096 + 2 + (size_t)chunk_layers + 1) * sizeof(uint32_t));
+    CountedOutput comps(E.scratch(14), (size_t)chunk_layers * (size_t)H, (uint32_t)H);   // a row's seeds, a layer's offset
     E.scratch(0).reserve((size_t)chunk_layers * layer_px * sizeof(int32_t));   // labels
     if (n_layers > (int)chunk_layers) E.scratch(2).reserve(layer_img);     // the carried layer
     static_assert(sizeof(RasterState) + sizeof(IslandState) <= kStateBytes, "both states share the state block");
     IslandState* d_istate = reinterpret_cast<IslandState*>(im.d_state + 1);
     uint8_t* d_img = im.d_img;
-    uint32_t* d_counts = E.scratch(14).as<uint32_t>();
-    uint32_t* d_offsets = d_counts + rows_cap;
-    uint32_t* d_scan_sums = d_offsets + rows_cap + 1;
-    uint32_t* d_loff = d_scan_sums + rows_cap / 4096 + 2;
     int32_t* d_lab = E.scratch(0).as<int32_t>();
     uint8_t* d_carry = n_layers > (int)chunk_layers ? E.scratch(2).as<uint8_t>() : nullptr;
     IMPLI_HIP(hipMemsetAsync(d_istate, 0, sizeof(IslandState), s));
     g_islands.comps.resize(0);
-    EventSet<5> ev;   // behind im.ev[3], the end of the raster passes: tiles, merge, rows + scan; around roots + tally
-    if (g_island_timing) {
-        ev.create();
-        for (double& m : g_island_ms) m = 0.0;
-    }
+    Timed<5, 5> tm(g_island_timer);   // behind im.ev[3], the end of the raster passes: tiles, merge, rows + scan; around roots + tally
     int64_t total = 0;
-    std::vector<uint32_t> loff((size_t)chunk_layers + 1);
     while (im.next()) {
         const int l0 = im.l0;
         const uint32_t nl = im.nl;
         launch_island_tiles(ig, nl, d_img, d_lab, d_istate, s);
-        if (ev[0]) IMPLI_HIP(hipEventRecord(ev[0], s));
+        tm.mark(0, s);
         launch_island_merge(ig, nl, d_lab, s);
-        if (ev[1]) IMPLI_HIP(hipEventRecord(ev[1], s));
-        const uint32_t rows = nl * (uint32_t)H;
-        launch_island_rows(ig, nl, d_lab, d_counts, s);
-        launch_scan_u32(d_counts, d_offsets, rows, d_scan_sums, false, s);
-        launch_slice_layer_offsets(d_offsets, (uint32_t)H, nl, d_loff, s);   // every H-th entry and the total
-        if (ev[2]) IMPLI_HIP(hipEventRecord(ev[2], s));
-        IMPLI_HIP(hipGetLastError());
-        IMPLI_HIP(hipMemcpyAsync(loff.data(), d_loff, ((size_t)nl + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        IMPLI_HIP(hipStreamSynchronize(s));
-        const uint32_t cc = loff[nl];   // the chunk's components
-        if (total + (int64_t)cc >= ((int64_t)1 << 31)) throw InputError("implisolid_islands: the result reaches 2^31 components");
-        for (uint32_t k = 0; k < nl; ++k) comp_offsets[l0 + (int)k] = total + loff[k];
+        tm.mark(1, s);
+        launch_island_rows(ig, nl, d_lab, comps.d_counts, s);
+        const uint32_t cc = comps.place(nl, s, total, "implisolid_islands: the result reaches 2^31 components", comp_offsets + l0,
+                                        [&] { tm.mark(2, s); });   // the chunk's components
         if (cc) {
             E.scratch(1).reserve((size_t)cc * 8 * sizeof(int32_t));
             int32_t* d_rec = E.scratch(1).as<int32_t>();
-            if (ev[3]) IMPLI_HIP(hipEventRecord(ev[3], s));
-            launch_island_roots(ig, nl, l0, d_lab, d_offsets, cc, d_rec, s);
-            launch_island_tally(ig, nl, l0, d_img, d_carry, d_lab, d_loff, d_rec, s);
-            if (ev[4]) IMPLI_HIP(hipEventRecord(ev[4], s));
+            tm.mark(3, s);
+            launch_island_roots(ig, nl, l0, d_lab, comps.d_offsets, cc, d_rec, s);
+            launch_island_tally(ig, nl, l0, d_img, d_carry, d_lab, comps.d_groups, d_rec, s);
+            tm.mark(4, s);
             IMPLI_HIP(hipGetLastError());
             g_islands.comps.resize((size_t)(total + cc) * 8);
             IMPLI_HIP(hipMemcpyAsync(g_islands.comps.data() + 8 * (size_t)total, d_rec, (size_t)cc * 8 * sizeof(int32_t),
@@ -687,17 +644,12 @@ int64_t island_layers(const QueryShape& q, const LayerRequest& r, int threshold,
         if (l0 + (int)nl < n_layers)
             IMPLI_HIP(hipMemcpyAsync(d_carry, d_img + (size_t)(nl - 1) * layer_img, layer_img, hipMemcpyDeviceToDevice, s));
         IMPLI_HIP(hipStreamSynchronize(s));   // the next chunk's launches write the buffers these copies read
-        if (ev[0]) {
-            float c = 0.f, d = 0.f, e = 0.f, f = 0.f;
-            IMPLI_HIP(hipEventElapsedTime(&c, im.ev[3], ev[0]));
-            IMPLI_HIP(hipEventElapsedTime(&d, ev[0], ev[1]));
-            IMPLI_HIP(hipEventElapsedTime(&e, ev[1], ev[2]));
-            if (cc) IMPLI_HIP(hipEventElapsedTime(&f, ev[3], ev[4]));
-            g_island_ms[0] += im.raster_ms();
-            g_island_ms[1] += c;
-            g_island_ms[2] += d;
-            g_island_ms[3] += e;
-            g_island_ms[4] += f;
+        if (tm) {
+            tm.add(0, im.raster_ms());
+            tm.add(1, im.ev[3], tm.ev[0]);
+            tm.add(2, tm.ev[0], tm.ev[1]);
+            tm.add(3, tm.ev[1], tm.ev[2]);
+            if (cc) tm.add(4, tm.ev[3], tm.ev[4]);
         }
         total += cc;
     }
@@ -728,7 +680,7 @@ int64_t implisolid_islands(const char* shape_json, int ignore_root_matrix, const
                            int supersample, const float* z, int n_layers, int threshold, int connectivity, int64_t* comp_offsets,
                            int32_t* labels, int64_t stats[8]) {
     last_error().clear();
-    g_islands.n = -1;   // whatever happens, the previous result is gone
+    g_islands.reset();
     if (!shape_json || !rect || !z || !comp_offsets) {
         report("implisolid_islands: bad arguments", false);
         return -1;
@@ -740,27 +692,18 @@ int64_t implisolid_islands(const char* shape_json, int ignore_root_matrix, const
         r.sample();
         QueryShape q(shape_json, ignore_root_matrix);
         q.upload();
-        g_islands.n = island_layers(q, r, threshold, connectivity, comp_offsets, labels, stats);
-        return g_islands.n;
+        return g_islands.publish(island_layers(q, r, threshold, connectivity, comp_offsets, labels, stats));
     });
 }
 
 int implisolid_islands_copy(int32_t* comps) {
-    last_error().clear();
-    if (g_islands.n < 0 || (g_islands.n > 0 && !comps)) {
-        report(g_islands.n < 0 ? "implisolid_islands_copy: no records to copy (the last implisolid_islands failed, or none ran)"
-                               : "implisolid_islands_copy: bad arguments", false);
-        return -1;
-    }
+    if (g_islands.refuses_copy("islands", "records", g_islands.n == 0 || comps)) return -1;
     if (g_islands.n > 0) std::memcpy(comps, g_islands.comps.data(), (size_t)g_islands.n * 8 * sizeof(int32_t));
     return 0;
 }
 
 int implisolid_debug_islands_ms(int enable, double ms[5]) {
-    g_island_timing = enable != 0;
-    if (ms)
-        for (int k = 0; k < 5; ++k) ms[k] = g_island_ms[k];
-    return 0;
+    return g_island_timer.entry(enable, ms);
 }
 
 }  // extern "C"
@@ -771,15 +714,14 @@ int implisolid_debug_islands_ms(int enable, double ms[5]) {
 // of a chunk is copied to a carry buffer for the first layer of the next.  The records add up on the device
 // over the chunks and come down once.  Scratch of its own: 0 the distances, 1 the records, 2 the carried layer.
 namespace {
-bool g_dist_timing = false;      // implisolid_debug_layer_distance_ms: HIP events around the launches
-double g_dist_ms[3] = {-1.0, -1.0, -1.0};
+PassTimer<3> g_dist_timer;       // implisolid_debug_layer_distance_ms: HIP events around the launches
 
 void distance_layers(const QueryShape& q, const LayerRequest& r, int threshold, int64_t reach2, int32_t* dist, int64_t* layer_rec,
                      int64_t stats[8]) {
     Engine& E = *q.E;
     hipStream_t s = q.s;
     const int n_layers = r.n_layers;
-    LayerImages im(q, r, "distance", "IMPLISOLID_DISTANCE_CHUNK", kDistMaxChunk, true, g_dist_timing);
+    LayerImages im(q, r, "distance", "IMPLISOLID_DISTANCE_CHUNK", kDistMaxChunk, true, g_dist_timer.on);
     const DistGrid dg = dist_grid(r.W, r.H, im.g.pitch, threshold);
     const uint32_t chunk_layers = im.chunk_layers;
     const size_t layer_px = im.layer_px;
@@ -791,19 +733,15 @@ void distance_layers(const QueryShape& q, const LayerRequest& r, int threshold, 
     unsigned long long* d_rec = E.scratch(1).as<unsigned long long>();
     int32_t* d_carry = n_layers > (int)chunk_layers ? E.scratch(2).as<int32_t>() : nullptr;
     IMPLI_HIP(hipMemsetAsync(d_rec, 0, (size_t)n_layers * 4 * sizeof(uint64_t), s));
-    EventSet<2> ev;   // behind im.ev[3], the end of the raster passes: columns, rows + unsupported
-    if (g_dist_timing) {
-        ev.create();
-        for (double& m : g_dist_ms) m = 0.0;
-    }
+    Timed<3, 2> tm(g_dist_timer);   // behind im.ev[3], the end of the raster passes: columns, rows + unsupported
     while (im.next()) {
         const int l0 = im.l0;
         const uint32_t nl = im.nl;
         launch_distance_columns(dg, nl, im.d_img, d_dist, s);
-        if (ev[0]) IMPLI_HIP(hipEventRecord(ev[0], s));
+        tm.mark(0, s);
         launch_distance_rows(dg, nl, l0, d_dist, d_rec, s);
         launch_distance_unsupported(dg, nl, l0, reach2, d_dist, d_carry, d_rec, s);
-        if (ev[1]) IMPLI_HIP(hipEventRecord(ev[1], s));
+        tm.mark(1, s);
         IMPLI_HIP(hipGetLastError());
         if (dist)
             IMPLI_HIP(hipMemcpyAsync(dist + (size_t)l0 * layer_px, d_dist, (size_t)nl * layer_px * sizeof(int32_t),
@@ -811,13 +749,10 @@ void distance_layers(const QueryShape& q, const LayerRequest& r, int threshold, 
         if (l0 + (int)nl < n_layers)
             IMPLI_HIP(hipMemcpyAsync(d_carry, d_dist + (size_t)(nl - 1) * layer_px, layer_px * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
         IMPLI_HIP(hipStreamSynchronize(s));   // the next chunk's launches write the buffers these copies read
-        if (ev[0]) {
-            float c = 0.f, d = 0.f;
-            IMPLI_HIP(hipEventElapsedTime(&c, im.ev[3], ev[0]));
-            IMPLI_HIP(hipEventElapsedTime(&d, ev[0], ev[1]));
-            g_dist_ms[0] += im.raster_ms();
-            g_dist_ms[1] += c;
-            g_dist_ms[2] += d;
+        if (tm) {
+            tm.add(0, im.raster_ms());
+            tm.add(1, im.ev[3], tm.ev[0]);
+            tm.add(2, tm.ev[0], tm.ev[1]);
         }
     }
     std::vector<unsigned long long> rec((size_t)n_layers * 4);
@@ -868,10 +803,7 @@ int implisolid_layer_distance(const char* shape_json, int ignore_root_matrix, co
 }
 
 int implisolid_debug_layer_distance_ms(int enable, double ms[3]) {
-    g_dist_timing = enable != 0;
-    if (ms)
-        for (int k = 0; k < 3; ++k) ms[k] = g_dist_ms[k];
-    return 0;
+    return g_dist_timer.entry(enable, ms);
 }
 
 }  // extern "C"
@@ -881,13 +813,11 @@ int implisolid_debug_layer_distance_ms(int enable, double ms[3]) {
 // run offsets (their last entry sizes the records), emit, and the copy of the records into a pinned staging
 // slot.  There are two slots: the host appends a chunk from its slot to the result slot while the device works
 // on the next one.  The image stays on the device; runs never cross layers, so nothing is carried between
-// chunks.  Scratch of its own: 14 the row counts, their scan, its sums and the layer offsets, 0 the starts,
-// 1 the values.
+// chunks.  Scratch of its own: 14 the counted output over the rows, 0 the starts, 1 the values.
 namespace {
-struct RunSlot {                 // the last call's runs; n < 0: none
+struct RunSlot : ResultSlot {    // the last call's runs
     PinnedVec<uint32_t> start;
     PinnedVec<uint8_t> value;
-    int64_t n = -1;
 };
 RunSlot g_runs;
 struct RunStage {                // the staging slots, kept until exit (grow-only)
@@ -896,32 +826,21 @@ struct RunStage {                // the staging slots, kept until exit (grow-onl
     PinnedVec<int64_t> sums;
 };
 RunStage g_run_stage;
-bool g_run_timing = false;       // implisolid_debug_layer_runs_ms: HIP events around the launches
-double g_run_ms[3] = {-1.0, -1.0, -1.0};
+PassTimer<3> g_run_timer;        // implisolid_debug_layer_runs_ms: HIP events around the launches
 
 int64_t run_layers(const QueryShape& q, const LayerRequest& r, int threshold, int64_t* run_offsets, int64_t* layer_sum,
                    int64_t stats[7]) {
     Engine& E = *q.E;
     hipStream_t s = q.s;
     const int H = r.H, n_layers = r.n_layers;
-    LayerImages im(q, r, "runs", "IMPLISOLID_RUNS_CHUNK", kRunMaxChunk, true, g_run_timing);
+    LayerImages im(q, r, "runs", "IMPLISOLID_RUNS_CHUNK", kRunMaxChunk, true, g_run_timer.on);
     const RunGrid rg = run_grid(r.W, H, im.g.pitch, threshold);
-    const uint32_t chunk_layers = im.chunk_layers;
-    const size_t rows_cap = (size_t)chunk_layers * (size_t)H;
-    // every reserve before any pointer is taken (the records' buffers, sized per chunk, hold nothing else)
-    E.scratch(14).reserve((2 * rows_cap + 1 + rows_cap / 4096 + 2 + (size_t)chunk_layers + 1) * sizeof(uint32_t));
-    uint32_t* d_counts = E.scratch(14).as<uint32_t>();
-    uint32_t* d_offsets = d_counts + rows_cap;
-    uint32_t* d_scan_sums = d_offsets + rows_cap + 1;
-    uint32_t* d_loff = d_scan_sums + rows_cap / 4096 + 2;
+    // the records' buffers, sized per chunk, hold nothing else
+    CountedOutput runs(E.scratch(14), (size_t)im.chunk_layers * (size_t)H, (uint32_t)H);   // a row's runs, a layer's offset
     g_runs.start.resize(0);
     g_runs.value.resize(0);
     g_run_stage.sums.resize((size_t)n_layers);
-    EventSet<3> ev;   // behind im.ev[3], the end of the raster passes: count + scan; around emit
-    if (g_run_timing) {
-        ev.create();
-        for (double& m : g_run_ms) m = 0.0;
-    }
+    Timed<3, 3> tm(g_run_timer);   // behind im.ev[3], the end of the raster passes: count + scan; around emit
     int64_t total = 0;
     // the chunk whose records are on their way into a staging slot, not yet in the result slot
     uint32_t pend = 0;
@@ -935,29 +854,20 @@ int64_t run_layers(const QueryShape& q, const LayerRequest& r, int threshold, in
         }
         pend = 0;
     };
-    std::vector<uint32_t> loff((size_t)chunk_layers + 1);
     while (im.next()) {   // its synchronisation: the last chunk's records have landed in the other slot
         const int l0 = im.l0, slot = (int)((im.chunks - 1) & 1);
         const uint32_t nl = im.nl;
-        const uint32_t rows = nl * (uint32_t)H;
-        launch_run_count(rg, nl, im.d_img, d_counts, s);
-        launch_scan_u32(d_counts, d_offsets, rows, d_scan_sums, false, s);
-        launch_slice_layer_offsets(d_offsets, (uint32_t)H, nl, d_loff, s);   // every H-th entry and the total
-        if (ev[0]) IMPLI_HIP(hipEventRecord(ev[0], s));
-        IMPLI_HIP(hipGetLastError());
-        IMPLI_HIP(hipMemcpyAsync(loff.data(), d_loff, ((size_t)nl + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        IMPLI_HIP(hipStreamSynchronize(s));
-        const uint32_t cc = loff[nl];   // the chunk's runs: one a layer at least
+        launch_run_count(rg, nl, im.d_img, runs.d_counts, s);
+        const uint32_t cc = runs.place(nl, s, total, "implisolid_layer_runs: the result reaches 2^31 runs", run_offsets + l0,
+                                       [&] { tm.mark(0, s); });   // the chunk's runs: one a layer at least
         if (cc < nl) throw HipError("runs: a layer without a run");
-        if (total + (int64_t)cc >= ((int64_t)1 << 31)) throw InputError("implisolid_layer_runs: the result reaches 2^31 runs");
-        for (uint32_t k = 0; k < nl; ++k) run_offsets[l0 + (int)k] = total + loff[k];
         E.scratch(0).reserve((size_t)cc * sizeof(uint32_t));
         E.scratch(1).reserve((size_t)cc);
         uint32_t* d_start = E.scratch(0).as<uint32_t>();
         uint8_t* d_value = E.scratch(1).as<uint8_t>();
-        if (ev[1]) IMPLI_HIP(hipEventRecord(ev[1], s));
-        launch_run_emit(rg, nl, im.d_img, d_offsets, cc, d_start, d_value, s);
-        if (ev[2]) IMPLI_HIP(hipEventRecord(ev[2], s));
+        tm.mark(1, s);
+        launch_run_emit(rg, nl, im.d_img, runs.d_offsets, cc, d_start, d_value, s);
+        tm.mark(2, s);
         IMPLI_HIP(hipGetLastError());
         g_run_stage.start[slot].resize(0);   // nothing of the chunk before last is kept
         g_run_stage.value[slot].resize(0);
@@ -969,14 +879,11 @@ int64_t run_layers(const QueryShape& q, const LayerRequest& r, int threshold, in
         drain(slot ^ 1);   // the chunk before this one, while the device works on this one
         pend = cc;
         total += cc;
-        if (ev[0]) {
-            float c = 0.f, d = 0.f;
+        if (tm) {   // only a timed call synchronises here
             IMPLI_HIP(hipStreamSynchronize(s));
-            IMPLI_HIP(hipEventElapsedTime(&c, im.ev[3], ev[0]));
-            IMPLI_HIP(hipEventElapsedTime(&d, ev[1], ev[2]));
-            g_run_ms[0] += im.raster_ms();
-            g_run_ms[1] += c;
-            g_run_ms[2] += d;
+            tm.add(0, im.raster_ms());
+            tm.add(1, im.ev[3], tm.ev[0]);
+            tm.add(2, tm.ev[1], tm.ev[2]);
         }
     }
     IMPLI_HIP(hipStreamSynchronize(s));
@@ -1015,7 +922,7 @@ int64_t implisolid_layer_runs(const char* shape_json, int ignore_root_matrix, co
                               int supersample, const float* z, int n_layers, int threshold, int64_t* run_offsets,
                               int64_t* layer_sum, int64_t stats[7]) {
     last_error().clear();
-    g_runs.n = -1;   // whatever happens, the previous result is gone
+    g_runs.reset();
     if (!shape_json || !rect || !z || !run_offsets || !layer_sum) {
         report("implisolid_layer_runs: bad arguments", false);
         return -1;
@@ -1028,28 +935,19 @@ int64_t implisolid_layer_runs(const char* shape_json, int ignore_root_matrix, co
         r.sample();
         QueryShape q(shape_json, ignore_root_matrix);
         q.upload();
-        g_runs.n = run_layers(q, r, threshold, run_offsets, layer_sum, stats);
-        return g_runs.n;
+        return g_runs.publish(run_layers(q, r, threshold, run_offsets, layer_sum, stats));
     });
 }
 
 int implisolid_layer_runs_copy(uint32_t* start, uint8_t* value) {
-    last_error().clear();
-    if (g_runs.n < 0 || !start || !value) {
-        report(g_runs.n < 0 ? "implisolid_layer_runs_copy: no runs to copy (the last implisolid_layer_runs failed, or none ran)"
-                            : "implisolid_layer_runs_copy: bad arguments", false);
-        return -1;
-    }
+    if (g_runs.refuses_copy("layer_runs", "runs", start && value)) return -1;   // a result has a run a layer: never empty
     std::memcpy(start, g_runs.start.data(), (size_t)g_runs.n * sizeof(uint32_t));
     std::memcpy(value, g_runs.value.data(), (size_t)g_runs.n);
     return 0;
 }
 
 int implisolid_debug_layer_runs_ms(int enable, double ms[3]) {
-    g_run_timing = enable != 0;
-    if (ms)
-        for (int k = 0; k < 3; ++k) ms[k] = g_run_ms[k];
-    return 0;
+    return g_run_timer.entry(enable, ms);
 }
 
 }  // extern "C"
@@ -1074,12 +972,12 @@ std::vector<float> ray_request(const std::string& entry, const float* origins, c
     return ts;
 }
 
-bool g_ray_timing = false;       // implisolid_debug_raycast_ms: HIP events around the two launches
-double g_ray_ms[2] = {-1.0, -1.0};
+PassTimer<2> g_ray_timer;        // implisolid_debug_raycast_ms: HIP events around the two launches
 
-void cast_rays(Engine& E, hipStream_t s, const Program* d_prog, int prog_depth, const float* d_tab, const std::vector<float>& ts,
-               const float* origins, const float* dirs, int64_t n, int bisect, int32_t* hit, float* t, float* f, float* normals,
-               int64_t stats[6]) {
+void cast_rays(const QueryShape& q, const std::vector<float>& ts, const float* origins, const float* dirs, int64_t n, int bisect,
+               int32_t* hit, float* t, float* f, float* normals, int64_t stats[6]) {
+    Engine& E = *q.E;
+    hipStream_t s = q.s;
     const int N = (int)ts.size() - 1;
     const uint32_t cap = (uint32_t)std::min<int64_t>((int64_t)env_limit("IMPLISOLID_RAY_CHUNK", kRayMaxChunk, kRayMaxChunk), n);
     const bool prune = Engine::pruning() >= 1;
@@ -1103,35 +1001,28 @@ void cast_rays(Engine& E, hipStream_t s, const Program* d_prog, int prog_depth, 
     float* d_n = normals ? E.scratch(15).as<float>() : nullptr;
     IMPLI_HIP(hipMemsetAsync(d_state, 0, sizeof(RayState), s));
     IMPLI_HIP(hipMemcpyAsync(d_ts, ts.data(), ts.size() * sizeof(float), hipMemcpyHostToDevice, s));
-    EventSet<3> ev;
-    if (g_ray_timing) {
-        ev.create();
-        g_ray_ms[0] = g_ray_ms[1] = 0.0;
-    }
+    Timed<2, 3> tm(g_ray_timer);
     int64_t chunks = 0;
     for (int64_t first = 0; first < n; first += cap, ++chunks) {
         const uint32_t nc = (uint32_t)std::min<int64_t>(cap, n - first);
         IMPLI_HIP(hipMemcpyAsync(d_org, origins + 3 * first, (size_t)nc * 12, hipMemcpyHostToDevice, s));
         IMPLI_HIP(hipMemcpyAsync(d_dir, dirs + 3 * first, (size_t)nc * 12, hipMemcpyHostToDevice, s));
-        if (ev[0]) IMPLI_HIP(hipEventRecord(ev[0], s));
-        launch_ray_march(d_prog, prog_depth, d_tab, E.tab_range(), d_ts, d_org, d_dir, nc, N, prune, d_hit, d_hmodes, d_fhit,
+        tm.mark(0, s);
+        launch_ray_march(q.d_prog, q.max_depth, q.d_tab, E.tab_range(), d_ts, d_org, d_dir, nc, N, prune, d_hit, d_hmodes, d_fhit,
                          d_work, s);
-        if (ev[1]) IMPLI_HIP(hipEventRecord(ev[1], s));
-        launch_ray_finish(d_prog, prog_depth, d_tab, d_ts, d_org, d_dir, nc, N, bisect, d_hit, d_hmodes, d_fhit, d_work, d_t,
+        tm.mark(1, s);
+        launch_ray_finish(q.d_prog, q.max_depth, q.d_tab, d_ts, d_org, d_dir, nc, N, bisect, d_hit, d_hmodes, d_fhit, d_work, d_t,
                           d_f, d_n, d_state, s);
-        if (ev[2]) IMPLI_HIP(hipEventRecord(ev[2], s));
+        tm.mark(2, s);
         IMPLI_HIP(hipGetLastError());
         IMPLI_HIP(hipMemcpyAsync(hit + first, d_hit, (size_t)nc * 4, hipMemcpyDeviceToHost, s));
         IMPLI_HIP(hipMemcpyAsync(t + first, d_t, (size_t)nc * 4, hipMemcpyDeviceToHost, s));
         IMPLI_HIP(hipMemcpyAsync(f + first, d_f, (size_t)nc * 4, hipMemcpyDeviceToHost, s));
         if (normals) IMPLI_HIP(hipMemcpyAsync(normals + 3 * first, d_n, (size_t)nc * 12, hipMemcpyDeviceToHost, s));
-        if (ev[0]) {
+        if (tm) {   // only a timed call synchronises here
             IMPLI_HIP(hipStreamSynchronize(s));
-            float a = 0.f, b = 0.f;
-            IMPLI_HIP(hipEventElapsedTime(&a, ev[0], ev[1]));
-            IMPLI_HIP(hipEventElapsedTime(&b, ev[1], ev[2]));
-            g_ray_ms[0] += a;
-            g_ray_ms[1] += b;
+            tm.add(0, tm.ev[0], tm.ev[1]);
+            tm.add(1, tm.ev[1], tm.ev[2]);
         }
     }
     RayState h{};
@@ -1165,7 +1056,7 @@ int implisolid_raycast(const char* shape_json, int ignore_root_matrix, const flo
         if (stats) std::fill(stats, stats + 6, (int64_t)0);
         if (n == 0) return 0;                           // ... and nothing creates the engine or a stream
         q.upload();
-        cast_rays(*q.E, q.s, q.d_prog, q.max_depth, q.d_tab, ts, origins, dirs, n, bisect, hit, t, f, normals, stats);
+        cast_rays(q, ts, origins, dirs, n, bisect, hit, t, f, normals, stats);
         return 0;
     });
 }
@@ -1179,12 +1070,7 @@ int implisolid_ray_params(float t0, float t1, int steps, float* ts) {
 }
 
 int implisolid_debug_raycast_ms(int enable, double ms[2]) {
-    g_ray_timing = enable != 0;
-    if (ms) {
-        ms[0] = g_ray_ms[0];
-        ms[1] = g_ray_ms[1];
-    }
-    return 0;
+    return g_ray_timer.entry(enable, ms);
 }
 
 }  // extern "C"
@@ -1195,19 +1081,18 @@ int implisolid_debug_raycast_ms(int enable, double ms[2]) {
 // the per-ray counts, tally, a read-back of the chunk's offsets (their last entry sizes the outputs), emit,
 // refine, and the copies into the host slot at the running offset.  E lends its scratch.
 namespace {
-struct SpanSlot {                // the last call's result; n < 0: none
+struct SpanSlot : ResultSlot {   // the last call's result
     PinnedVec<int32_t> k;
     PinnedVec<float> t, f, normals;
-    int64_t n = -1;
     bool has_normals = false;
 };
 SpanSlot g_spans;
-bool g_span_timing = false;      // implisolid_debug_ray_spans_ms: HIP events around the launches
-double g_span_ms[3] = {-1.0, -1.0, -1.0};
+PassTimer<3> g_span_timer;       // implisolid_debug_ray_spans_ms: HIP events around the launches
 
-int64_t span_rays(Engine& E, hipStream_t s, const Program* d_prog, int prog_depth, const float* d_tab, const std::vector<float>& ts,
-                  const float* origins, const float* dirs, int64_t n, int bisect, bool want_normals, int64_t* span_offsets,
-                  int64_t stats[8]) {
+int64_t span_rays(const QueryShape& q, const std::vector<float>& ts, const float* origins, const float* dirs, int64_t n, int bisect,
+                  bool want_normals, int64_t* span_offsets, int64_t stats[8]) {
+    Engine& E = *q.E;
+    hipStream_t s = q.s;
     const int N = (int)ts.size() - 1;
     const uint64_t nseg = (uint64_t)((N + kRaySegment - 1) / kRaySegment);
     const uint64_t by_env = env_limit("IMPLISOLID_SPAN_CHUNK", kRayMaxChunk, kRayMaxChunk);
@@ -1218,7 +1103,6 @@ int64_t span_rays(Engine& E, hipStream_t s, const Program* d_prog, int prog_dept
     E.scratch(11).reserve((size_t)cap * 6 * sizeof(float));                         // origins, directions
     E.scratch(12).reserve((size_t)cap * nseg * sizeof(uint64_t));                   // the solidity words
     E.scratch(13).reserve((size_t)cap * 2 * sizeof(uint32_t));                      // counts, info
-    E.scratch(14).reserve(((size_t)cap + 1 + cap / 4096 + 2) * sizeof(uint32_t));   // offsets, then the scan's sums
     SpanState* d_state = E.scratch(10).as<SpanState>();
     float* d_ts = behind_state<SpanState>(E.scratch(10));
     float* d_org = E.scratch(11).as<float>();
@@ -1226,37 +1110,26 @@ int64_t span_rays(Engine& E, hipStream_t s, const Program* d_prog, int prog_dept
     uint64_t* d_words = E.scratch(12).as<uint64_t>();
     uint32_t* d_counts = E.scratch(13).as<uint32_t>();
     uint32_t* d_info = d_counts + cap;
-    uint32_t* d_offsets = E.scratch(14).as<uint32_t>();
-    uint32_t* d_sums = d_offsets + cap + 1;
+    CountedOutput spans(E.scratch(14), cap, 0, d_counts);   // a ray's spans, and its own offset
     IMPLI_HIP(hipMemsetAsync(d_state, 0, sizeof(SpanState), s));
     IMPLI_HIP(hipMemcpyAsync(d_ts, ts.data(), ts.size() * sizeof(float), hipMemcpyHostToDevice, s));
     g_spans.k.resize(0);
     g_spans.t.resize(0);
     g_spans.f.resize(0);
     g_spans.normals.resize(0);
-    EventSet<6> ev;
-    if (g_span_timing) {
-        ev.create();
-        g_span_ms[0] = g_span_ms[1] = g_span_ms[2] = 0.0;
-    }
+    Timed<3, 6> tm(g_span_timer);
     int64_t total = 0, chunks = 0;
-    std::vector<uint32_t> off((size_t)cap + 1);
     for (int64_t first = 0; first < n; first += cap, ++chunks) {
         const uint32_t nc = (uint32_t)std::min<int64_t>(cap, n - first);
         IMPLI_HIP(hipMemcpyAsync(d_org, origins + 3 * first, (size_t)nc * 12, hipMemcpyHostToDevice, s));
         IMPLI_HIP(hipMemcpyAsync(d_dir, dirs + 3 * first, (size_t)nc * 12, hipMemcpyHostToDevice, s));
-        if (ev[0]) IMPLI_HIP(hipEventRecord(ev[0], s));
-        launch_span_march(d_prog, prog_depth, d_tab, E.tab_range(), d_ts, d_org, d_dir, nc, N, prune, d_words, d_counts, d_info, s);
-        if (ev[1]) IMPLI_HIP(hipEventRecord(ev[1], s));
-        launch_scan_u32(d_counts, d_offsets, nc, d_sums, false, s);
-        launch_span_tally(nc, d_counts, d_info, d_state, s);
-        if (ev[2]) IMPLI_HIP(hipEventRecord(ev[2], s));
-        IMPLI_HIP(hipGetLastError());
-        IMPLI_HIP(hipMemcpyAsync(off.data(), d_offsets, ((size_t)nc + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        IMPLI_HIP(hipStreamSynchronize(s));
-        const uint32_t sc = off[nc];   // the chunk's spans
-        if (total + (int64_t)sc >= ((int64_t)1 << 31)) throw InputError("implisolid_ray_spans: the result reaches 2^31 spans");
-        for (uint32_t i = 0; i < nc; ++i) span_offsets[first + i] = total + off[i];
+        tm.mark(0, s);
+        launch_span_march(q.d_prog, q.max_depth, q.d_tab, E.tab_range(), d_ts, d_org, d_dir, nc, N, prune, d_words, d_counts, d_info, s);
+        tm.mark(1, s);
+        const uint32_t sc = spans.place(nc, s, total, "implisolid_ray_spans: the result reaches 2^31 spans", span_offsets + first, [&] {
+            launch_span_tally(nc, d_counts, d_info, d_state, s);
+            tm.mark(2, s);
+        });   // the chunk's spans
         if (sc) {
             E.scratch(9).reserve((size_t)sc * 3 * sizeof(uint32_t));    // {k_in, k_out}, then the spans' rays
             E.scratch(15).reserve((size_t)sc * 4 * sizeof(float));      // t, f
@@ -1266,12 +1139,12 @@ int64_t span_rays(Engine& E, hipStream_t s, const Program* d_prog, int prog_dept
             float* d_t = E.scratch(15).as<float>();
             float* d_f = d_t + 2 * (size_t)sc;
             float* d_n = want_normals ? E.scratch(0).as<float>() : nullptr;
-            if (ev[3]) IMPLI_HIP(hipEventRecord(ev[3], s));
-            launch_span_emit(nc, N, d_words, d_info, d_offsets, d_k, d_ray_of, s);
-            if (ev[4]) IMPLI_HIP(hipEventRecord(ev[4], s));
-            launch_span_refine(d_prog, prog_depth, d_tab, E.tab_range(), d_ts, d_org, d_dir, N, bisect, prune, sc, d_k, d_ray_of,
+            tm.mark(3, s);
+            launch_span_emit(nc, N, d_words, d_info, spans.d_offsets, d_k, d_ray_of, s);
+            tm.mark(4, s);
+            launch_span_refine(q.d_prog, q.max_depth, q.d_tab, E.tab_range(), d_ts, d_org, d_dir, N, bisect, prune, sc, d_k, d_ray_of,
                                d_t, d_f, d_n, s);
-            if (ev[5]) IMPLI_HIP(hipEventRecord(ev[5], s));
+            tm.mark(5, s);
             IMPLI_HIP(hipGetLastError());
             const size_t at = (size_t)total, upto = (size_t)(total + sc);
             g_spans.k.resize(upto * 2);
@@ -1284,17 +1157,13 @@ int64_t span_rays(Engine& E, hipStream_t s, const Program* d_prog, int prog_dept
             if (want_normals) IMPLI_HIP(hipMemcpyAsync(g_spans.normals.data() + 6 * at, d_n, (size_t)sc * 24, hipMemcpyDeviceToHost, s));
             IMPLI_HIP(hipStreamSynchronize(s));   // the next chunk's launches write the buffers these copies read
         }
-        if (ev[0]) {
-            float a = 0.f, b = 0.f, c = 0.f, d = 0.f;
-            IMPLI_HIP(hipEventElapsedTime(&a, ev[0], ev[1]));
-            IMPLI_HIP(hipEventElapsedTime(&b, ev[1], ev[2]));
+        if (tm) {
+            tm.add(0, tm.ev[0], tm.ev[1]);
+            tm.add(1, tm.ev[1], tm.ev[2]);   // scan and tally
             if (sc) {
-                IMPLI_HIP(hipEventElapsedTime(&c, ev[3], ev[4]));
-                IMPLI_HIP(hipEventElapsedTime(&d, ev[4], ev[5]));
+                tm.add(1, tm.ev[3], tm.ev[4]);   // ... then emit
+                tm.add(2, tm.ev[4], tm.ev[5]);
             }
-            g_span_ms[0] += a;
-            g_span_ms[1] += b + c;   // scan and tally, then emit
-            g_span_ms[2] += d;
         }
         total += sc;
     }
@@ -1323,7 +1192,7 @@ int64_t implisolid_ray_spans(const char* shape_json, int ignore_root_matrix, con
                              float t0, float t1, int steps, int bisect, int want_normals, int64_t* span_offsets,
                              int64_t stats[8]) {
     last_error().clear();
-    g_spans.n = -1;   // whatever happens, the previous result is gone
+    g_spans.reset();
     if (!shape_json || !span_offsets || (n > 0 && (!origins || !dirs))) {
         report("implisolid_ray_spans: bad arguments", false);
         return -1;
@@ -1336,30 +1205,19 @@ int64_t implisolid_ray_spans(const char* shape_json, int ignore_root_matrix, con
         g_spans.has_normals = want_normals != 0;
         if (n == 0) {                                   // ... and nothing creates the engine or a stream
             span_offsets[0] = 0;
-            g_spans.n = 0;
-            return 0;
+            return g_spans.publish(0);
         }
         q.upload();
-        g_spans.n = span_rays(*q.E, q.s, q.d_prog, q.max_depth, q.d_tab, ts, origins, dirs, n, bisect, want_normals != 0,
-                              span_offsets, stats);
-        return g_spans.n;
+        return g_spans.publish(span_rays(q, ts, origins, dirs, n, bisect, want_normals != 0, span_offsets, stats));
     });
 }
 
 int implisolid_ray_spans_copy(int32_t* k, float* t, float* f, float* normals) {
-    last_error().clear();
-    if (g_spans.n < 0) {
-        report("implisolid_ray_spans_copy: no spans to copy (the last implisolid_ray_spans failed, or none ran)", false);
-        return -1;
-    }
-    if (normals && !g_spans.has_normals) {
+    if (g_spans.n >= 0 && normals && !g_spans.has_normals) {   // ahead of the pointers; behind "no spans to copy"
         report("implisolid_ray_spans_copy: the call computed no normals (want_normals was 0)", false);
         return -1;
     }
-    if (g_spans.n > 0 && (!k || !t || !f)) {
-        report("implisolid_ray_spans_copy: bad arguments", false);
-        return -1;
-    }
+    if (g_spans.refuses_copy("ray_spans", "spans", g_spans.n == 0 || (k && t && f))) return -1;
     if (g_spans.n > 0) {
         const size_t S = (size_t)g_spans.n;
         std::memcpy(k, g_spans.k.data(), S * 2 * sizeof(int32_t));
@@ -1371,13 +1229,7 @@ int implisolid_ray_spans_copy(int32_t* k, float* t, float* f, float* normals) {
 }
 
 int implisolid_debug_ray_spans_ms(int enable, double ms[3]) {
-    g_span_timing = enable != 0;
-    if (ms) {
-        ms[0] = g_span_ms[0];
-        ms[1] = g_span_ms[1];
-        ms[2] = g_span_ms[2];
-    }
-    return 0;
+    return g_span_timer.entry(enable, ms);
 }
 
 }  // extern "C"
@@ -1388,8 +1240,9 @@ int implisolid_debug_ray_spans_ms(int enable, double ms[3]) {
 // the state block with the layer counts behind it, after the last launch; a raised overflow flag voids
 // the run, the lists grow and everything runs again (the first launch zeroes the sums).
 namespace {
-bool compute_mass(Engine& E, hipStream_t s, const Program* d_prog, int prog_depth, const float* d_tab, const float box[6],
-                  int depth, uint64_t moments[10], int64_t* layer_cells, int64_t stats[4]) {
+bool compute_mass(const QueryShape& q, const float box[6], int depth, uint64_t moments[10], int64_t* layer_cells, int64_t stats[4]) {
+    Engine& E = *q.E;
+    hipStream_t s = q.s;
     const int N = 1 << depth, last = depth - 2, first = std::min(3, last);
     std::vector<float> tables((size_t)3 * (N + 1) + (size_t)3 * N);
     bounds_edges(box, depth, tables.data());                    // validates depth and box (InputError)
@@ -1421,7 +1274,7 @@ bool compute_mass(Engine& E, hipStream_t s, const Program* d_prog, int prog_dept
             IMPLI_HIP(hipMemcpyAsync(d_edges, tables.data(), tables.size() * sizeof(float), hipMemcpyHostToDevice, s));
             uploaded = true;
         }
-        launch_mass(d_prog, prog_depth, d_tab, E.tab_range(), d_edges, d_mids, depth, prune, d_box, d_modes, cap, d_state,
+        launch_mass(q.d_prog, q.max_depth, q.d_tab, E.tab_range(), d_edges, d_mids, depth, prune, d_box, d_modes, cap, d_state,
                     d_layers, s);
         IMPLI_HIP(hipGetLastError());
         IMPLI_HIP(hipMemcpyAsync(h.data(), d_state, head, hipMemcpyDeviceToHost, s));
@@ -1462,7 +1315,7 @@ int implisolid_mass(const char* shape_json, int ignore_root_matrix, const float 
         }
         QueryShape q(shape_json, ignore_root_matrix);
         q.upload();
-        return compute_mass(*q.E, q.s, q.d_prog, q.max_depth, q.d_tab, box, depth, moments, layer_cells, stats) ? 1 : 0;
+        return compute_mass(q, box, depth, moments, layer_cells, stats) ? 1 : 0;
     });
 }
 

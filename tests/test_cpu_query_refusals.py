@@ -6,6 +6,10 @@ the queries moved to csrc/abi_queries.hip, and those of the layer and ray entrie
 share their request checks (LayerRequest, ray_request): they pin that neither changed an error path, nor
 which of two faults at once is reported.  No GPU."""
 import ctypes
+import json
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -663,4 +667,57 @@ def test_no_slice_to_copy_after_a_refused_slice(impli, name):
     assert observe(L, name)[0] == -1
     assert (ENTRY["slice_copy"](L), impli.last_error()) == SLICE_COPY
     assert (ENTRY["slice_copy"](L, xy=None, keys=None), impli.last_error()) == SLICE_COPY
+    next_call_works(impli)
+
+
+# ---- the result slots and the pass timers ---------------------------------------------------------------------------
+# What the four copy entries and the six timer entries answer, recorded from the library before the queries came
+# to share their result slot and their pass timer: in a process that has run no query, and after a refused one.
+ENTRY["runs"] = Args("implisolid_layer_runs", shape=SPHERE, irm=0, rect=RECT, width=8, height=8, supersample=2, z=Z2, n_layers=2,
+                     threshold=0, offsets=i64(3), sums=i64(2), stats=i64(7))
+COPY = {
+    "slice": Args("implisolid_slice_copy", xy=F(*[0] * 4), keys=np.zeros(2, np.uint32)),
+    "islands": Args("implisolid_islands_copy", comps=np.zeros(8, np.int32)),
+    "runs": Args("implisolid_layer_runs_copy", start=np.zeros(1, np.uint32), value=np.zeros(1, np.uint8)),
+    "ray_spans": Args("implisolid_ray_spans_copy", k=np.zeros(2, np.int32), t=F(0, 0), f=F(0, 0), normals=F(*[0] * 6)),
+}
+NOTHING_TO_COPY = {
+    "slice": SLICE_COPY,
+    "islands": (-1, "implisolid_islands_copy: no records to copy (the last implisolid_islands failed, or none ran)"),
+    "runs": (-1, "implisolid_layer_runs_copy: no runs to copy (the last implisolid_layer_runs failed, or none ran)"),
+    "ray_spans": (-1, "implisolid_ray_spans_copy: no spans to copy (the last implisolid_ray_spans failed, or none ran)"),
+}
+REFUSED = {"slice": dict(n_layers=0), "islands": dict(connectivity=6), "runs": dict(threshold=5), "ray_spans": dict(steps=0)}
+
+
+def _copies(L, last_error):
+    """each copy entry's answer with its valid pointers, then with null ones"""
+    out = {}
+    for name, copy in COPY.items():
+        with_pointers = (copy(L), last_error())
+        out[name] = [with_pointers, (copy(L, **{k: None for k in copy.valid}), last_error())]
+    return out
+
+
+def test_before_any_query_the_timers_read_minus_one_and_nothing_is_there_to_copy():
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import json, sys; sys.path.insert(0, 'tests'); import implisolid_amd as I, test_cpu_query_refusals as t; L = I.lib(); "
+            "ms = [I.debug_bounds_ms(False), I.islands_kernel_ms(False), I.layer_distance_kernel_ms(False), "
+            "I.layer_runs_kernel_ms(False), I.raycast_kernel_ms(False), I.ray_spans_kernel_ms(False)]; "
+            "print('RESULT', json.dumps([ms, t._copies(L, I.last_error)]))")
+    out = subprocess.run([sys.executable, "-c", code], cwd=root, capture_output=True, text=True, timeout=120)
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("RESULT ")]
+    assert len(lines) == 1, (out.stdout, out.stderr)
+    ms, copies = json.loads(lines[0][len("RESULT "):])
+    # bounds (one figure, returned), islands, layer distance, layer runs, raycast, ray spans
+    assert ms == [-1.0] + [[-1.0] * n for n in (5, 3, 3, 2, 3)]
+    for name, want in NOTHING_TO_COPY.items():
+        assert [tuple(c) for c in copies[name]] == [want, want], name
+
+
+@pytest.mark.parametrize("name", list(REFUSED))
+def test_nothing_to_copy_after_a_refused_query(impli, name):
+    L = impli.lib()
+    assert ENTRY[name](L, **REFUSED[name]) == -1 and impli.last_error()
+    assert _copies(L, impli.last_error)[name] == [NOTHING_TO_COPY[name]] * 2
     next_call_works(impli)
