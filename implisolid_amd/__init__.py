@@ -59,6 +59,7 @@ ABI_SYMBOLS = [
     "implisolid_islands", "implisolid_islands_copy", "implisolid_debug_islands_ms",
     "implisolid_layer_distance", "implisolid_debug_layer_distance_ms",
     "implisolid_layer_runs", "implisolid_layer_runs_copy", "implisolid_debug_layer_runs_ms",
+    "implisolid_layer_bodies", "implisolid_layer_bodies_copy", "implisolid_debug_layer_bodies_ms",
     "implisolid_raycast", "implisolid_ray_params", "implisolid_debug_raycast_ms",
     "implisolid_ray_spans", "implisolid_ray_spans_copy", "implisolid_debug_ray_spans_ms",
 ]
@@ -227,6 +228,10 @@ def lib():
                                    ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)], ctypes.c_int64),
         "implisolid_layer_runs_copy": ([up, ctypes.POINTER(ctypes.c_uint8)], c_int),
         "implisolid_debug_layer_runs_ms": ([c_int, ctypes.POINTER(ctypes.c_double)], c_int),
+        "implisolid_layer_bodies": ([c_char_p, c_int, fp, c_int, c_int, c_int, fp, c_int, c_int, c_int, c_int, c_int,
+                                     ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)], ctypes.c_int64),
+        "implisolid_layer_bodies_copy": ([ctypes.POINTER(ctypes.c_int64), ip], c_int),
+        "implisolid_debug_layer_bodies_ms": ([c_int, ctypes.POINTER(ctypes.c_double)], c_int),
         "implisolid_raycast": ([c_char_p, c_int, fp, fp, ctypes.c_int64, ctypes.c_float, ctypes.c_float, c_int, c_int, ip, fp,
                                 fp, fp, ctypes.POINTER(ctypes.c_int64)], c_int),
         "implisolid_ray_params": ([ctypes.c_float, ctypes.c_float, c_int, fp], c_int),
@@ -750,7 +755,7 @@ def _rect4(rect, what):
 
 
 def _layer_args(what, rect, z, width, height, supersample):
-    """What raster_layers, layer_islands, layer_distance and layer_runs do with their arguments first: (rect, z, W, H, s)."""
+    """What raster_layers, layer_islands, layer_distance, layer_runs and layer_bodies do with their arguments first: (rect, z, W, H, s)."""
     r = _rect4(rect, what)
     zz = np.ascontiguousarray(z, np.float32).reshape(-1)
     W, H, s = int(width), int(height), int(supersample)
@@ -1040,6 +1045,95 @@ def layer_runs_kernel_ms(enable=True):
     """Diagnostics: switch the event timing of layer_runs()'s kernels on or off; returns the last timed call's
     (raster passes, count pass + scan, emit pass) ms, -1 before any."""
     return _pass_ms("layer_runs", 3, enable)
+
+
+BODY_DTYPE = np.dtype([(name, np.int64) for name in ("seed", "volume", "x0", "y0", "l0", "x1", "y1", "l1")])
+BODY_RUN_DTYPE = np.dtype([(name, np.int32) for name in ("start", "length", "body")])
+
+
+def layer_bodies(shape, rect, width, height, z, supersample=1, threshold=1, target=1, connectivity=None, ignore_root_matrix=False,
+                 want_runs=False, return_stats=False):
+    """The bodies of the layer stack z = z[l] on the GPU: the connected components of its voxels through all layers
+    (include/implisolid.h implisolid_layer_bodies).  The images are raster_layers'; target 1 takes the solid voxels
+    (coverage >= threshold), target 0 the empty ones; connectivity is 6 or 26, and None means the dual pair: 26 for
+    target 1, 6 for target 0.  Returns (run_offsets int64 (L + 1,): layer l's row runs are [run_offsets[l],
+    run_offsets[l + 1]); bodies, a structured array (BODY_DTYPE) in increasing seed of {seed = the smallest l * W * H
+    + py * W + px, volume, x0, y0, l0, x1, y1, l1 = the inclusive bounding box}), then with want_runs runs, a
+    structured array (BODY_RUN_DTYPE) of {start = py * W + x0, length, body = the index of its body's record} per
+    row run, and with return_stats [raster_layers' five figures, row runs, bodies, target voxels]."""
+    fp, lp = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64)
+    r, zz, W, H, s = _layer_args("layer_bodies", rect, z, width, height, supersample)
+    if connectivity is None:
+        connectivity = 26 if int(target) == 1 else 6
+    offs = np.zeros(zz.size + 1, np.int64)
+    stats = (ctypes.c_int64 * 8)()
+    B = lib().implisolid_layer_bodies(_s(shape), int(bool(ignore_root_matrix)), r.ctypes.data_as(fp), W, H, s, zz.ctypes.data_as(fp),
+                                      int(zz.size), int(threshold), int(target), int(connectivity), int(bool(want_runs)),
+                                      offs.ctypes.data_as(lp), stats)
+    if B < 0:
+        raise ImplisolidError(last_error())
+    bodies = np.empty(B, BODY_DTYPE)
+    runs = np.empty(int(offs[-1]), BODY_RUN_DTYPE) if want_runs else None
+    if lib().implisolid_layer_bodies_copy(bodies.ctypes.data_as(lp),
+                                          runs.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if want_runs else None) != 0:
+        raise ImplisolidError(last_error())
+    out = (offs, bodies)
+    if want_runs:
+        out += (runs,)
+    if return_stats:
+        out += ([int(v) for v in stats],)
+    return out
+
+
+def _body_rows(a, dtype, what):
+    """records as a structured array of `dtype`: one already, or integers (n, fields)"""
+    a = np.asarray(a)
+    if a.dtype.names:
+        if a.dtype.names != dtype.names:
+            raise ValueError("%s: the records' fields must be %s" % (what, ", ".join(dtype.names)))
+        return a.reshape(-1)
+    return np.ascontiguousarray(a.reshape(-1, len(dtype.names)), dtype[0]).view(dtype).reshape(-1)
+
+
+def bodies_decode(run_offsets, runs, width, height):
+    """Host only: the label stack of layer_bodies()'s row runs, int32 (L, height, width): the voxel's body index,
+    or -1 where the voxel is not of the target class."""
+    W, H = int(width), int(height)
+    offs = np.asarray(run_offsets, np.int64).reshape(-1)
+    rr = _body_rows(runs, BODY_RUN_DTYPE, "bodies_decode")
+    if offs.size < 2 or offs[0] != 0 or offs[-1] != rr.size or (np.diff(offs) < 0).any():
+        raise ValueError("bodies_decode: run_offsets must run from 0 to len(runs) without decreasing")
+    start, length = rr["start"].astype(np.int64), rr["length"].astype(np.int64)
+    if (length < 1).any() or (start < 0).any() or (start % W + length > W).any() or (start // W >= H).any():
+        raise ValueError("bodies_decode: every run must lie inside one image row")
+    L = offs.size - 1
+    first = start + np.repeat(np.arange(L, dtype=np.int64), np.diff(offs)) * (W * H)
+    out = np.full(L * H * W, -1, np.int32)
+    # every voxel of every run: its run's first key plus its position in the run
+    at = np.repeat(first - np.concatenate(([0], np.cumsum(length)[:-1])), length) + np.arange(int(length.sum()), dtype=np.int64)
+    out[at] = np.repeat(rr["body"], length)
+    return out.reshape(L, H, W)
+
+
+def enclosed_voids(bodies, width, height, n_layers):
+    """Host only: the records of layer_bodies() that touch no face of the stack (x0 > 0, y0 > 0, l0 > 0, x1 < width -
+    1, y1 < height - 1, l1 < n_layers - 1).  Meant for target=0: the empty regions sealed on all sides."""
+    b = _body_rows(bodies, BODY_DTYPE, "enclosed_voids")
+    return b[(b["x0"] > 0) & (b["y0"] > 0) & (b["l0"] > 0) & (b["x1"] < int(width) - 1) & (b["y1"] < int(height) - 1)
+             & (b["l1"] < int(n_layers) - 1)]
+
+
+def floating_bodies(bodies):
+    """Host only: the records of layer_bodies() that start above the first layer (l0 > 0).  Meant for target=1: the
+    bodies that do not stand on the build plate."""
+    b = _body_rows(bodies, BODY_DTYPE, "floating_bodies")
+    return b[b["l0"] > 0]
+
+
+def layer_bodies_kernel_ms(enable=True):
+    """Diagnostics: switch the event timing of layer_bodies()'s kernels on or off; returns the last timed call's
+    (raster passes, row-run count + scan + emit, link, finish) ms, -1 before any."""
+    return _pass_ms("layer_bodies", 4, enable)
 
 
 def ray_params(t0, t1, steps):

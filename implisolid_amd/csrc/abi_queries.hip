@@ -1,9 +1,9 @@
 // abi_queries.hip -- the field queries of the C ABI: the interval probes, bounds, slices, layer images and
-// their islands, distance fields and run-length streams, rays and mass properties.  Each entry validates its request, compiles
+// their islands, distance fields, run-length streams and bodies, rays and mass properties.  Each entry validates its request, compiles
 // the shape (QueryShape), puts it on the device and runs its passes; the scaffolding is abi_common.hpp's.
-// The four layer queries share their request (LayerRequest) and the passes that make a chunk's image
+// The five layer queries share their request (LayerRequest) and the passes that make a chunk's image
 // (LayerImages): each reads as what it does with the image.  The two ray queries share ray_request.  Slice,
-// islands, runs and ray spans place their records with abi_common.hpp's CountedOutput and keep them in a
+// islands, runs, bodies and ray spans place their records with abi_common.hpp's CountedOutput and keep them in a
 // ResultSlot; the timed queries keep their figures in a PassTimer.
 #include <cmath>
 #include <cstring>
@@ -361,7 +361,7 @@ int64_t implisolid_slice_loops(const uint32_t* keys, int64_t n_segments, int64_t
 
 }  // extern "C"
 
-// ---- what the layer queries share: the request and the image (raster, islands, layer distance, runs) ------
+// ---- what the layer queries share: the request and the image (raster, islands, layer distance, runs, bodies) ------
 namespace {
 // The request of implisolid_<entry>, refused in this order: n_layers, z, width / height, supersample, threshold
 // (an entry without one passes 1, which every supersample admits).  The entry's own checks follow, then
@@ -948,6 +948,164 @@ int implisolid_layer_runs_copy(uint32_t* start, uint8_t* value) {
 
 int implisolid_debug_layer_runs_ms(int enable, double ms[3]) {
     return g_run_timer.entry(enable, ms);
+}
+
+}  // extern "C"
+
+// ---- bodies of the layer stack (implisolid_layer_bodies) ------------------------------------------------------
+// Per chunk, behind LayerImages' head, bodies.hip's passes: count, the scan, a read-back of the chunk's per-layer
+// run offsets (their last entry sizes the stack's arrays), emit, link.  The image stays on the device and nothing
+// of it is carried: the runs, their union-find and the rows' offsets live in stack-wide arrays that grow with
+// the chunks, and a chunk's first layer links to the runs of the layer below there.  Behind the last chunk the
+// finish passes: the roots per row, their scan, the records, the tally; then the records, and the runs when asked
+// for, come down into the result slot.  Scratch of its own: 14 the counted output over a chunk's rows, 0 the
+// runs, 1 the union-find, 2 the rows' offsets, 3 the counted output over the stack's rows, 4 the roots' ordinals,
+// 5 the records, 6 the run records.
+namespace {
+struct BodySlot : ResultSlot {   // the last call's records, and its runs when it asked for them
+    PinnedVec<int64_t> bodies;
+    PinnedVec<int32_t> runs;
+    int64_t n_runs = -1;         // < 0: the call did not ask for runs
+};
+BodySlot g_bodies;
+PassTimer<4> g_body_timer;       // implisolid_debug_layer_bodies_ms: HIP events around the launches
+
+// A stack-wide array grown to `want` bytes with its first `keep` bytes kept: DevBuf::reserve hands out another
+// block and drops the old one's contents, so the new block is filled from the old one before that is released.
+void grow_keeping(DevBuf& b, size_t keep, size_t want, hipStream_t s) {
+    if (b.p && want <= b.bytes) return;
+    DevBuf grown;
+    grown.reserve(std::max(want, b.bytes + b.bytes / 2));
+    try {
+        if (keep) IMPLI_HIP(hipMemcpyAsync(grown.p, b.p, keep, hipMemcpyDeviceToDevice, s));
+        IMPLI_HIP(hipStreamSynchronize(s));   // nothing in flight reads or writes the old block
+    } catch (...) {
+        grown.release();
+        throw;
+    }
+    std::swap(b, grown);
+    grown.release();
+}
+
+int64_t body_layers(const QueryShape& q, const LayerRequest& r, int threshold, int target, int connectivity, bool want_runs,
+                    int64_t* run_offsets, int64_t stats[8]) {
+    Engine& E = *q.E;
+    hipStream_t s = q.s;
+    const int H = r.H, n_layers = r.n_layers;
+    LayerImages im(q, r, "bodies", "IMPLISOLID_BODIES_CHUNK", kBodyMaxChunk, true, g_body_timer.on);
+    const BodyGrid bg = body_grid(r.W, H, im.g.pitch, threshold, target, connectivity);
+    const size_t rows = (size_t)n_layers * (size_t)H;   // <= 2^30
+    // every reserve before any pointer is taken; the runs' arrays grow in the loop and are addressed through their DevBuf
+    CountedOutput placed(E.scratch(14), (size_t)im.chunk_layers * (size_t)H, (uint32_t)H);   // a row's runs, a layer's offset
+    CountedOutput roots(E.scratch(3), rows, (uint32_t)rows);                                 // a row's roots; one group, the stack
+    E.scratch(2).reserve((rows + 1) * sizeof(uint32_t));
+    DevBuf& b_runs = E.scratch(0);
+    DevBuf& b_parent = E.scratch(1);
+    uint32_t* d_rowoff = E.scratch(2).as<uint32_t>();
+    static_assert(sizeof(RasterState) + sizeof(BodyState) <= kStateBytes, "both states share the state block");
+    BodyState* d_bstate = reinterpret_cast<BodyState*>(im.d_state + 1);
+    IMPLI_HIP(hipMemsetAsync(d_bstate, 0, sizeof(BodyState), s));
+    g_bodies.bodies.resize(0);
+    g_bodies.runs.resize(0);
+    Timed<4, 4> tm(g_body_timer);   // behind im.ev[3], the end of the raster passes: count + scan + emit, link; around the finish
+    int64_t total = 0;
+    while (im.next()) {
+        const int l0 = im.l0;
+        const uint32_t nl = im.nl;
+        launch_body_count(bg, nl, im.d_img, placed.d_counts, d_bstate, s);
+        const uint32_t cc = placed.place(nl, s, total, "implisolid_layer_bodies: the stack reaches 2^31 row runs", run_offsets + l0);
+        grow_keeping(b_runs, (size_t)total * 2 * sizeof(int32_t), (size_t)(total + cc + 1) * 2 * sizeof(int32_t), s);
+        grow_keeping(b_parent, (size_t)total * sizeof(int32_t), (size_t)(total + cc + 1) * sizeof(int32_t), s);
+        launch_body_emit(bg, nl, l0, im.d_img, placed.d_offsets, (uint32_t)total, cc, b_runs.as<int32_t>(), b_parent.as<int32_t>(),
+                         d_rowoff, s);
+        tm.mark(0, s);
+        launch_body_link(bg, nl, l0, b_runs.as<int32_t>(), d_rowoff, b_parent.as<int32_t>(), s);
+        tm.mark(1, s);
+        IMPLI_HIP(hipGetLastError());
+        total += cc;
+        if (tm) {   // only a timed call synchronises here
+            IMPLI_HIP(hipStreamSynchronize(s));
+            tm.add(0, im.raster_ms());
+            tm.add(1, im.ev[3], tm.ev[0]);
+            tm.add(2, tm.ev[0], tm.ev[1]);
+        }
+    }
+    run_offsets[n_layers] = total;
+    // the finish: the roots in run order are the bodies in seed order
+    tm.mark(2, s);
+    launch_body_root_rows(bg, (uint32_t)rows, d_rowoff, b_parent.as<int32_t>(), roots.d_counts, s);
+    int64_t first = 0;
+    const uint32_t B = roots.place(1, s, 0, "implisolid_layer_bodies: the stack reaches 2^31 bodies", &first);
+    if ((int64_t)B > total) throw HipError("bodies: more roots than runs");
+    E.scratch(4).reserve((size_t)(total + 1) * sizeof(uint32_t));
+    E.scratch(5).reserve((size_t)(B + 1u) * 8 * sizeof(int64_t));
+    if (want_runs) E.scratch(6).reserve((size_t)(total + 1) * 3 * sizeof(int32_t));
+    long long* d_rec = E.scratch(5).as<long long>();
+    int32_t* d_out = want_runs ? E.scratch(6).as<int32_t>() : nullptr;
+    launch_body_roots(bg, (uint32_t)rows, b_runs.as<int32_t>(), d_rowoff, b_parent.as<int32_t>(), roots.d_offsets, B,
+                      E.scratch(4).as<uint32_t>(), d_rec, s);
+    launch_body_tally(bg, (uint32_t)rows, b_runs.as<int32_t>(), d_rowoff, b_parent.as<int32_t>(), E.scratch(4).as<uint32_t>(), B, d_rec,
+                      d_out, s);
+    tm.mark(3, s);
+    IMPLI_HIP(hipGetLastError());
+    g_bodies.bodies.resize((size_t)B * 8);
+    if (B) IMPLI_HIP(hipMemcpyAsync(g_bodies.bodies.data(), d_rec, (size_t)B * 8 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    if (want_runs) {
+        g_bodies.runs.resize((size_t)total * 3);
+        if (total) IMPLI_HIP(hipMemcpyAsync(g_bodies.runs.data(), d_out, (size_t)total * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    }
+    BodyState hb{};
+    IMPLI_HIP(hipMemcpyAsync(&hb, d_bstate, sizeof hb, hipMemcpyDeviceToHost, s));
+    IMPLI_HIP(hipStreamSynchronize(s));
+    if (tm) tm.add(3, tm.ev[2], tm.ev[3]);
+    int64_t volume = 0;
+    for (uint32_t b = 0; b < B; ++b) volume += g_bodies.bodies.data()[8 * (size_t)b + 1];
+    if (volume != (int64_t)hb.voxels) throw HipError("bodies: the records' volumes and the target voxels disagree");
+    g_bodies.n_runs = want_runs ? total : -1;
+    if (stats) {
+        im.stats(stats);
+        stats[5] = total;
+        stats[6] = (int64_t)B;
+        stats[7] = (int64_t)hb.voxels;
+    }
+    return (int64_t)B;
+}
+}  // namespace
+
+extern "C" {
+
+int64_t implisolid_layer_bodies(const char* shape_json, int ignore_root_matrix, const float rect[4], int width, int height,
+                                int supersample, const float* z, int n_layers, int threshold, int target, int connectivity,
+                                int want_runs, int64_t* run_offsets, int64_t stats[8]) {
+    last_error().clear();
+    g_bodies.reset();
+    g_bodies.n_runs = -1;
+    if (!shape_json || !rect || !z || !run_offsets) {
+        report("implisolid_layer_bodies: bad arguments", false);
+        return -1;
+    }
+    return guard_device([&]() -> int64_t {
+        // the request first: bad input is refused before anything is compiled or reaches the device
+        LayerRequest r("layer_bodies", rect, width, height, supersample, z, n_layers, threshold);
+        if (target != 0 && target != 1) throw InputError("implisolid_layer_bodies: target must be 0 (empty) or 1 (solid)");
+        if (connectivity != 6 && connectivity != 26) throw InputError("implisolid_layer_bodies: connectivity must be 6 or 26");
+        if (want_runs != 0 && want_runs != 1) throw InputError("implisolid_layer_bodies: want_runs must be 0 or 1");
+        r.sample();
+        QueryShape q(shape_json, ignore_root_matrix);
+        q.upload();
+        return g_bodies.publish(body_layers(q, r, threshold, target, connectivity, want_runs != 0, run_offsets, stats));
+    });
+}
+
+int implisolid_layer_bodies_copy(int64_t* bodies, int32_t* runs) {
+    if (g_bodies.refuses_copy("layer_bodies", "bodies", (g_bodies.n == 0 || bodies) && (g_bodies.n_runs <= 0 || runs))) return -1;
+    if (g_bodies.n > 0) std::memcpy(bodies, g_bodies.bodies.data(), (size_t)g_bodies.n * 8 * sizeof(int64_t));
+    if (g_bodies.n_runs > 0) std::memcpy(runs, g_bodies.runs.data(), (size_t)g_bodies.n_runs * 3 * sizeof(int32_t));
+    return 0;
+}
+
+int implisolid_debug_layer_bodies_ms(int enable, double ms[4]) {
+    return g_body_timer.entry(enable, ms);
 }
 
 }  // extern "C"

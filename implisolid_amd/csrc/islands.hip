@@ -34,6 +34,7 @@
 #include <stdexcept>
 
 #include "kernels.hpp"
+#include "unionfind_device.hpp"   // find_lds, find_glb, unite<>
 
 namespace impli {
 
@@ -43,40 +44,6 @@ typedef unsigned long long u64;
 constexpr int kTW = kIslandTileW, kTH = kIslandTileH;
 static_assert(kTW == 64, "one ballot is one tile row");
 static_assert(kTH % 4 == 0, "the four waves of a block share the rows evenly");
-
-// ---- union-find, the smaller index is the parent --------------------------------------------------------
-// LDS flavour: volatile reads (another lane's atomicMin must be seen)
-__device__ __forceinline__ int find_lds(const volatile int* L, int x) {
-    int p;
-    while ((p = L[x]) != x) x = p;   // p < x: strictly decreasing
-    return x;
-}
-// global flavour: relaxed device-scope loads, not served from a stale cache line
-__device__ __forceinline__ int find_glb(int* L, int x) {
-    int p;
-    while ((p = __hip_atomic_load(&L[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != x) x = p;
-    return x;
-}
-// Joins the classes of a and b.  With a > b both roots, atomicMin(&L[a], b) returns a when a was still a
-// root: done.  Otherwise another lane has pointed a at old < a in the meantime and L[a] is now min(old, b),
-// a member of the class either way; what remains is to join old and b, both < a: the larger index of the
-// pair has strictly decreased, which bounds the rounds.
-template <bool LDS>
-__device__ __forceinline__ void unite(int* L, int a, int b) {
-    for (;;) {
-        a = LDS ? find_lds(L, a) : find_glb(L, a);
-        b = LDS ? find_lds(L, b) : find_glb(L, b);
-        if (a == b) return;
-        if (a < b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        const int old = atomicMin(&L[a], b);
-        if (old == a) return;
-        a = old;
-    }
-}
 
 // the first lane of the run of `w` that holds `lane` (bit `lane` of w is set)
 __device__ __forceinline__ int run_start(uint64_t w, int lane) {

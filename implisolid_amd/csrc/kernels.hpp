@@ -270,6 +270,47 @@ void launch_run_count(RunGrid g, uint32_t n_layers, const uint8_t* d_img, uint32
 void launch_run_emit(RunGrid g, uint32_t n_layers, const uint8_t* d_img, const uint32_t* d_offsets, uint32_t total,
                      uint32_t* d_start, uint8_t* d_value, hipStream_t s);
 
+// Bodies of the layer stack (implisolid_layer_bodies; DESIGN "Bodies of the layer stack", bodies.hip): the
+// connected components of the target voxels (target 1: cov >= threshold, 0: cov < threshold) through the whole
+// stack under 6- or 26-adjacency, as a union-find over the stack's row runs.  The stack-wide arrays hold every
+// chunk's runs: d_runs {x0, x1} int32 pairs, d_parent one int32 a run, d_rowoff one uint32 per image row of the
+// stack + 1 (row l H + py holds runs [d_rowoff[row], d_rowoff[row + 1])).  Per chunk the launches go on s in the
+// order count, scan of d_counts (launch_scan_u32), launch_slice_layer_offsets with tpl = H, emit, link; only the
+// chunk's per-layer offsets are read back, between the scan and emit, to size the arrays.  Behind the last chunk:
+// root_rows over the stack's rows, the scan of its counts, roots, tally.
+struct BodyGrid {
+    int W, H;            // pixels per axis
+    uint32_t pitch;      // bytes per image row
+    int threshold, target, connectivity;
+};
+struct BodyState {       // zeroed before the first chunk; the chunks add to it
+    unsigned long long voxels;    // target voxels
+};
+constexpr uint32_t kBodyMaxChunk = 1u << 20;      // (layer, raster tile) pairs per chunk, as kRasterMaxChunk: a 256 MiB image
+constexpr uint64_t kBodyMaxPixels = 1ull << 28;   // what one chunk launch takes: a chunk is never less than one layer
+constexpr uint64_t kBodyMaxRows = 1ull << 30;     // image rows of a stack: 65536 layers of 16384 rows
+BodyGrid body_grid(int W, int H, uint32_t pitch, int threshold, int target, int connectivity);
+// count: d_counts[layer * H + py] = the row's target runs; the chunk's target voxels onto d_state->voxels
+void launch_body_count(BodyGrid g, uint32_t n_layers, const uint8_t* d_img, uint32_t* d_counts, BodyState* d_state, hipStream_t s);
+// emit: the chunk's `total` runs behind the `base` runs of the chunks before (base + total < 2^31): {x0, x1},
+// parent = own index, and the rows' offsets; d_offsets: the exclusive scan of d_counts.  l0: the chunk's first layer
+void launch_body_emit(BodyGrid g, uint32_t n_layers, int l0, const uint8_t* d_img, const uint32_t* d_offsets, uint32_t base,
+                      uint32_t total, int32_t* d_runs, int32_t* d_parent, uint32_t* d_rowoff, hipStream_t s);
+// link: every run of the chunk united with the adjacent runs of the row above it in its layer and of the layer
+// below (the chunk's own, or for its first layer the last of the chunk before, from the same arrays)
+void launch_body_link(BodyGrid g, uint32_t n_layers, int l0, const int32_t* d_runs, const uint32_t* d_rowoff, int32_t* d_parent,
+                      hipStream_t s);
+// root_rows: d_counts[row] = the row's roots, over the `rows` = layers x H rows of the stack
+void launch_body_root_rows(BodyGrid g, uint32_t rows, const uint32_t* d_rowoff, const int32_t* d_parent, uint32_t* d_counts,
+                           hipStream_t s);
+// roots: d_ord[root run] = its ordinal, and the records {seed, 0, MAX, MAX, l0, -1, -1, -1} in seed order; d_offsets:
+// the exclusive scan of d_counts, total: its last entry (nothing is written at or past it)
+void launch_body_roots(BodyGrid g, uint32_t rows, const int32_t* d_runs, const uint32_t* d_rowoff, const int32_t* d_parent,
+                       const uint32_t* d_offsets, uint32_t total, uint32_t* d_ord, long long* d_rec, hipStream_t s);
+// tally: every run's length and extent added to its body's record; d_out (nullable): {start, length, body} per run
+void launch_body_tally(BodyGrid g, uint32_t rows, const int32_t* d_runs, const uint32_t* d_rowoff, int32_t* d_parent,
+                       const uint32_t* d_ord, uint32_t n_bodies, long long* d_rec, int32_t* d_out, hipStream_t s);
+
 // Rays against the solid (implisolid_raycast; DESIGN "Rays against the solid", raycast.hip): per ray the
 // first solid sample of the table d_ts (host.hpp ray_params, N + 1 floats), the bisection inside its
 // bracket and the normal there.  One chunk = n rays (3 n floats of origins and directions each); both

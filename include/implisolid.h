@@ -533,6 +533,62 @@ int implisolid_layer_runs_copy(uint32_t* start, uint8_t* value);
  * over its chunks, -1 before any.  Returns 0 */
 int implisolid_debug_layer_runs_ms(int enable, double ms[3]);
 
+/* Additive: the bodies of the layer stack on the GPU -- the connected components of the voxels through the
+ * whole stack: whether the solid is one piece, which parts float, and which empty regions are sealed on all
+ * sides and would trap resin (no reference counterpart).  Arguments, limits, refusals and their order are
+ * implisolid_islands': shape_json, ignore_root_matrix, rect, width, height in [1, 16384], supersample s in
+ * {1, 2, 4}, z, n_layers, threshold in [1, s^2]; further
+ *   target        1: the solid voxels (cov >= threshold); 0: the empty ones (cov < threshold); anything else is
+ *                 refused
+ *   connectivity  6 or 26; anything else is refused
+ *   want_runs     0 or 1; anything else is refused
+ * cov[l][py][px] is exactly implisolid_raster's.  A voxel is (l, py, px), l being the position in the caller's z
+ * list: the neighbours of layer l are entries l - 1 and l + 1 of z, whatever the heights are (repeated and
+ * unsorted planes are legal, as everywhere else).  Two target voxels are adjacent if they differ by one step in
+ * exactly one of px, py, l (connectivity 6), or by at most one step in each and are not equal (connectivity
+ * 26).  Adjacency holds inside the stack only: there is no implicit border of either class.  A body is a class
+ * of the transitive closure of adjacency.  Restricted to one layer, connectivity 6 is implisolid_islands' 4 and
+ * connectivity 26 its 8.
+ * The key of a voxel is l * W * H + py * W + px, an int64.  One record per body, eight int64 {seed, volume, x0,
+ * y0, l0, x1, y1, l1}:
+ *   seed                     the smallest key among the body's voxels: the seed lies in layer l0
+ *   volume                   its voxel count
+ *   x0, y0, l0, x1, y1, l1   the inclusive bounding box
+ * in increasing seed.  With target 0 a body that touches no face of the stack (x0 > 0, y0 > 0, l0 > 0, x1 < W -
+ * 1, y1 < H - 1, l1 < n_layers - 1) is an enclosed void; with target 1 a body with l0 > 0 starts in mid-air.
+ * The row runs are the compact form of the label image: a row run is a maximal sequence of target voxels
+ * within one image row, so row runs never cross a row end (unlike implisolid_layer_runs' stream runs).  With
+ * want_runs one record per row run is kept, three int32 {start = py * W + x0, length, body}, body being the
+ * index of its body's record; the runs come layer by layer, within a layer in increasing start.
+ *   run_offsets  n_layers + 1 entries, required, always filled: layer l's row runs are [run_offsets[l],
+ *                run_offsets[l + 1])
+ *   stats        (may be NULL) implisolid_raster's five figures, then the row runs, the bodies and the target
+ *                voxels
+ *   returns      the number of bodies B, or -1 with implisolid_last_error(): implisolid_raster's refusals, a bad
+ *                threshold, target, connectivity or want_runs, or run_offsets NULL -- all refused before
+ *                anything is compiled or reaches a device --, or at run time a stack that reaches 2^31 row runs
+ *                or 2^31 bodies
+ * The records, and the runs when asked for, stay in one library-owned host slot until the next
+ * implisolid_layer_bodies call; a failed call empties the slot.  implisolid_layer_bodies_copy copies them out
+ * (bodies: 8 B int64; runs: 3 int32 per row run, may be NULL when the call did not ask for runs): 0, or -1 when
+ * there is nothing to copy or a needed pointer is NULL.
+ * Everything is an integer: no result depends on the pruning level, the chunking, the order in which atomics
+ * land or the launch geometry; before returning the library checks that the volumes add up to the target voxels
+ * counted from the images.  The labelling is a union-find over the row runs of the whole stack, not a voxel
+ * array: the image never leaves the device, the only per-pixel memory is a chunk's image, and the stack-wide
+ * device memory is 16 bytes per row run (28 with want_runs), 12 per image row and 64 per body.  Layers are
+ * processed in chunks of whole layers of at most IMPLISOLID_BODIES_CHUNK (layer, 16 x 16 tile) pairs
+ * (environment, read at each call; default and maximum 2^20, at least one layer's tiles): 2^28 pixels, a 256 MiB
+ * image; no image is carried between chunks.  One device, the interpreter kernels. */
+int64_t implisolid_layer_bodies(const char* shape_json, int ignore_root_matrix, const float rect[4], int width, int height,
+                                int supersample, const float* z, int n_layers, int threshold, int target, int connectivity,
+                                int want_runs, int64_t* run_offsets, int64_t stats[8]);
+int implisolid_layer_bodies_copy(int64_t* bodies, int32_t* runs);
+/* diagnostics: with enable != 0 the following implisolid_layer_bodies calls time their kernels with HIP events;
+ * ms (may be NULL) = the last timed call's {raster passes, row-run count + scan + emit, link, finish}
+ * milliseconds summed over its chunks, -1 before any.  Returns 0 */
+int implisolid_debug_layer_bodies_ms(int enable, double ms[4]);
+
 /* Additive: rays cast at the solid on the GPU -- per ray the first hit, its distance, the field value
  * and the normal there (no reference counterpart: the reference front end ray-casts the mesh).
  *   origins, dirs  3 n floats each, n in [0, 2^24], every float finite.  A direction need not have unit
