@@ -115,10 +115,12 @@ __global__ __launch_bounds__(256) void k_raster_eval(const Program* __restrict__
     __shared__ uint32_t s_w[4];
     const int t = threadIdx.x;
     const TileAt at = tile_at(g, first + list[blockIdx.x]);
-    // the tile's modes word is block-uniform: uniform skips, scalar instruction fetch
+    // the tile's modes word is block-uniform: uniform skips, scalar instruction fetch.  The lane read returns an
+    // int: the low half goes through uint32_t, or its bit 31 (CSG node 15 pruned to its right operand) would be
+    // extended over the high half and give the nodes 16 .. 31 a mode that no interpreter knows
     const uint64_t m64 = lmodes[blockIdx.x];
-    const uint64_t m = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(m64 >> 32)) << 32) |
-                       (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)m64);
+    const uint64_t m = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(m64 >> 32)) << 32) |
+                       (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)m64);
     const int px = t & (kT - 1), py = t >> 4;
     uint32_t cov = 0;
     if (px < at.nx && py < at.ny) {

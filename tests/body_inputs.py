@@ -9,6 +9,7 @@ import itertools
 import numpy as np
 
 import island_inputs as ii
+import run_inputs as ri
 
 SIZES = ii.SIZES
 LAYERS = [1, 2, 3]
@@ -113,6 +114,44 @@ def sized(W, H, L):
     return np.random.default_rng(10000 * L + 100 * W + H).random((L, H, W)) < 0.6
 
 
+GROWING_NOISE = [2, 6, 12, 24, 40, 70, 110, 170, 260, 380]   # single pixels in rows 8 .. 19 of layer l
+
+
+def growing():
+    """ten layers of 64 x 24 whose run count rises from layer to layer, for a stack whose arrays outgrow their
+    block from chunk to chunk (a layer per chunk).  Rows 0 .. 1: a pillar of 2 x 2 pixels through every layer,
+    the stack's first run.  Rows 3 .. 5: a block in layers 0 .. 1 and, apart from it, a block in layers 7 .. 9.
+    Rows 8 .. 19: single pixels on even columns, GROWING_NOISE[l] of them in layer l, every layer's a superset of
+    the layer's below.  Row 22: one-pixel pillars at x = 40 and x = 60 through every layer, joined only by a bar in
+    the last.  Rows 2, 6 .. 7 and 20 .. 21 are empty: the four parts touch neither each other nor the pixels"""
+    L, H, W = len(GROWING_NOISE), 24, 64
+    b = np.zeros((L, H, W), bool)
+    b[:, 0:2, 0:2] = True
+    b[0:2, 3:6, 10:15] = True
+    b[7:10, 3:6, 30:35] = True
+    b[:, 22, 40] = b[:, 22, 60] = True
+    b[L - 1, 22, 40:61] = True
+    at = (131 * np.arange(12 * 32)) % (12 * 32)   # a fixed order of the places: 131 and 384 have no common factor
+    for l, n in enumerate(GROWING_NOISE):
+        b[l, 8 + at[:n] // 32, 2 * (at[:n] % 32)] = True
+    return b
+
+
+def rounds():
+    """two layers of two rows of 512 pixels for the passes that take a row's runs 64 at a time.  Layer 0: row 0 is
+    solid over [0, 300); row 1 holds a pixel at every even x, 256 runs, of which the first 150 stand under row 0:
+    under 6 its first two rounds of 64 runs are of row 0's body, the third holds 22 of them and 42 bodies of one
+    pixel, the fourth 64 such bodies.  Layer 1: a bar over [401, 404) of row 0 that touches nothing under 6, and
+    row 1 solid over [0, 290) and pixels at every fourth x behind it (292, 296, ...), over pixels of layer 0"""
+    b = np.zeros((2, 2, 512), bool)
+    b[0, 0, 0:300] = True
+    b[0, 1, 0::2] = True
+    b[1, 0, 401:404] = True
+    b[1, 1, 0:290] = True
+    b[1, 1, 292::4] = True
+    return b
+
+
 def empty():
     return np.zeros((3, 17, 65), bool)
 
@@ -135,4 +174,10 @@ PAINTED = {
     "empty": empty,
     "full": full,
     "chunked": ii.chunked,
+    "growing": growing,
+    "rounds": rounds,
+    # rows of two full steps of the walk and of two and three rounds of 64 runs, on irregular data
+    "dense_511": ri.PAINTED["dense_511"],
+    "dense_512": ri.PAINTED["dense_512"],
+    "dense_512_ends": ri.PAINTED["dense_512_ends"],
 }

@@ -1,6 +1,7 @@
 """Host side of the bodies query (implisolid_layer_bodies' argument checks, implisolid_layer_bodies_copy,
 bodies_decode, enclosed_voids, floating_bodies), the restatement tests/np_bodies.py against np_islands on single
-layers, and the preconditions of the cases of test_gpu_bodies.py.  No GPU."""
+layers, and the preconditions of the cases of test_gpu_bodies.py, among them a restatement of the sizing rule of the
+stack-wide arrays (body_layers' grow_keeping over engine.hip's block classes) on the run counts of `growing`.  No GPU."""
 import ctypes
 import json
 import os
@@ -14,6 +15,8 @@ import body_inputs as bi   # noqa: E402
 import island_inputs as ii   # noqa: E402
 import np_bodies   # noqa: E402
 import np_islands   # noqa: E402
+import run_inputs as ri   # noqa: E402
+import test_cpu_runs as cr   # noqa: E402  (the comb's reference image; its tests are not collected from here)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EYE = ii.EYE
@@ -28,6 +31,17 @@ def restated(name, target, connectivity):
     if key not in _REST:
         bits = bi.PAINTED[name]()
         _REST[key] = (bits,) + np_bodies.bodies(bits.astype(np.uint8), 1, target, connectivity)
+    return _REST[key]
+
+
+comb_image = cr.comb_image
+
+
+def comb_bodies(oracle, s, threshold, target, connectivity):
+    """np_bodies.bodies of the comb's reference image, computed once"""
+    key = ("comb", s, threshold, target, connectivity)
+    if key not in _REST:
+        _REST[key] = np_bodies.bodies(comb_image(oracle, s), threshold, target, connectivity)
     return _REST[key]
 
 
@@ -196,6 +210,168 @@ def test_the_chunked_stack_joins_bodies_across_the_chunk_borders():
         assert both.any() and np.array_equal(below[both], above[both]), "bodies run through the border"
     assert (rec[:, 4] < 4).any() and (rec[:, 7] >= 8).any() and len(rec) > 3
     assert any(r[4] == 4 for r in rec) or any(r[4] == 8 for r in rec), "a body that starts on a chunk's first layer"
+
+
+# ---- a stack that outgrows its arrays ----------------------------------------------------------------------------
+def pool_class(n):
+    """engine.hip's block sizes: at least 256 bytes, then eighths of an octave (5, 6, 7, 8 eighths of a power of two)"""
+    c = 256
+    while c < n:
+        c <<= 1
+    q = c >> 3
+    for k in (5, 6, 7, 8):
+        if n <= q * k and q * k >= 256:
+            return q * k
+    return c
+
+
+def regrowths(counts, item):
+    """body_layers' sizing of one stack-wide array of `item` bytes a run over chunks of counts[k] runs, from an empty
+    buffer: [(bytes kept, new block's bytes)] of every chunk that takes another block.  grow_keeping leaves a block
+    that holds total + cc + 1 entries; otherwise the new one is the class of max(want, 1.5 x bytes) and the first
+    `total` entries are copied over"""
+    out, size, total = [], 0, 0
+    for cc in counts:
+        want = (total + cc + 1) * item
+        if not (size and want <= size):
+            size = pool_class(max(want, size + size // 2, 256))
+            out.append((total * item, size))
+        total += cc
+    return out
+
+
+GROWING_CASES = [(1, 26), (0, 6)]   # what test_gpu_bodies.py runs in a process of its own
+GROWING_REGROWTHS = {}              # (target, connectivity) -> (of the runs, of the union-find), with bytes kept
+
+
+def test_the_sizing_rule_s_restatement():
+    assert [pool_class(n) for n in (1, 256, 257, 320, 321, 384, 449, 512, 513, 641, 1025)] == [256, 256, 320, 320, 384, 384, 512, 512, 640, 768, 1280]
+    assert regrowths([10], 8) == [(0, 256)] and regrowths([31, 1], 8) == [(0, 256), (248, 384)]
+    assert regrowths([31, 0, 16, 1], 8) == [(0, 256), (248, 384), (376, 640)], "a block that still fits is left; 1.5 x 384 = 576 is of the class 640"
+    assert regrowths([10, 200], 4) == [(0, 256), (40, 896)], "a chunk beyond 1.5 x: the class of what it needs"
+
+
+@pytest.mark.parametrize("target, connectivity", GROWING_CASES)
+def test_the_growing_stack_outgrows_its_arrays_chunk_by_chunk(target, connectivity):
+    bits, offs, rec, runs, dec = restated("growing", target, connectivity)
+    L, H, W = bits.shape
+    assert L == 10 and H <= 24 and W <= 64
+    counts = np.diff(offs).tolist()
+    assert all(b > a for a, b in zip(counts, counts[1:])), "the run count rises from layer to layer"
+    grown = [regrowths(counts, item) for item in (8, 4)]   # int32 {x0, x1} and the int32 parent, a layer per chunk
+    kept = [sum(1 for keep, size in g if keep > 0) for g in grown]
+    GROWING_REGROWTHS[(target, connectivity)] = kept
+    print("growing", target, connectivity, "runs per layer", counts, "blocks taken with bytes kept: runs", kept[0], grown[0], "parent", kept[1], grown[1])
+    assert min(kept) >= 3 and all(g[0][0] == 0 for g in grown), "both arrays move at least three times with earlier chunks' entries in them"
+    assert grown[0][-1][0] > 0 and len(grown[0]) > L // 2, "and still in the second half of the stack"
+
+
+@pytest.mark.parametrize("connectivity", [6, 26])
+def test_the_growing_stack_holds_the_stated_bodies(connectivity):
+    bits, offs, rec, runs, dec = restated("growing", 1, connectivity)
+    L, H, W = bits.shape
+    by_seed = {int(r[0]): r.tolist() for r in rec}
+    key = lambda l, y, x: (l * H + y) * W + x   # noqa: E731
+    # the pillar: the stack's first run is its root, and the last layer still adds runs to it
+    assert by_seed[0] == [0, 4 * L, 0, 0, 0, 1, 1, L - 1] and runs[0].tolist() == [0, 2, 0]
+    assert runs[offs[L - 1]].tolist() == [0, 2, 0] and runs[offs[L - 1] + 1].tolist() == [W, 2, 0]
+    assert by_seed[key(0, 3, 10)] == [key(0, 3, 10), 2 * 15, 10, 3, 0, 14, 5, 1], "a body that ends in layer 1"
+    assert by_seed[key(7, 3, 30)] == [key(7, 3, 30), 3 * 15, 30, 3, 7, 34, 5, 9], "a body that starts in layer 7"
+    # the pair: its second pillar's runs of the first layers are written by the first chunk and hang on x = 40's only
+    # through the bar of the last layer
+    assert by_seed[key(0, 22, 40)] == [key(0, 22, 40), 2 * (L - 1) + 21, 40, 22, 0, 60, 22, L - 1] and key(0, 22, 60) not in by_seed
+    assert not bits[:L - 1, 21:24, 41:60].any() and bits[L - 1, 22, 40:61].all()
+    assert dec[0, 22, 60] == dec[0, 22, 40] == dec[L - 1, 22, 50]
+    open_ = np_bodies.bodies(np.where(np.arange(L)[:, None, None] < L - 1, bits, False).astype(np.uint8), 1, 1, connectivity)
+    assert open_[3][0, 22, 60] != open_[3][0, 22, 40], "without the last layer they are two bodies"
+    assert len(rec) > 30 and (rec[:, 4] > 0).sum() > 20, "and the single pixels start bodies in every layer"
+
+
+# ---- rows of two full steps and more ---------------------------------------------------------------------------------
+DENSE = ["dense_511", "dense_512", "dense_512_ends"]
+
+
+def _row_runs(offs, runs, H, W):
+    """the run records of every row of the stack: {(l, py): int32 (n, 3)}"""
+    out = {}
+    for l in range(len(offs) - 1):
+        r = runs[offs[l]:offs[l + 1]]
+        for py in range(H):
+            out[(l, py)] = r[r[:, 0] // W == py]
+    return out
+
+
+@pytest.mark.parametrize("name", DENSE)
+def test_the_dense_rows_fill_both_steps_and_more_than_a_round(name):
+    bits = bi.PAINTED[name]()
+    L, H, W = bits.shape
+    assert (L, H) == (2, 3) and W in (511, 512) and 256 < W <= 512, "two steps of the walk; 512 is the table's limit"
+    for target in (0, 1):
+        on = bits == (target == 1)
+        for l in range(L):
+            for py in range(H):
+                starts = ri.step_starts(on[l, py])
+                assert len(starts) == 2 and min(starts) >= 40, (name, target, l, py, starts)
+                assert sum(starts) > 64, "more than one round of 64 runs in every row, of each class"
+                first = on[l, py] & ~np.concatenate(([False], on[l, py, :-1]))
+                assert len(set((np.flatnonzero(first[256:]) // 4).tolist())) >= 16, "starts in many lanes of the second step"
+    if name == "dense_512_ends":
+        assert bits[0, :, 511].all() and not bits[1, :, 511].any(), "a last pixel of each class in every row, behind a full step of ends"
+        assert ri.step_starts(bits[0, 1])[0] > 64 and sum(ri.step_starts(bits[0, 1])) > 128, "three rounds of 64 runs in a row"
+        assert sum(ri.step_starts(~bits[0, 1])) > 128
+    if W == 512:
+        assert any(bits[l, py, 511] for l in range(L) for py in range(H)) and not all(bits[l, py, 511] for l in range(L) for py in range(H))
+
+
+def test_some_dense_row_holds_more_than_128_solid_runs():
+    assert max(sum(ri.step_starts(row)) for name in DENSE for layer in bi.PAINTED[name]() for row in layer) > 128
+
+
+@pytest.mark.parametrize("name", DENSE)
+def test_long_dense_rows_hold_runs_of_many_bodies(name):
+    # under 6 a row of more than 64 runs holds runs of three and more bodies: the tally's step of mixed bodies
+    bits, offs, rec, runs, dec = restated(name, 1, 6)
+    rows = _row_runs(offs, runs, 3, bits.shape[2])
+    assert all(len(r) > 64 and len(set(r[:, 2].tolist())) >= 3 for r in rows.values())
+
+
+def test_the_rounds_stack_gathers_a_body_over_rounds_and_rows_and_then_mixes():
+    bits, offs, rec, runs, dec = restated("rounds", 1, 6)
+    rows = _row_runs(offs, runs, 2, 512)
+    kinds = {k: [sorted(set(r[i:i + 64, 2].tolist())) for i in range(0, len(r), 64)] for k, r in rows.items()}
+    assert [len(rows[k]) for k in sorted(rows)] == [1, 256, 1, 1 + 55]
+    # the tally's wave takes the four rows in turn: row 0's run and two whole rounds of row 1 are of body 0 ...
+    assert kinds[(0, 0)] == [[0]] and kinds[(0, 1)][:2] == [[0], [0]]
+    # ... the third round holds it beside bodies of its own, the fourth only such bodies ...
+    assert len(kinds[(0, 1)]) == 4 and kinds[(0, 1)][2][0] == 0 and len(kinds[(0, 1)][2]) == 1 + 42 and len(kinds[(0, 1)][3]) == 64
+    assert (rows[(0, 1)][:150, 2] == 0).all() and (rows[(0, 1)][150:, 2] > 0).all()
+    # ... the bar is another body in a step of its own, and the last row comes back to body 0 with others behind it
+    assert kinds[(1, 0)] != [[0]] and len(kinds[(1, 0)][0]) == 1 and rec[kinds[(1, 0)][0][0]].tolist() == [1024 + 401, 3, 401, 0, 1, 403, 0, 1]
+    assert rows[(1, 1)][:3, 2].tolist() == [0, 0, 0] and len(kinds[(1, 1)][0]) == 1 + 53
+    # the neighbour row of more than 64 runs: the runs of layer 1 bisect row (0, 1)'s 256
+    assert rows[(1, 1)][0].tolist() == [512, 290, 0] and len(rec) == 1 + 106 + 1
+    assert 1 < len(restated("rounds", 1, 26)[2]) < len(rec), "under 26 the bar and the pixel at x = 300 touch body 0 by a corner"
+
+
+def test_the_comb_fills_every_step_and_straddles_every_seam(oracle):
+    cov = comb_image(oracle, 1)
+    W, H = ri.COMB_W, ri.COMB_H
+    assert cov.shape == (2, H, W) and W == 4 * 256 + 6 and len(ri.COMB_TEETH) == 34
+    on = cov[0, 1] >= 1
+    solid, empty = ri.step_starts(on), ri.step_starts(~on)
+    print("comb, the middle row of plane 0: solid and empty starts per step", solid, empty)
+    # the last step holds six pixels: at most three starts of one class, so its count is of both classes
+    assert len(solid) == 5 and min(solid[:4]) >= 4 and min(empty[:4]) >= 4 and solid[4] >= 2 and empty[4] >= 2 and solid[4] + empty[4] >= 4
+    for x in ri.COMB_SEAMS:
+        assert on[x - 1] and on[x] and not on[x - 2] and not on[x + 1], "a tooth of two pixels on the seam"
+        assert not (cov[0, 0, x - 8:x + 8] >= 1).any() and not (cov[0, 2, x - 8:x + 8] >= 1).any(), "and an empty run across it above and below"
+    for conn in (6, 26):
+        offs, rec, runs, dec = comb_bodies(oracle, 1, 1, 0, conn)
+        assert len(rec) == 1 and rec[0].tolist() == [0, int((cov < 1).sum()), 0, 0, 0, W - 1, H - 1, 1], "the empty class is one body"
+        offs, rec, runs, dec = comb_bodies(oracle, 1, 1, 1, conn)
+        assert len(rec) == len(ri.COMB_TEETH), "and every tooth a solid body"
+    grey = comb_image(oracle, 2)
+    assert 1 < int(grey[grey < 4].max()) and int(grey.max()) == 4, "grey values beyond 0 / 1"
 
 
 # ---- the ABI ---------------------------------------------------------------------------------------------------

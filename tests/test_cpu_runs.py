@@ -49,6 +49,13 @@ def encoded(name):
     return _ENC[name]
 
 
+def comb_image(oracle, s):
+    """the comb's reference image uint8 (2, 3, 1030): np_raster.coverage of the oracle's field, through
+    test_gpu_raster._ref, which keeps it for the GPU tests"""
+    import test_gpu_raster as gr   # its tests are not collected from here
+    return gr._ref(None, oracle, "comb", ri.COMB, ri.COMB_RECT, ri.COMB_W, ri.COMB_H, s, ri.COMB_Z)[0]
+
+
 def _same(a, b):
     return all(x.dtype == y.dtype and np.array_equal(x, y) for x, y in zip(a, b))
 
@@ -173,6 +180,77 @@ def test_the_corner_pixels_are_runs_of_one():
 def test_the_tall_stack_has_more_rows_than_a_scan_tile():
     bits, offs, start, value = encoded("tall_thin")
     assert bits.shape[0] * bits.shape[1] > 4096 and len(start) > 4096
+
+
+# ---- rows of two full steps and more ---------------------------------------------------------------------------------
+DENSE = ["dense_511", "dense_512", "dense_512_ends"]
+
+
+def row_step_starts(offs, start, W, H, l):
+    """the run starts of layer l in each 256-pixel step of each row: int (H, steps)"""
+    p = start[offs[l]:offs[l + 1]].astype(np.int64)
+    out = np.zeros((H, (W + 255) // 256), np.int64)
+    np.add.at(out, (p // W, p % W // 256), 1)
+    return out
+
+
+@pytest.mark.parametrize("name", DENSE)
+def test_the_dense_rows_start_many_runs_in_both_steps(name):
+    bits, offs, start, value = encoded(name)
+    L, H, W = bits.shape
+    assert (L, H) == (2, 3) and 256 < W <= 512 and W in (511, 512), "two steps of the walk; 512 is the table's limit"
+    for l in range(L):
+        n = row_step_starts(offs, start, W, H, l)
+        print(name, l, "starts per row and step", n.tolist())
+        assert n.shape == (H, 2) and n.min() >= 80, "a start in most lanes of both steps of every row"
+        for target in (False, True):   # the runs of either class, as the bodies query walks them
+            assert all(sum(ri.step_starts(bits[l, py] == target)) > 64 for py in range(H))
+        p = start[offs[l]:offs[l + 1]].astype(np.int64)
+        second = p[p % W >= 256]
+        assert len(set((second % W % 256 // 4).tolist())) >= 48, "in many lanes of the second step"
+    if W == 512:
+        assert {bool(bits[l, py, 511]) for l in range(L) for py in range(H)} == {False, True}
+    if name == "dense_512_ends":
+        assert bits[0, :, 511].all() and not bits[1, :, 511].any(), "a last pixel of each value in every row"
+        assert sum(ri.step_starts(bits[0, 1])) > 128, "more than 128 runs of the solid class in a row"
+
+
+def test_the_comb_compiles_within_the_program_s_stacks(impli):
+    n_instr, depth = impli.program_info(ri.COMB)[:2]
+    n = len(ri.COMB_TEETH)
+    # two instructions a tooth and two a Union: 33 CSG nodes, so their two-bit pruning modes reach past the low half
+    # of the 64-bit modes word (and the last one past the 32 nodes that are pruned at all)
+    assert depth <= 16 and n_instr == 2 * n + 2 * (n - 1) and n - 1 > 32, (n_instr, depth)
+    flat = {"type": "Union", "matrix": EYE, "children": [c for group in ri.COMB["children"] for c in group["children"]]}
+    assert len(flat["children"]) == len(ri.COMB_TEETH)
+    with pytest.raises(impli.ImplisolidError) as e:   # why the teeth are grouped
+        impli.program_info(flat)
+    assert "too deep" in str(e.value)
+
+
+def test_the_comb_starts_runs_in_every_step_and_straddles_every_seam(oracle):
+    W, H = ri.COMB_W, ri.COMB_H
+    assert W == 4 * 256 + 6 and (W + 15) // 16 * 16 != W and 30 <= len(ri.COMB_TEETH) <= 48, "five steps, the last of six pixels; a few dozen teeth"
+    for s in (1, 2):
+        cov = comb_image(oracle, s)
+        assert cov.shape == (2, H, W) and cov.dtype == np.uint8
+        for threshold in sorted({0, 1, s * s}):
+            offs, start, value = np_runs.encode(cov, threshold)
+            n = row_step_starts(offs, start, W, H, 0)
+            print("comb", s, threshold, "starts per row and step, plane 0", n.tolist(), "plane 1", row_step_starts(offs, start, W, H, 1).tolist())
+            assert n.shape == (H, 5)
+            if threshold == s * s and s > 1:
+                continue   # full coverage only: the teeth of less than a pixel are gone, and the last step with them
+            assert n[1].min() >= 4, "the middle row starts four runs and more in each of the five steps"
+            v = np_runs.values(cov, threshold)[0]
+            first = set(start[offs[0]:offs[1]].tolist())
+            for x in ri.COMB_SEAMS:
+                assert v[1, x - 1] == v[1, x] != 0 and v[1, x - 2] == 0 and v[1, x + 1] == 0, "a tooth of two pixels on the seam"
+                assert W + x - 1 in first and W + x not in first and W + x + 1 in first, "its run crosses the seam"
+                assert (v[0, x - 6:x + 6] == 0).all(), "and a run of zeros crosses it in the row above"
+        if s == 2:
+            assert 1 < int(cov[cov < 4].max()) and int(cov.max()) == 4, "grey values beyond 0 / 1"
+    assert (comb_image(oracle, 1)[1] >= 1).any() and not np.array_equal(comb_image(oracle, 1)[0], comb_image(oracle, 1)[1]), "the planes differ"
 
 
 # ---- the ABI -------------------------------------------------------------------------------------------------------

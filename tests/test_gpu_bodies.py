@@ -6,9 +6,14 @@ the oracle's field values for the shapes (test_gpu_raster._ref, as in test_gpu_i
 records, the run records and their decoded label stack are integers and must equal it exactly, for both targets
 and both connectivities, whatever the pruning level skips or fills and however the layers are chunked.  The
 preconditions of the cases are asserted without a GPU in test_cpu_bodies.py.
+
+Rows of two full steps of the walk with runs in every lane (dense_511, dense_512, dense_512_ends) and of five steps
+(the comb, 1030 pixels), rows of two to four rounds of 64 runs (the dense rows, rounds) and a stack whose arrays
+outgrow their block chunk by chunk in a process of its own (growing, tests/bodies_grow_worker.py) are among them.
 """
 import ctypes
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -19,6 +24,7 @@ import body_inputs as bi   # noqa: E402
 import island_inputs as ii   # noqa: E402
 import np_bodies   # noqa: E402
 import np_islands   # noqa: E402
+import run_inputs as ri   # noqa: E402
 import test_cpu_bodies as cb   # noqa: E402  (the cached restatements; its tests are not collected from here)
 import test_cpu_islands as ci   # noqa: E402  (the sphere pair)
 import test_gpu_mass as gm   # noqa: E402
@@ -160,6 +166,57 @@ def test_chunks_give_the_same_answer(impli, name, tiles, target, connectivity, m
     for r in (one, each, four):
         _check(impli, r, (ro, rb, rr, rd), W, H)
         assert all(np.array_equal(x, y) for x, y in zip(r[:3], one[:3])) and r[3][5:] == one[3][5:]
+
+
+def test_a_fresh_process_grows_its_arrays_chunk_by_chunk(impli, tmp_path):
+    # In this process the scratch that earlier tests left holds any test stack, and grow_keeping returns at once.
+    # A child's engine starts empty: with a layer per chunk the runs and the union-find of `growing` take a larger
+    # block in most chunks, the earlier chunks' entries copied over (test_cpu_bodies.py restates the sizes)
+    worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), "bodies_grow_worker.py")
+    for target, connectivity in cb.GROWING_CASES:
+        bits, ro, rb, rr, rd = cb.restated("growing", target, connectivity)
+        L, H, W = bits.shape
+        out = str(tmp_path / ("growing_%d_%d.npz" % (target, connectivity)))
+        env = {k: v for k, v in os.environ.items() if k != "IMPLISOLID_BODIES_CHUNK"}
+        p = subprocess.run([sys.executable, worker, out, str(target), str(connectivity)], env=env, capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, "the worker for %s ended with %d:\n%s" % ((target, connectivity), p.returncode, p.stderr[-4000:])
+        with np.load(out) as f:
+            got = (f["offsets"], f["bodies"], f["runs"], f["stats"].tolist())
+        print("growing", target, connectivity, "runs per layer", np.diff(got[0]).tolist(), "bodies", len(got[1]), "stats", got[3])
+        _check(impli, got, (ro, rb, rr, rd), W, H)
+        assert got[3][4] == L, "a layer per chunk"
+
+
+# ---- rows of five steps: the comb ----------------------------------------------------------------------------------
+def _comb_ref(oracle, s, threshold, target, connectivity):
+    # of the reference image that test_gpu_raster._ref keeps; test_cpu_bodies.py asserts what it holds
+    return cb.comb_bodies(oracle, s, threshold, target, connectivity)
+
+
+@pytest.mark.parametrize("level", [0, 2])
+@pytest.mark.parametrize("s, threshold", [(1, 1), (2, 1), (2, 4)])
+def test_the_comb_equals_the_restatement(impli, oracle, s, threshold, level):
+    W, H, z = ri.COMB_W, ri.COMB_H, ri.COMB_Z
+    assert np.array_equal(cb.comb_image(oracle, s), gr._ref(impli, oracle, "comb", ri.COMB, ri.COMB_RECT, W, H, s, z)[0])
+    for target, connectivity in CASES:
+        want = _comb_ref(oracle, s, threshold, target, connectivity)
+        got = _run(impli, level, ri.COMB, ri.COMB_RECT, W, H, z, s, threshold, target, connectivity)
+        print("comb", s, threshold, level, target, connectivity, "runs per layer", np.diff(got[0]).tolist(), "bodies", len(got[1]), "stats", got[3])
+        _check(impli, got, want, W, H)
+        assert got[3][4] == 1 and len(want[1]) > 0
+        if target == 0 and threshold == 1:
+            assert len(got[1]) == 1 and got[1][0].tolist() == (0, got[3][7], 0, 0, 0, W - 1, H - 1, 1), "the empty class is one body"
+
+
+def test_comb_chunks_give_the_same_answer(impli, oracle, monkeypatch):
+    z = ri.COMB_Z
+    for target, connectivity in ((1, 26), (0, 6)):
+        want = _comb_ref(oracle, 1, 1, target, connectivity)
+        monkeypatch.setenv("IMPLISOLID_BODIES_CHUNK", "1")    # a layer per chunk: plane 1 links to plane 0 in the stack's arrays
+        each = _run(impli, 2, ri.COMB, ri.COMB_RECT, ri.COMB_W, ri.COMB_H, z, 1, 1, target, connectivity)
+        monkeypatch.delenv("IMPLISOLID_BODIES_CHUNK")
+        assert each[3][4] == len(z) == 2
+        _check(impli, each, want, ri.COMB_W, ri.COMB_H)
 
 
 # ---- the shapes ------------------------------------------------------------------------------------------------

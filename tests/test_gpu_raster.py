@@ -162,6 +162,22 @@ def test_pruning_fills_and_skips_tiles_on_a_sphere(impli, oracle):
     assert abs(int(got2[1][0]) * h * h - np.pi * 0.25) <= 2 * np.pi * 0.5 * np.sqrt(2.0) * h
 
 
+@pytest.mark.parametrize("s", [1, 2])
+def test_pruned_tiles_of_a_tree_of_more_than_sixteen_csg_nodes(impli, oracle, s):
+    # the comb (tests/run_inputs.py) has 33 Unions: the modes of the nodes 16 .. 31 stand in the high half of a
+    # listed tile's modes word, and in its tiles node 15 keeps its right operand, which sets the low half's bit 31
+    import run_inputs as ri
+    W, H, z = ri.COMB_W, ri.COMB_H, ri.COMB_Z
+    want = _ref(impli, oracle, "comb", ri.COMB, ri.COMB_RECT, W, H, s, z)
+    solid_tiles = int((np.pad(want[0], ((0, 0), (0, 0), (0, 1040 - W))).reshape(len(z), H, 65, 16).max(axis=(1, 3)) > 0).sum())
+    for level in (0, 1, 2):
+        got = _at_level(impli, level, ri.COMB, ri.COMB_RECT, W, H, z, s)
+        print("comb", s, level, got[2])
+        _check_bits(got, want, W, H, s)
+        # a bound may list more tiles than hold a solid sample, never fewer; most of the image is empty
+        assert got[2][0] == 130 and (got[2][1] == 130 if level == 0 else solid_tiles <= got[2][1] + got[2][2] < 130), (solid_tiles, got[2])
+
+
 # ---- the mass sums: two independent kernel families ----------------------------------------------------------
 @pytest.mark.parametrize("box", sorted(gm.BOXES))
 @pytest.mark.parametrize("name", NAMES)

@@ -163,6 +163,36 @@ def test_chunks_of_a_shape_give_the_same_runs(impli, oracle, monkeypatch):
     _check(impli, got, cov, 0)
 
 
+# ---- rows of five steps: the comb ------------------------------------------------------------------------------------
+# 1030 x 3: four full steps of the walk and one of six pixels, run starts in every step of the middle row and a
+# tooth across every seam (test_cpu_runs.py asserts it on the reference image)
+@pytest.mark.parametrize("level", [0, 2])
+@pytest.mark.parametrize("s", [1, 2])
+def test_the_comb_equals_the_restatement_and_the_raster_image(impli, oracle, s, level):
+    W, H, z = ri.COMB_W, ri.COMB_H, ri.COMB_Z
+    cov = gr._ref(impli, oracle, "comb", ri.COMB, ri.COMB_RECT, W, H, s, z)[0]
+    assert np.array_equal(cov, cr.comb_image(oracle, s))
+    image, isums, istats = gr._at_level(impli, level, ri.COMB, ri.COMB_RECT, W, H, z, s)
+    for threshold in sorted({0, 1, s * s}):
+        got = _run(impli, level, ri.COMB, ri.COMB_RECT, W, H, z, s, threshold)
+        print("comb", s, level, threshold, "per layer", np.diff(got[0]).tolist(), "stats", got[4])
+        img = _check(impli, got, cov, threshold)
+        assert np.array_equal(img, np_runs.values(image, threshold)), "the decoded runs are raster_layers' image"
+        assert np.array_equal(got[3], isums) and got[4][:5] == istats and got[4][4] == 1
+        if threshold == 0 and s > 1:
+            assert 1 < int(got[2].max()) <= s * s, "grey values beyond 0 / 1"
+
+
+def test_comb_chunks_give_the_same_runs(impli, oracle, monkeypatch):
+    W, H, z = ri.COMB_W, ri.COMB_H, ri.COMB_Z
+    cov = gr._ref(impli, oracle, "comb", ri.COMB, ri.COMB_RECT, W, H, 2, z)[0]
+    monkeypatch.setenv("IMPLISOLID_RUNS_CHUNK", "1")    # below one layer's tiles: a layer per chunk
+    each = _run(impli, 2, ri.COMB, ri.COMB_RECT, W, H, z, 2, 0)
+    monkeypatch.delenv("IMPLISOLID_RUNS_CHUNK")
+    assert each[4][4] == len(z) == 2
+    _check(impli, each, cov, 0)
+
+
 # ---- the call sequence -----------------------------------------------------------------------------------------------
 def test_two_calls_give_identical_results(impli):
     a = (SHAPES["tree_deep"], RECTS["non_dyadic"], 33, 17, gr.Z, 4, 0)
