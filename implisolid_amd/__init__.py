@@ -58,6 +58,7 @@ ABI_SYMBOLS = [
     "implisolid_raster", "implisolid_raster_coords",
     "implisolid_islands", "implisolid_islands_copy", "implisolid_debug_islands_ms",
     "implisolid_layer_distance", "implisolid_debug_layer_distance_ms",
+    "implisolid_layer_hollow", "implisolid_hollow_wall2", "implisolid_debug_layer_hollow_ms",
     "implisolid_layer_runs", "implisolid_layer_runs_copy", "implisolid_debug_layer_runs_ms",
     "implisolid_layer_bodies", "implisolid_layer_bodies_copy", "implisolid_debug_layer_bodies_ms",
     "implisolid_raycast", "implisolid_ray_params", "implisolid_debug_raycast_ms",
@@ -224,6 +225,11 @@ def lib():
         "implisolid_layer_distance": ([c_char_p, c_int, fp, c_int, c_int, c_int, fp, c_int, c_int, ctypes.c_int64, ip,
                                        ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)], c_int),
         "implisolid_debug_layer_distance_ms": ([c_int, ctypes.POINTER(ctypes.c_double)], c_int),
+        "implisolid_layer_hollow": ([c_char_p, c_int, fp, c_int, c_int, c_int, fp, c_int, c_int, ctypes.POINTER(ctypes.c_int64), c_int,
+                                     c_int, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_int64),
+                                     ctypes.POINTER(ctypes.c_int64)], c_int),
+        "implisolid_hollow_wall2": ([ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_int64), c_int], c_int),
+        "implisolid_debug_layer_hollow_ms": ([c_int, ctypes.POINTER(ctypes.c_double)], c_int),
         "implisolid_layer_runs": ([c_char_p, c_int, fp, c_int, c_int, c_int, fp, c_int, c_int, ctypes.POINTER(ctypes.c_int64),
                                    ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)], ctypes.c_int64),
         "implisolid_layer_runs_copy": ([up, ctypes.POINTER(ctypes.c_uint8)], c_int),
@@ -755,7 +761,7 @@ def _rect4(rect, what):
 
 
 def _layer_args(what, rect, z, width, height, supersample):
-    """What raster_layers, layer_islands, layer_distance, layer_runs and layer_bodies do with their arguments first: (rect, z, W, H, s)."""
+    """What raster_layers, layer_islands, layer_distance, layer_hollow, layer_runs and layer_bodies do with their arguments first: (rect, z, W, H, s)."""
     r = _rect4(rect, what)
     zz = np.ascontiguousarray(z, np.float32).reshape(-1)
     W, H, s = int(width), int(height), int(supersample)
@@ -989,6 +995,62 @@ def layer_distance_kernel_ms(enable=True):
     """Diagnostics: switch the event timing of layer_distance()'s kernels on or off; returns the last timed
     call's (raster passes, column pass, row pass + records) ms, -1 before any."""
     return _pass_ms("layer_distance", 3, enable)
+
+
+HOLLOW_DTYPE = np.dtype([(name, np.int64) for name in ("solid", "core")])
+HOLLOW_MAX_REACH = 1024
+
+
+def hollow_wall2(wall_px, pitch_px):
+    """Host only: layer_hollow()'s threshold table for a wall of wall_px pixels over layers pitch_px pixels apart
+    (include/implisolid.h implisolid_hollow_wall2): int64 (R + 1,), wall2[j] = floor(wall^2 - (j pitch)^2) for every
+    j with (j pitch)^2 <= wall^2 -- the digital ellipsoid whose in-plane radius is the wall."""
+    w2 = np.empty(HOLLOW_MAX_REACH + 1, np.int64)
+    R = lib().implisolid_hollow_wall2(float(wall_px), float(pitch_px), w2.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), int(w2.size))
+    if R < 0:
+        raise ImplisolidError(last_error())
+    return w2[:R + 1].copy()
+
+
+def layer_hollow(shape, rect, width, height, z, wall2, supersample=1, threshold=1, ends=3, ignore_root_matrix=False,
+                 return_stats=False, want_out=True):
+    """The solid's layers z = z[l] hollowed to a shell on the GPU (include/implisolid.h implisolid_layer_hollow).
+    The images are raster_layers'; a pixel is solid iff its coverage >= threshold.  wall2 (reach + 1 entries,
+    non-increasing, hollow_wall2() makes one) holds the squared in-plane radius of the structuring element at a
+    layer offset of +-j: voxel (l, py, px) is core iff no empty voxel (m, q) has |m - l| <= reach and |q - p|^2 <=
+    wall2[|m - l|].  ends: bit 0 / bit 1 make the layers in front of entry 0 / behind the last entry count as
+    empty (a skin forms there); a clear bit means they do not exist.  Returns (out uint8 (L, H, W) = 0 for a core
+    voxel and the coverage for every other -- or None with want_out=False; records, a structured array
+    (HOLLOW_DTYPE) per layer of {solid, core} voxels), and with return_stats [raster_layers' five figures, solid
+    voxels, core voxels, layers whose distance transform was computed]."""
+    fp, lp = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64)
+    r, zz, W, H, s = _layer_args("layer_hollow", rect, z, width, height, supersample)
+    try:
+        w2 = np.ascontiguousarray(wall2).reshape(-1)
+        if w2.size < 1 or w2.dtype.kind not in "iu" or any(not -(1 << 63) <= int(v) < (1 << 63) for v in w2):
+            raise OverflowError
+        w2 = w2.astype(np.int64)
+    except (OverflowError, TypeError, ValueError):
+        raise ImplisolidError("layer_hollow: wall2 must be integers in [0, 2^30), one per layer offset 0 .. reach")
+    out = np.empty((zz.size, H, W), np.uint8) if want_out else None
+    records = np.zeros(zz.size, HOLLOW_DTYPE)
+    stats = (ctypes.c_int64 * 8)()
+    rc = lib().implisolid_layer_hollow(_s(shape), int(bool(ignore_root_matrix)), r.ctypes.data_as(fp), W, H, s,
+                                       zz.ctypes.data_as(fp), int(zz.size), int(threshold), w2.ctypes.data_as(lp),
+                                       min(int(w2.size) - 1, 1 << 30), int(ends),
+                                       out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)) if want_out else None,
+                                       records.ctypes.data_as(lp), stats)
+    if rc != 0:
+        raise ImplisolidError(last_error())
+    if return_stats:
+        return out, records, [int(v) for v in stats]
+    return out, records
+
+
+def layer_hollow_kernel_ms(enable=True):
+    """Diagnostics: switch the event timing of layer_hollow()'s kernels on or off; returns the last timed call's
+    (raster passes, ring copy + column pass, row pass, window pass) ms, -1 before any."""
+    return _pass_ms("layer_hollow", 4, enable)
 
 
 def layer_runs(shape, rect, width, height, z, supersample=1, threshold=0, ignore_root_matrix=False, return_stats=False):

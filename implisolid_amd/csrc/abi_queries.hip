@@ -1,7 +1,7 @@
 // abi_queries.hip -- the field queries of the C ABI: the interval probes, bounds, slices, layer images and
-// their islands, distance fields, run-length streams and bodies, rays and mass properties.  Each entry validates its request, compiles
+// their islands, distance fields, hollowed shells, run-length streams and bodies, rays and mass properties.  Each entry validates its request, compiles
 // the shape (QueryShape), puts it on the device and runs its passes; the scaffolding is abi_common.hpp's.
-// The five layer queries share their request (LayerRequest) and the passes that make a chunk's image
+// The six layer queries share their request (LayerRequest) and the passes that make a chunk's image
 // (LayerImages): each reads as what it does with the image.  The two ray queries share ray_request.  Slice,
 // islands, runs, bodies and ray spans place their records with abi_common.hpp's CountedOutput and keep them in a
 // ResultSlot; the timed queries keep their figures in a PassTimer.
@@ -361,7 +361,7 @@ int64_t implisolid_slice_loops(const uint32_t* keys, int64_t n_segments, int64_t
 
 }  // extern "C"
 
-// ---- what the layer queries share: the request and the image (raster, islands, layer distance, runs, bodies) ------
+// ---- what the layer queries share: the request and the image (raster, islands, layer distance, hollow, runs, bodies) ------
 namespace {
 // The request of implisolid_<entry>, refused in this order: n_layers, z, width / height, supersample, threshold
 // (an entry without one passes 1, which every supersample admits).  The entry's own checks follow, then
@@ -804,6 +804,187 @@ int implisolid_layer_distance(const char* shape_json, int ignore_root_matrix, co
 
 int implisolid_debug_layer_distance_ms(int enable, double ms[3]) {
     return g_dist_timer.entry(enable, ms);
+}
+
+}  // extern "C"
+
+// ---- hollowed layers (implisolid_layer_hollow) ----------------------------------------------------------------
+// Per chunk, behind LayerImages' head: the chunk's image copied into the image ring, distance.hip's column and row
+// passes into the distance ring (a chunk that wraps round the ring's end goes in two runs of consecutive slots),
+// then hollow.hip's window pass over the layers whose window is complete -- output lags input by reach layers -- in
+// batches of at most a chunk's layers, each copied into the caller's array.  Both rings hold chunk + 2 reach layers
+// (or the whole call, if that is fewer): the window of the oldest layer not yet emitted and a whole new chunk.  No
+// layer is rastered or transformed twice.  The records add up on the device and come down once.  Scratch of its
+// own: 0 the distance ring, 1 the records, 2 the threshold table, 3 the image ring, 4 a batch of out, 5 the row
+// pass's records (their solid counts are checked against the window pass's).
+namespace {
+PassTimer<4> g_hollow_timer;     // implisolid_debug_layer_hollow_ms: HIP events around the launches
+
+void hollow_layers(const QueryShape& q, const LayerRequest& r, int threshold, const int64_t* wall2, int reach, int ends, uint8_t* out,
+                   int64_t* layer_rec, int64_t stats[8]) {
+    Engine& E = *q.E;
+    hipStream_t s = q.s;
+    const int n_layers = r.n_layers;
+    LayerImages im(q, r, "hollow", "IMPLISOLID_HOLLOW_CHUNK", kHollowMaxChunk, true, g_hollow_timer.on);
+    const uint32_t chunk_layers = im.chunk_layers;
+    const uint32_t ring = (uint32_t)std::min<uint64_t>((uint64_t)chunk_layers + 2u * (uint64_t)reach, (uint64_t)n_layers);
+    const size_t layer_px = im.layer_px, layer_img = im.layer_img;
+    const DistGrid dg = dist_grid(r.W, r.H, im.g.pitch, threshold);
+    HollowGrid hg;
+    hg.W = r.W;
+    hg.H = r.H;
+    hg.pitch = im.g.pitch;
+    hg.threshold = threshold;
+    hg.n_layers = n_layers;
+    hg.reach = reach;
+    hg.ends = ends;
+    hg.ring = ring;
+    // every reserve before any pointer is taken
+    E.scratch(0).reserve((size_t)ring * layer_px * sizeof(int32_t));
+    E.scratch(1).reserve((size_t)n_layers * 2 * sizeof(uint64_t));
+    E.scratch(2).reserve((size_t)(reach + 1) * sizeof(int32_t));
+    E.scratch(3).reserve((size_t)ring * layer_img);
+    if (out) E.scratch(4).reserve((size_t)chunk_layers * layer_px);
+    E.scratch(5).reserve((size_t)n_layers * 4 * sizeof(uint64_t));
+    int32_t* d_dist = E.scratch(0).as<int32_t>();
+    unsigned long long* d_rec = E.scratch(1).as<unsigned long long>();
+    int32_t* d_wall2 = E.scratch(2).as<int32_t>();
+    uint8_t* d_ring = E.scratch(3).as<uint8_t>();
+    uint8_t* d_out = out ? E.scratch(4).as<uint8_t>() : nullptr;
+    unsigned long long* d_drec = E.scratch(5).as<unsigned long long>();
+    std::vector<int32_t> w32(wall2, wall2 + reach + 1);   // each in [0, 2^30): the entry checked
+    IMPLI_HIP(hipMemcpyAsync(d_wall2, w32.data(), w32.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    IMPLI_HIP(hipMemsetAsync(d_rec, 0, (size_t)n_layers * 2 * sizeof(uint64_t), s));
+    IMPLI_HIP(hipMemsetAsync(d_drec, 0, (size_t)n_layers * 4 * sizeof(uint64_t), s));
+    Timed<4, 4> tm(g_hollow_timer);   // behind im.ev[3]: the ring copy + columns, rows; around each window launch
+    int emitted = 0;                  // output layers [0, emitted) are done
+    int64_t transformed = 0;
+    auto emit = [&](int upto) {
+        while (emitted < upto) {
+            const uint32_t nb = (uint32_t)std::min<int64_t>(chunk_layers, upto - emitted);
+            tm.mark(2, s);
+            launch_hollow_window(hg, emitted, nb, d_ring, d_dist, d_wall2, d_out, d_rec, s);
+            tm.mark(3, s);
+            IMPLI_HIP(hipGetLastError());
+            if (out)   // the next batch's launch is ordered behind this copy
+                IMPLI_HIP(hipMemcpyAsync(out + (size_t)emitted * layer_px, d_out, (size_t)nb * layer_px, hipMemcpyDeviceToHost, s));
+            if (tm) {
+                IMPLI_HIP(hipStreamSynchronize(s));
+                tm.add(3, tm.ev[2], tm.ev[3]);
+            }
+            emitted += (int)nb;
+        }
+    };
+    while (im.next()) {
+        const int l0 = im.l0;
+        const uint32_t nl = im.nl;
+        // the chunk's runs of consecutive slots: two where it wraps round the ring's end
+        struct Run {
+            uint32_t first, slot, n;
+        } runs[2];
+        int n_runs = 0;
+        for (uint32_t done = 0; done < nl; ++n_runs) {
+            const uint32_t slot = (uint32_t)(l0 + (int)done) % ring;
+            runs[n_runs] = {done, slot, std::min(nl - done, ring - slot)};   // nl <= ring: at most two
+            done += runs[n_runs].n;
+        }
+        for (int k = 0; k < n_runs; ++k) {
+            const Run& u = runs[k];
+            IMPLI_HIP(hipMemcpyAsync(d_ring + (size_t)u.slot * layer_img, im.d_img + (size_t)u.first * layer_img, (size_t)u.n * layer_img,
+                                     hipMemcpyDeviceToDevice, s));
+            launch_distance_columns(dg, u.n, d_ring + (size_t)u.slot * layer_img, d_dist + (size_t)u.slot * layer_px, s);
+        }
+        tm.mark(0, s);
+        for (int k = 0; k < n_runs; ++k)
+            launch_distance_rows(dg, runs[k].n, l0 + (int)runs[k].first, d_dist + (size_t)runs[k].slot * layer_px, d_drec, s);
+        tm.mark(1, s);
+        IMPLI_HIP(hipGetLastError());
+        transformed += nl;
+        if (tm) {
+            IMPLI_HIP(hipStreamSynchronize(s));
+            tm.add(0, im.raster_ms());
+            tm.add(1, im.ev[3], tm.ev[0]);
+            tm.add(2, tm.ev[0], tm.ev[1]);
+        }
+        const int fed = l0 + (int)nl;   // layers [0, fed) are in the rings, the last ring of them still there
+        emit(fed == n_layers ? n_layers : std::max(0, fed - reach));
+    }
+    std::vector<unsigned long long> rec((size_t)n_layers * 2), drec((size_t)n_layers * 4);
+    IMPLI_HIP(hipMemcpyAsync(rec.data(), d_rec, rec.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    IMPLI_HIP(hipMemcpyAsync(drec.data(), d_drec, drec.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    IMPLI_HIP(hipStreamSynchronize(s));
+    if (emitted != n_layers || transformed != (int64_t)n_layers) throw HipError("hollow: a layer was left out");
+    int64_t solid = 0, core = 0;
+    for (int l = 0; l < n_layers; ++l) {
+        const unsigned long long* in = rec.data() + 2 * (size_t)l;
+        if (in[1] > in[0] || in[0] != drec[4 * (size_t)l]) throw HipError("hollow: a layer's record contradicts itself");
+        layer_rec[2 * (size_t)l] = (int64_t)in[0];
+        layer_rec[2 * (size_t)l + 1] = (int64_t)in[1];
+        solid += (int64_t)in[0];
+        core += (int64_t)in[1];
+    }
+    if (stats) {
+        im.stats(stats);
+        stats[5] = solid;
+        stats[6] = core;
+        stats[7] = transformed;
+    }
+}
+}  // namespace
+
+extern "C" {
+
+int implisolid_layer_hollow(const char* shape_json, int ignore_root_matrix, const float rect[4], int width, int height,
+                            int supersample, const float* z, int n_layers, int threshold, const int64_t* wall2, int reach, int ends,
+                            uint8_t* out, int64_t* layer_rec, int64_t stats[8]) {
+    last_error().clear();
+    if (!shape_json || !rect || !z || !wall2 || !layer_rec) {
+        report("implisolid_layer_hollow: bad arguments", false);
+        return -1;
+    }
+    return guard_device([&] {
+        // the request first: bad input is refused before anything is compiled or reaches the device
+        LayerRequest r("layer_hollow", rect, width, height, supersample, z, n_layers, threshold);
+        if (reach < 0 || reach > kHollowMaxReach) throw InputError("implisolid_layer_hollow: reach must be in [0, 1024]");
+        const uint64_t tpl = (uint64_t)((width + kRasterTile - 1) / kRasterTile) * (uint64_t)((height + kRasterTile - 1) / kRasterTile);
+        if ((2ull * (uint64_t)reach + 1ull) * tpl > kHollowMaxWindow)
+            throw InputError("implisolid_layer_hollow: (2 reach + 1) layers must hold at most 2^20 tiles");
+        for (int j = 0; j <= reach; ++j)
+            if (wall2[j] < 0 || wall2[j] >= (int64_t)kDistNone || (j && wall2[j] > wall2[j - 1]))
+                throw InputError("implisolid_layer_hollow: wall2 must be in [0, 2^30) and non-increasing");
+        if (ends < 0 || ends > 3) throw InputError("implisolid_layer_hollow: ends must be in [0, 3]");
+        r.sample();
+        QueryShape q(shape_json, ignore_root_matrix);
+        q.upload();
+        hollow_layers(q, r, threshold, wall2, reach, ends, out, layer_rec, stats);
+        return 0;
+    });
+}
+
+int implisolid_hollow_wall2(double wall_px, double pitch_px, int64_t* wall2, int cap) {
+    return guard_host([&] {
+        if (!std::isfinite(wall_px) || wall_px < 0.0 || !std::isfinite(pitch_px) || pitch_px <= 0.0)
+            throw InputError("implisolid_hollow_wall2: wall must be finite and >= 0, pitch finite and > 0");
+        const double w2 = wall_px * wall_px;
+        if (!(w2 < (double)kDistNone)) throw InputError("implisolid_hollow_wall2: wall^2 must be below 2^30");
+        int R = 0;   // the largest j with (j pitch)^2 <= wall^2: the squares do not decrease with j
+        while (R <= kHollowMaxReach) {
+            const double h = (double)(R + 1) * pitch_px;
+            if (!(h * h <= w2)) break;
+            ++R;
+        }
+        if (R > kHollowMaxReach) throw InputError("implisolid_hollow_wall2: the wall reaches more than 1024 layers");
+        if (!wall2 || R + 1 > cap) throw InputError("implisolid_hollow_wall2: wall2 holds fewer than reach + 1 entries");
+        for (int j = 0; j <= R; ++j) {
+            const double h = (double)j * pitch_px;
+            wall2[j] = (int64_t)std::floor(w2 - h * h);
+        }
+        return R;
+    });
+}
+
+int implisolid_debug_layer_hollow_ms(int enable, double ms[4]) {
+    return g_hollow_timer.entry(enable, ms);
 }
 
 }  // extern "C"

@@ -248,6 +248,28 @@ void launch_distance_rows(DistGrid g, uint32_t n_layers, int l0, int32_t* d_dist
 void launch_distance_unsupported(DistGrid g, uint32_t n_layers, int l0, int64_t reach2, const int32_t* d_dist, const int32_t* d_carry,
                                  unsigned long long* d_rec, hipStream_t s);
 
+// Hollowed layers (implisolid_layer_hollow; DESIGN "Hollowing the layer stack", hollow.hip): the window pass over
+// the distance fields of the layers within reach.  The images (as launch_raster_eval and launch_raster_fill left
+// them, H rows of `pitch` bytes, pitch a multiple of 16) and the distance fields (int32 [H][W], as
+// launch_distance_rows left them) live in two rings of `ring` layers, layer m of the call in slot m % ring; ring ==
+// n_layers, or ring > 2 reach (a voxel's window never meets itself).
+struct HollowGrid {
+    int W, H;            // pixels per axis
+    uint32_t pitch;      // bytes per image row
+    int threshold;
+    int n_layers;        // of the call
+    int reach, ends;     // layers within reach on either side; bit 0 / 1: the layers in front of / behind the call are empty
+    uint32_t ring;       // layers in either ring
+};
+constexpr uint32_t kHollowMaxChunk = 1u << 18;    // (layer, raster tile) pairs per chunk, as kDistMaxChunk
+constexpr int kHollowMaxReach = 1024;
+constexpr uint64_t kHollowMaxWindow = 1ull << 20; // (2 reach + 1) x tiles per layer: the carried window stays at or below 1 GiB
+// window: output layers [l0, l0 + n_out), every layer within reach of them inside the call in its slot of both
+// rings.  d_wall2: reach + 1 thresholds in [0, 2^30).  d_out (nullable): uint8 [n_out][H][W], 0 for a core voxel and
+// the coverage byte otherwise.  d_rec: two u64 per layer of the call {solid, core}, zeroed before the first batch
+void launch_hollow_window(HollowGrid g, int l0, uint32_t n_out, const uint8_t* d_img, const int32_t* d_dist, const int32_t* d_wall2,
+                          uint8_t* d_out, unsigned long long* d_rec, hipStream_t s);
+
 // Run-length layer images (implisolid_layer_runs; DESIGN "Run-length layer images", runs.hip): the runs of
 // every layer's row-major stream p = py W + px over the real pixels of a chunk's image (as launch_raster_eval
 // and launch_raster_fill left it: n_layers x H rows of `pitch` bytes, pitch a multiple of 16).  A pixel's value

@@ -486,6 +486,65 @@ int implisolid_layer_distance(const char* shape_json, int ignore_root_matrix, co
  * milliseconds summed over its chunks, -1 before any.  Returns 0 */
 int implisolid_debug_layer_distance_ms(int enable, double ms[3]);
 
+/* Additive: the layer stack hollowed to a shell of a given wall on the GPU -- the exact 3D erosion of the solid
+ * voxels by a structuring element given layer by layer, what a resin slicer's hollowing does, without a mesh and
+ * without downloading a distance field (no reference counterpart).  Arguments, limits, refusals and their order
+ * are implisolid_layer_distance's: shape_json, ignore_root_matrix, rect, width, height in [1, 16384], supersample
+ * s in {1, 2, 4}, z, n_layers, threshold in [1, s^2]; further, refused in this order,
+ *   reach         in [0, 1024]: the layers on either side that a voxel looks at.  (2 reach + 1) times the 16 x 16
+ *                 tiles of a layer must not exceed 2^20: the window of layers a voxel looks at stays on the device
+ *   wall2         required, reach + 1 entries, each in [0, 2^30), non-increasing: wall2[j] is the squared in-plane
+ *                 radius, in pixels, of the structuring element at a layer offset of +-j.  The library knows no z
+ *                 metric: layers are neighbours by their position in z, as everywhere else (repeated and unsorted
+ *                 planes are legal); implisolid_hollow_wall2 makes the table of an ellipsoid from a wall and a
+ *                 layer pitch in pixels
+ *   ends          in {0, 1, 2, 3}.  Bit 0: the layers in front of entry 0 of z count as empty, so a skin of the
+ *                 wall's thickness forms on the build plate; bit 1: the layers behind the last entry count as
+ *                 empty.  A clear bit means those layers do not exist, and the shell stays open there
+ * cov[l][py][px] is exactly implisolid_raster's and dist[l][py][px] exactly implisolid_layer_distance's.  A voxel
+ * (l, py, px) is solid iff cov >= threshold.  Only the pixels of the image exist in the plane.  A voxel is core
+ * iff for every j in [-reach, reach], with m = l + j,
+ *   0 <= m < n_layers   dist[m][py][px] > wall2[|j|]
+ *   m < 0               bit 0 of ends is clear
+ *   m >= n_layers       bit 1 of ends is clear
+ * Equivalently: no empty voxel (m, qy, qx), the virtual empty layers of ends included, has |m - l| <= reach and
+ * (qx - px)^2 + (qy - py)^2 <= wall2[|m - l|].  j = 0 makes every core voxel solid, at a squared distance of more
+ * than wall2[0] from every empty pixel of its own layer.  A layer of one class has dist = +-NONE (2^30): an
+ * all-solid layer passes every threshold and an empty one fails every one.  Because only the image's pixels
+ * exist, a rect without an empty margin around the solid leaves no skin at the image's sides: the solid is cut
+ * open there, exactly as dist sees no other class beyond the border.
+ *   out        (may be NULL: only the records come down) uint8 [n_layers][H][W], the caller's host buffer: 0 for
+ *              a core voxel, cov for every other.  The shell keeps its grey levels: out is the printable image
+ *   layer_rec  required, two int64 per layer {solid, core}: the layer's solid voxels and its core voxels
+ *   stats      (may be NULL) implisolid_raster's five figures, then the solid voxels, the core voxels and the
+ *              number of layers whose distance transform was computed (n_layers: none is computed twice)
+ *   returns    0, or -1 with implisolid_last_error(): implisolid_layer_distance's refusals, a bad reach, wall2 or
+ *              ends, or wall2 or layer_rec NULL; bad input is refused before anything is compiled or reaches a
+ *              device, and a refused call writes nothing
+ * There is no library-owned slot.  Everything is an integer: no result depends on the pruning level, the
+ * chunking, the order in which atomics land or the launch geometry; before returning the library checks core <=
+ * solid for every layer and the solid counts against the distance pass's.  Neither the images nor the distance
+ * fields leave the device.  Layers stream through in chunks of whole layers of at most IMPLISOLID_HOLLOW_CHUNK
+ * (layer, 16 x 16 tile) pairs (environment, read at each call; default and maximum 2^18, at least one layer's
+ * tiles).  A layer's output needs the layers up to reach ahead, so output lags input by reach layers: a ring of
+ * chunk + 2 reach distance layers (4 bytes a pixel) and as many image layers is carried on the device between
+ * chunks, and no layer is rastered or transformed twice.  One device, the interpreter kernels. */
+int implisolid_layer_hollow(const char* shape_json, int ignore_root_matrix, const float rect[4], int width, int height,
+                            int supersample, const float* z, int n_layers, int threshold,
+                            const int64_t* wall2, int reach, int ends,
+                            uint8_t* out, int64_t* layer_rec, int64_t stats[8]);
+/* host only, no GPU: the table of the digital ellipsoid with in-plane radius wall_px pixels over layers pitch_px
+ * pixels apart.  Returns R, the largest j >= 0 with (j pitch) (j pitch) <= wall wall, and fills wall2[j] = (int64)
+ * floor(wall wall - (j pitch) (j pitch)) for j <= R; the arithmetic is in doubles, each product and the
+ * difference rounded on its own, no fused multiply-add.  (3, 1) gives {9, 8, 5, 0}, (2.5, 2) gives {6, 2}.
+ * Returns -1 with implisolid_last_error(), nothing written, for a non-finite or negative wall, a non-finite
+ * pitch or pitch <= 0, wall wall >= 2^30, R > 1024, or R + 1 > cap (wall2 NULL counts as cap 0) */
+int implisolid_hollow_wall2(double wall_px, double pitch_px, int64_t* wall2, int cap);
+/* diagnostics: with enable != 0 the following implisolid_layer_hollow calls time their kernels with HIP events;
+ * ms (may be NULL) = the last timed call's {raster passes, copy into the ring and column pass, row pass, window
+ * pass} milliseconds summed over its chunks, -1 before any.  Returns 0 */
+int implisolid_debug_layer_hollow_ms(int enable, double ms[4]);
+
 /* Additive: the layer images as run-length streams on the GPU -- what a resin printer's file formats store
  * and what a slicer finally hands over, without downloading a pixel (no reference counterpart).  Arguments,
  * limits and refusals are implisolid_raster's, in the same order: shape_json, ignore_root_matrix, rect, width,
