@@ -59,6 +59,7 @@ ABI_SYMBOLS = [
     "implisolid_islands", "implisolid_islands_copy", "implisolid_debug_islands_ms",
     "implisolid_layer_distance", "implisolid_debug_layer_distance_ms",
     "implisolid_layer_hollow", "implisolid_hollow_wall2", "implisolid_debug_layer_hollow_ms",
+    "implisolid_layer_supports", "implisolid_layer_supports_copy", "implisolid_debug_layer_supports_ms",
     "implisolid_layer_runs", "implisolid_layer_runs_copy", "implisolid_debug_layer_runs_ms",
     "implisolid_layer_bodies", "implisolid_layer_bodies_copy", "implisolid_debug_layer_bodies_ms",
     "implisolid_raycast", "implisolid_ray_params", "implisolid_debug_raycast_ms",
@@ -230,6 +231,11 @@ def lib():
                                      ctypes.POINTER(ctypes.c_int64)], c_int),
         "implisolid_hollow_wall2": ([ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_int64), c_int], c_int),
         "implisolid_debug_layer_hollow_ms": ([c_int, ctypes.POINTER(ctypes.c_double)], c_int),
+        "implisolid_layer_supports": ([c_char_p, c_int, fp, c_int, c_int, c_int, fp, c_int, c_int, ctypes.c_int64, c_int,
+                                       ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                                       ctypes.POINTER(ctypes.c_int64)], ctypes.c_int64),
+        "implisolid_layer_supports_copy": ([ip], c_int),
+        "implisolid_debug_layer_supports_ms": ([c_int, ctypes.POINTER(ctypes.c_double)], c_int),
         "implisolid_layer_runs": ([c_char_p, c_int, fp, c_int, c_int, c_int, fp, c_int, c_int, ctypes.POINTER(ctypes.c_int64),
                                    ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)], ctypes.c_int64),
         "implisolid_layer_runs_copy": ([up, ctypes.POINTER(ctypes.c_uint8)], c_int),
@@ -761,7 +767,7 @@ def _rect4(rect, what):
 
 
 def _layer_args(what, rect, z, width, height, supersample):
-    """What raster_layers, layer_islands, layer_distance, layer_hollow, layer_runs and layer_bodies do with their arguments first: (rect, z, W, H, s)."""
+    """What raster_layers, layer_islands, layer_distance, layer_hollow, layer_supports, layer_runs and layer_bodies do with their arguments first: (rect, z, W, H, s)."""
     r = _rect4(rect, what)
     zz = np.ascontiguousarray(z, np.float32).reshape(-1)
     W, H, s = int(width), int(height), int(supersample)
@@ -1051,6 +1057,62 @@ def layer_hollow_kernel_ms(enable=True):
     """Diagnostics: switch the event timing of layer_hollow()'s kernels on or off; returns the last timed call's
     (raster passes, ring copy + column pass, row pass, window pass) ms, -1 before any."""
     return _pass_ms("layer_hollow", 4, enable)
+
+
+SUPPORT_DTYPE = np.dtype([(name, np.int32) for name in ("p", "depth", "foot", "load")])
+SUPPORT_REC_DTYPE = np.dtype([(name, np.int64) for name in ("unsupported", "tips")])
+
+
+def layer_supports(shape, rect, width, height, z, cell, supersample=1, threshold=1, reach2=0, ignore_root_matrix=False,
+                   return_stats=False):
+    """Support tips under the solid's layers z = z[l] on the GPU (include/implisolid.h implisolid_layer_supports):
+    one tip per non-empty cell of a grid of cell x cell pixels laid over each layer's unsupported pixels --
+    layer_distance()'s: solid, and dist < -reach2 at the same pixel of layer l - 1; none in layer 0.  Returns (tips,
+    a structured array (SUPPORT_DTYPE) of {p = py * width + px of the cell's unsupported pixel with the largest
+    dist, the smallest such p; depth = its dist (DIST_NONE in an all-solid layer); foot = the highest layer below
+    whose pixel p is solid, -1 when the column reaches the plate; load = the cell's unsupported pixels}, by layer
+    and within a layer by cell (py // cell) * ceil(width / cell) + px // cell; tip_offsets int64 (L + 1,): layer l's
+    tips are tips[tip_offsets[l]:tip_offsets[l + 1]]; records, a structured array (SUPPORT_REC_DTYPE) per layer of
+    {unsupported, tips}), and with return_stats also [raster_layers' five figures, unsupported pixels, tips, tips
+    with foot == -1].  cell=1 lists the unsupported pixels themselves."""
+    fp, lp = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64)
+    r, zz, W, H, s = _layer_args("layer_supports", rect, z, width, height, supersample)
+    if not -(1 << 63) <= int(reach2) < (1 << 63):
+        raise ImplisolidError("layer_supports: reach2 must be in [0, 2^30)")
+    if not 1 <= int(cell) <= 16384:
+        raise ImplisolidError("layer_supports: cell must be in [1, 16384]")
+    offs = np.zeros(zz.size + 1, np.int64)
+    records = np.zeros(zz.size, SUPPORT_REC_DTYPE)
+    stats = (ctypes.c_int64 * 8)()
+    n = lib().implisolid_layer_supports(_s(shape), int(bool(ignore_root_matrix)), r.ctypes.data_as(fp), W, H, s, zz.ctypes.data_as(fp),
+                                        int(zz.size), int(threshold), int(reach2), int(cell), offs.ctypes.data_as(lp),
+                                        records.ctypes.data_as(lp), stats)
+    if n < 0:
+        raise ImplisolidError(last_error())
+    tips = np.empty(n, SUPPORT_DTYPE)
+    if lib().implisolid_layer_supports_copy(tips.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))) != 0:
+        raise ImplisolidError(last_error())
+    if return_stats:
+        return tips, offs, records, [int(v) for v in stats]
+    return tips, offs, records
+
+
+def supports_decode(tips, tip_offsets, width):
+    """Host only: where layer_supports()'s tips are: (l, py, px), int64 (T,) each."""
+    offs = np.asarray(tip_offsets, np.int64).reshape(-1)
+    tips = np.asarray(tips)
+    p = (tips["p"] if tips.dtype.names else tips.reshape(-1, 4)[:, 0]).astype(np.int64).reshape(-1)
+    W = int(width)
+    if W < 1 or offs.size < 1 or offs[0] != 0 or offs[-1] != p.size or (np.diff(offs) < 0).any() or (p < 0).any():
+        raise ValueError("supports_decode: tip_offsets must run from 0 to len(tips) without decreasing, width >= 1")
+    l = np.repeat(np.arange(offs.size - 1, dtype=np.int64), np.diff(offs))
+    return l, p // W, p % W
+
+
+def layer_supports_kernel_ms(enable=True):
+    """Diagnostics: switch the event timing of layer_supports()'s kernels on or off; returns the last timed call's
+    (raster passes, column + row passes, cell pass, count + scan + emit + top passes) ms, -1 before any."""
+    return _pass_ms("layer_supports", 4, enable)
 
 
 def layer_runs(shape, rect, width, height, z, supersample=1, threshold=0, ignore_root_matrix=False, return_stats=False):

@@ -1,9 +1,9 @@
 // abi_queries.hip -- the field queries of the C ABI: the interval probes, bounds, slices, layer images and
-// their islands, distance fields, hollowed shells, run-length streams and bodies, rays and mass properties.  Each entry validates its request, compiles
+// their islands, distance fields, hollowed shells, support tips, run-length streams and bodies, rays and mass properties.  Each entry validates its request, compiles
 // the shape (QueryShape), puts it on the device and runs its passes; the scaffolding is abi_common.hpp's.
-// The six layer queries share their request (LayerRequest) and the passes that make a chunk's image
+// The seven layer queries share their request (LayerRequest) and the passes that make a chunk's image
 // (LayerImages): each reads as what it does with the image.  The two ray queries share ray_request.  Slice,
-// islands, runs, bodies and ray spans place their records with abi_common.hpp's CountedOutput and keep them in a
+// islands, supports, runs, bodies and ray spans place their records with abi_common.hpp's CountedOutput and keep them in a
 // ResultSlot; the timed queries keep their figures in a PassTimer.
 #include <cmath>
 #include <cstring>
@@ -361,7 +361,7 @@ int64_t implisolid_slice_loops(const uint32_t* keys, int64_t n_segments, int64_t
 
 }  // extern "C"
 
-// ---- what the layer queries share: the request and the image (raster, islands, layer distance, hollow, runs, bodies) ------
+// ---- what the layer queries share: the request and the image (raster, islands, layer distance, hollow, supports, runs, bodies) ------
 namespace {
 // The request of implisolid_<entry>, refused in this order: n_layers, z, width / height, supersample, threshold
 // (an entry without one passes 1, which every supersample admits).  The entry's own checks follow, then
@@ -985,6 +985,188 @@ int implisolid_hollow_wall2(double wall_px, double pitch_px, int64_t* wall2, int
 
 int implisolid_debug_layer_hollow_ms(int enable, double ms[4]) {
     return g_hollow_timer.entry(enable, ms);
+}
+
+}  // extern "C"
+
+// ---- support tips under the layer stack (implisolid_layer_supports) -------------------------------------------
+// Per chunk, behind LayerImages' head: distance.hip's column and row passes, then supports.hip's: the cell pass
+// into the chunk's zeroed table, count, the scan, a read-back of the chunk's per-layer tip offsets (their last
+// entry sizes the records), emit, and, where a chunk follows, the top pass; then the copy of the records into a
+// pinned staging slot.  There are two slots: the host appends a chunk from its slot to the result slot while the
+// device works on the next one.  The image and the distances stay on the device: the last distance layer of a
+// chunk is copied to a carry buffer for the first layer of the next, and `top` carries the highest solid layer
+// of every pixel in front of the chunk.  The per-layer unsupported counts add up on the device and come down
+// once.  Scratch of its own: 14 the counted output over the cells, 0 the distances, 1 the layers' unsupported
+// counts with the row pass's records and the bad flag behind them, 2 the carried layer, 3 the table, 4 the
+// chunk's records, 5 top.
+namespace {
+struct SupportSlot : ResultSlot {   // the last call's tips
+    PinnedVec<int32_t> tips;
+};
+SupportSlot g_supports;
+struct SupportStage {               // the staging slots, kept until exit (grow-only)
+    PinnedVec<int32_t> tips[2];
+};
+SupportStage g_support_stage;
+PassTimer<4> g_support_timer;       // implisolid_debug_layer_supports_ms: HIP events around the launches
+
+int64_t support_layers(const QueryShape& q, const LayerRequest& r, int threshold, int64_t reach2, int cell, int64_t* tip_offsets,
+                       int64_t* layer_rec, int64_t stats[8]) {
+    Engine& E = *q.E;
+    hipStream_t s = q.s;
+    const int n_layers = r.n_layers;
+    LayerImages im(q, r, "supports", "IMPLISOLID_SUPPORTS_CHUNK", kSupportMaxChunk, true, g_support_timer.on);
+    const DistGrid dg = dist_grid(r.W, r.H, im.g.pitch, threshold);
+    const SupportGrid sg = support_grid(r.W, r.H, im.g.pitch, threshold, cell);
+    const uint32_t chunk_layers = im.chunk_layers, ncc = sg.ncx * sg.ncy;   // ncc <= the layer's pixels
+    const size_t layer_px = im.layer_px, table = (size_t)chunk_layers * ncc;
+    const bool chunked = n_layers > (int)chunk_layers;
+    // every reserve before any pointer is taken (the records' buffer, sized per chunk, holds nothing else)
+    CountedOutput tips(E.scratch(14), table, ncc);   // a cell's tip, a layer's offset
+    E.scratch(0).reserve((size_t)chunk_layers * layer_px * sizeof(int32_t));          // distances
+    E.scratch(1).reserve((size_t)n_layers * 5 * sizeof(uint64_t) + sizeof(uint64_t)); // unsupported; the row pass's records; bad
+    if (chunked) E.scratch(2).reserve(layer_px * sizeof(int32_t));                    // the carried layer
+    E.scratch(3).reserve(table * (sizeof(uint64_t) + sizeof(uint32_t)));              // keys, then loads
+    if (chunked) E.scratch(5).reserve(layer_px * sizeof(int32_t));                    // top
+    int32_t* d_dist = E.scratch(0).as<int32_t>();
+    unsigned long long* d_unsup = E.scratch(1).as<unsigned long long>();
+    unsigned long long* d_drec = d_unsup + n_layers;
+    uint32_t* d_bad = reinterpret_cast<uint32_t*>(d_drec + 4 * (size_t)n_layers);
+    int32_t* d_carry = chunked ? E.scratch(2).as<int32_t>() : nullptr;
+    unsigned long long* d_keys = E.scratch(3).as<unsigned long long>();
+    uint32_t* d_loads = reinterpret_cast<uint32_t*>(d_keys + table);
+    int32_t* d_top = chunked ? E.scratch(5).as<int32_t>() : nullptr;
+    IMPLI_HIP(hipMemsetAsync(d_unsup, 0, (size_t)n_layers * 5 * sizeof(uint64_t) + sizeof(uint64_t), s));
+    g_supports.tips.resize(0);
+    Timed<4, 5> tm(g_support_timer);   // behind im.ev[3]: columns + rows, cells, count + scan; around emit + top
+    int64_t total = 0;
+    // the chunk whose records are on their way into a staging slot, not yet in the result slot
+    uint32_t pend = 0;
+    auto drain = [&](int slot) {   // after a synchronisation that covers the pending copy
+        if (pend) {
+            const size_t at = g_supports.tips.size();
+            g_supports.tips.resize(at + 4 * (size_t)pend);
+            std::memcpy(g_supports.tips.data() + at, g_support_stage.tips[slot].data(), (size_t)pend * 4 * sizeof(int32_t));
+        }
+        pend = 0;
+    };
+    while (im.next()) {   // its synchronisation: the last chunk's records have landed in the other slot
+        const int l0 = im.l0, slot = (int)((im.chunks - 1) & 1);
+        const uint32_t nl = im.nl;
+        const bool more = l0 + (int)nl < n_layers;
+        launch_distance_columns(dg, nl, im.d_img, d_dist, s);
+        launch_distance_rows(dg, nl, l0, d_dist, d_drec, s);
+        tm.mark(0, s);
+        IMPLI_HIP(hipMemsetAsync(d_keys, 0, (size_t)nl * ncc * sizeof(uint64_t), s));
+        IMPLI_HIP(hipMemsetAsync(d_loads, 0, (size_t)nl * ncc * sizeof(uint32_t), s));
+        launch_support_cells(sg, nl, l0, reach2, d_dist, d_carry, d_keys, d_loads, d_unsup, s);
+        tm.mark(1, s);
+        launch_support_count(sg, nl, d_keys, tips.d_counts, s);
+        const uint32_t cc = tips.place(nl, s, total, "implisolid_layer_supports: the result reaches 2^31 tips", tip_offsets + l0,
+                                       [&] { tm.mark(2, s); });   // the chunk's tips
+        int32_t* d_rec = nullptr;
+        if (cc) {
+            E.scratch(4).reserve((size_t)cc * 4 * sizeof(int32_t));
+            d_rec = E.scratch(4).as<int32_t>();
+        }
+        tm.mark(3, s);
+        if (cc) launch_support_emit(sg, nl, l0, d_keys, d_loads, tips.d_offsets, cc, im.d_img, d_top, d_rec, d_bad, s);
+        if (more) launch_support_top(sg, nl, l0, im.d_img, d_top, s);
+        tm.mark(4, s);
+        if (cc) {
+            g_support_stage.tips[slot].resize(0);   // nothing of the chunk before last is kept
+            g_support_stage.tips[slot].resize((size_t)cc * 4);
+            IMPLI_HIP(hipMemcpyAsync(g_support_stage.tips[slot].data(), d_rec, (size_t)cc * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        }
+        if (more)
+            IMPLI_HIP(hipMemcpyAsync(d_carry, d_dist + (size_t)(nl - 1) * layer_px, layer_px * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+        IMPLI_HIP(hipGetLastError());
+        drain(slot ^ 1);   // the chunk before this one, while the device works on this one
+        pend = cc;
+        total += cc;
+        if (tm) {   // only a timed call synchronises here
+            IMPLI_HIP(hipStreamSynchronize(s));
+            tm.add(0, im.raster_ms());
+            tm.add(1, im.ev[3], tm.ev[0]);
+            tm.add(2, tm.ev[0], tm.ev[1]);
+            tm.add(3, tm.ev[1], tm.ev[2]);
+            tm.add(3, tm.ev[3], tm.ev[4]);
+        }
+    }
+    std::vector<unsigned long long> unsup((size_t)n_layers * 5);   // the row pass's records behind the counts
+    uint32_t bad = 0;
+    IMPLI_HIP(hipMemcpyAsync(unsup.data(), d_unsup, unsup.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    IMPLI_HIP(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, s));
+    IMPLI_HIP(hipStreamSynchronize(s));
+    drain((int)((im.chunks - 1) & 1));
+    tip_offsets[n_layers] = total;
+    if (bad) throw HipError("supports: a tip lies outside its cell");
+    // the records against their definition
+    int64_t unsupported = 0, plate = 0;
+    for (int l = 0; l < n_layers; ++l) {
+        const int32_t* rec = g_supports.tips.data() + 4 * (size_t)tip_offsets[l];
+        const int64_t n = tip_offsets[l + 1] - tip_offsets[l];
+        int64_t load = 0, last_cell = -1;
+        for (int64_t k = 0; k < n; ++k) {
+            const int32_t* t = rec + 4 * k;
+            const int64_t p = t[0];
+            if (p < 0 || p >= (int64_t)layer_px || t[3] < 1 || t[1] < 1 || t[2] < -1 || t[2] > l - 2)
+                throw HipError("supports: a tip's record contradicts itself");
+            const int64_t c = (p / r.W / cell) * (int64_t)sg.ncx + (p % r.W) / cell;
+            if (c <= last_cell) throw HipError("supports: a tip lies outside the cell whose turn it is");
+            last_cell = c;
+            load += t[3];
+            plate += t[2] == -1;
+        }
+        if (load != (int64_t)unsup[(size_t)l] || n > (int64_t)unsup[(size_t)l] || unsup[(size_t)l] > unsup[(size_t)n_layers + 4 * (size_t)l])
+            throw HipError("supports: a layer's loads and its unsupported pixels disagree");
+        layer_rec[2 * (size_t)l] = (int64_t)unsup[(size_t)l];
+        layer_rec[2 * (size_t)l + 1] = n;
+        unsupported += (int64_t)unsup[(size_t)l];
+    }
+    if (stats) {
+        im.stats(stats);
+        stats[5] = unsupported;
+        stats[6] = total;
+        stats[7] = plate;
+    }
+    return total;
+}
+}  // namespace
+
+extern "C" {
+
+int64_t implisolid_layer_supports(const char* shape_json, int ignore_root_matrix, const float rect[4], int width, int height,
+                                  int supersample, const float* z, int n_layers, int threshold, int64_t reach2, int cell,
+                                  int64_t* tip_offsets, int64_t* layer_rec, int64_t stats[8]) {
+    last_error().clear();
+    g_supports.reset();
+    if (!shape_json || !rect || !z) {
+        report("implisolid_layer_supports: bad arguments", false);
+        return -1;
+    }
+    return guard_device([&]() -> int64_t {
+        // the request first: bad input is refused before anything is compiled or reaches the device
+        LayerRequest r("layer_supports", rect, width, height, supersample, z, n_layers, threshold);
+        if (reach2 < 0 || reach2 >= (int64_t)kDistNone) throw InputError("implisolid_layer_supports: reach2 must be in [0, 2^30)");
+        if (cell < 1 || cell > kSupportMaxCell) throw InputError("implisolid_layer_supports: cell must be in [1, 16384]");
+        if (!tip_offsets || !layer_rec) throw InputError("implisolid_layer_supports: tip_offsets and layer_rec are required");
+        r.sample();
+        QueryShape q(shape_json, ignore_root_matrix);
+        q.upload();
+        return g_supports.publish(support_layers(q, r, threshold, reach2, cell, tip_offsets, layer_rec, stats));
+    });
+}
+
+int implisolid_layer_supports_copy(int32_t* tips) {
+    if (g_supports.refuses_copy("layer_supports", "tips", g_supports.n == 0 || tips)) return -1;
+    if (g_supports.n > 0) std::memcpy(tips, g_supports.tips.data(), (size_t)g_supports.n * 4 * sizeof(int32_t));
+    return 0;
+}
+
+int implisolid_debug_layer_supports_ms(int enable, double ms[4]) {
+    return g_support_timer.entry(enable, ms);
 }
 
 }  // extern "C"

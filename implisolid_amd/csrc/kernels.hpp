@@ -270,6 +270,43 @@ constexpr uint64_t kHollowMaxWindow = 1ull << 20; // (2 reach + 1) x tiles per l
 void launch_hollow_window(HollowGrid g, int l0, uint32_t n_out, const uint8_t* d_img, const int32_t* d_dist, const int32_t* d_wall2,
                           uint8_t* d_out, unsigned long long* d_rec, hipStream_t s);
 
+// Support tips under the layer stack (implisolid_layer_supports; DESIGN "Support tips under the layer stack",
+// supports.hip): one tip per non-empty cell of a square grid over each layer's unsupported pixels (dist > 0 and
+// the pixel of the distance layer below < -reach2), and the layer each tip's column lands on.  The distances are
+// launch_distance_rows' (int32 [n_layers][H][W]), the image launch_raster_eval's and launch_raster_fill's
+// (n_layers x H rows of `pitch` bytes, pitch a multiple of 16, padding columns zero).  The chunk's table holds
+// per (layer, cell) an 8-byte key (dist << 32) | (0xFFFFFFFF - p) of the cell's tip, 0 for a cell without one,
+// and a 4-byte load; both zeroed before the cell pass.  Per chunk the launches go on s in the order cells,
+// count, scan of d_counts (launch_scan_u32), launch_slice_layer_offsets with tpl = ncx ncy, emit, top; only
+// the chunk's per-layer offsets are read back, between the scan and emit, to size the records.
+struct SupportGrid {
+    int W, H;            // pixels per axis
+    uint32_t pitch;      // bytes per image row
+    int threshold;
+    int cell;            // the side of a cell in pixels
+    uint32_t ncx, ncy;   // cells per axis: ceil(W / cell), ceil(H / cell)
+};
+constexpr uint32_t kSupportMaxChunk = 1u << 18;   // (layer, raster tile) pairs per chunk, as kDistMaxChunk
+constexpr int kSupportMaxCell = 16384;
+SupportGrid support_grid(int W, int H, uint32_t pitch, int threshold, int cell);
+// cells: every unsupported pixel's key and count onto its cell of the table, each layer's unsupported pixels
+// onto d_unsupported[l0 + layer].  Below the chunk's first layer lies d_carry (the last distance layer of the
+// chunk before, H x W; not read when l0 == 0: the call's first layer has no unsupported pixel)
+void launch_support_cells(SupportGrid g, uint32_t n_layers, int l0, int64_t reach2, const int32_t* d_dist, const int32_t* d_carry,
+                          unsigned long long* d_keys, uint32_t* d_loads, unsigned long long* d_unsupported, hipStream_t s);
+// count: d_counts[layer * ncx ncy + c] = the cell has a tip
+void launch_support_count(SupportGrid g, uint32_t n_layers, const unsigned long long* d_keys, uint32_t* d_counts, hipStream_t s);
+// emit: the records {p, depth, foot, load} in (layer, cell) order; d_offsets: the exclusive scan of d_counts,
+// total: its last entry (nothing is written at or past it).  foot: the highest layer below the tip's own
+// whose pixel p is solid, from the chunk's image down to its first layer, then d_top[p] (the same over the
+// layers in front of the chunk, -1 for none; null when l0 == 0).  *d_bad: raised where a record contradicts
+// its cell
+void launch_support_emit(SupportGrid g, uint32_t n_layers, int l0, const unsigned long long* d_keys, const uint32_t* d_loads,
+                         const uint32_t* d_offsets, uint32_t total, const uint8_t* d_img, const int32_t* d_top, int32_t* d_rec,
+                         uint32_t* d_bad, hipStream_t s);
+// top: d_top[p] raised to the highest solid layer of the chunk at p; l0 == 0 starts from -1 without reading it
+void launch_support_top(SupportGrid g, uint32_t n_layers, int l0, const uint8_t* d_img, int32_t* d_top, hipStream_t s);
+
 // Run-length layer images (implisolid_layer_runs; DESIGN "Run-length layer images", runs.hip): the runs of
 // every layer's row-major stream p = py W + px over the real pixels of a chunk's image (as launch_raster_eval
 // and launch_raster_fill left it: n_layers x H rows of `pitch` bytes, pitch a multiple of 16).  A pixel's value

@@ -545,6 +545,61 @@ int implisolid_hollow_wall2(double wall_px, double pitch_px, int64_t* wall2, int
  * pass} milliseconds summed over its chunks, -1 before any.  Returns 0 */
 int implisolid_debug_layer_hollow_ms(int enable, double ms[4]);
 
+/* Additive: support tips under the layer stack on the GPU -- where a resin slicer's supports touch the model and
+ * where each support's column lands, without downloading a distance field (no reference counterpart).  One tip per
+ * non-empty cell of a square grid laid over each layer's unsupported pixels.  Arguments, limits, refusals and their
+ * order are implisolid_layer_distance's: shape_json, ignore_root_matrix, rect, width, height in [1, 16384],
+ * supersample s in {1, 2, 4}, z, n_layers, threshold in [1, s^2], reach2 in [0, 2^30); shape_json, rect or z NULL
+ * is refused first.  Further, refused in this order,
+ *   cell          in [1, 16384]: the side of the placement grid in pixels
+ *   tip_offsets   required, n_layers + 1 int64
+ *   layer_rec     required, two int64 per layer
+ * cov[l][py][px] is exactly implisolid_raster's and dist[l][py][px] exactly implisolid_layer_distance's.
+ * Unsupported pixels: for l >= 1, U_l = { p : dist[l][p] > 0 and dist[l - 1][p] < -reach2 }; U_0 is empty, layer 0
+ * rests on the plate.  This is implisolid_layer_distance's unsupported, pixel for pixel.  "Below" is entry l - 1 of
+ * z, as everywhere else: repeated and unsorted planes are legal.
+ * Cells: ncx = ceil(W / cell), ncy = ceil(H / cell); the cell of p = (px, py) is c = (py / cell) ncx + px / cell
+ * (integer divisions).  The last cells of a row or column may be partial; a cell larger than both sides gives one.
+ * Tips: every (l, c) with a pixel of U_l in c yields one tip, the pixel of U_l in c with the largest dist[l][p]
+ * -- the pixel deepest inside its own layer, on an island's first layer its middle and not its rim --, among equals
+ * the smallest p = py W + px.
+ *   tips        (implisolid_layer_supports_copy) four int32 per tip {p, depth, foot, load}:
+ *     p           the tip's pixel, py W + px
+ *     depth       dist[l][p], which may be NONE = 2^30
+ *     foot        the largest m < l with cov[m][p] >= threshold: the layer of the model the support's column
+ *                 stands on; -1 when there is none and the column reaches the plate.  Layer l - 1 is empty at p
+ *                 (that made p unsupported): foot <= l - 2
+ *     load        the pixels of U_l in the cell: the unsupported pixels this tip stands for
+ *                 in order of layer, and within a layer of increasing c
+ *   tip_offsets layer l's tips are [tip_offsets[l], tip_offsets[l + 1])
+ *   layer_rec   per layer {unsupported = |U_l|, tips}
+ *   stats       (may be NULL) implisolid_raster's five figures, then the unsupported pixels, the tips and the tips
+ *               with foot == -1
+ *   returns     the number of tips, or -1 with implisolid_last_error(): the refusals above, or 2^31 tips or more
+ *               (found at run time); bad input is refused before anything is compiled or reaches a device, and a
+ *               refused call writes nothing
+ * cell = 1 lists the unsupported pixels themselves, each with its foot: the compact form of the overhang mask.
+ * The tips stay in a library-owned slot until the next implisolid_layer_supports call, which empties it whether it
+ * succeeds or not; implisolid_layer_supports_copy copies them out (tips may be NULL when there are none) and
+ * returns 0, or -1 when there is no result.  Everything is an integer: no result depends on the pruning level, the
+ * chunking, the order in which atomics land or the launch geometry; before returning the library checks that every
+ * layer's loads add up to its unsupported pixels, tips <= unsupported <= solid, and that every tip lies in the
+ * cell whose turn it is.  Neither the images nor the distance fields leave the device.  Layers go through in
+ * chunks of whole layers of at most IMPLISOLID_SUPPORTS_CHUNK (layer, 16 x 16 tile) pairs (environment, read at
+ * each call; default and maximum 2^18, at least one layer's tiles).  Device memory besides the image: 4 bytes a
+ * pixel of a chunk plus one carried layer for the distances; 12 bytes per cell of a chunk for the table of keys
+ * and loads, and 8 for its counts and offsets; where there is more than one chunk, 4 bytes a pixel for `top`,
+ * the highest solid layer of every pixel in front of the chunk, from which the feet below a chunk are read.
+ * One device, the interpreter kernels. */
+int64_t implisolid_layer_supports(const char* shape_json, int ignore_root_matrix, const float rect[4], int width, int height,
+                                  int supersample, const float* z, int n_layers, int threshold, int64_t reach2, int cell,
+                                  int64_t* tip_offsets, int64_t* layer_rec, int64_t stats[8]);
+int implisolid_layer_supports_copy(int32_t* tips);
+/* diagnostics: with enable != 0 the following implisolid_layer_supports calls time their kernels with HIP events;
+ * ms (may be NULL) = the last timed call's {raster passes, column and row passes, cell pass, count, scan, emit
+ * and top passes} milliseconds summed over its chunks, -1 before any.  Returns 0 */
+int implisolid_debug_layer_supports_ms(int enable, double ms[4]);
+
 /* Additive: the layer images as run-length streams on the GPU -- what a resin printer's file formats store
  * and what a slicer finally hands over, without downloading a pixel (no reference counterpart).  Arguments,
  * limits and refusals are implisolid_raster's, in the same order: shape_json, ignore_root_matrix, rect, width,
