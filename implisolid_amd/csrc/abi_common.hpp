@@ -1,4 +1,4 @@
-// abi_common.hpp -- what the files behind the C ABI share (abi.hip, abi_queries.hip).  Internal: not
+// abi_common.hpp -- what the files behind the C ABI share (abi.hip, abi_queries.hip, abi_layers.hip).  Internal: not
 // installed, not part of include/.
 #pragma once
 #include <algorithm>
@@ -253,6 +253,58 @@ struct ResultSlot {
         report(n < 0 ? who + "_copy: no " + noun + " to copy (the last " + who + " failed, or none ran)" : who + "_copy: bad arguments",
                false);
         return true;
+    }
+};
+
+// ---- two staging slots for a chunked query's records ----------------------------------------------------------
+// A chunk's records come down into one of two pinned staging slots, and the host moves them on to the result while
+// the device works on the next chunk.  The order: begin() at the head of a chunk, behind a synchronisation (the
+// chunk before has landed in the other slot), gives the chunk's slot; staged(at, n), behind the chunk's copies
+// into that slot, moves the chunk before out of the other slot and notes this one: n items for position `at` of
+// the result; finish(), behind the call's last synchronisation, moves the last chunk.  move(slot, at, n) is the
+// query's: what to move and where from.  No call of these synchronises.  The staging arrays are the query's,
+// grow-only and kept until exit; restage() sizes one for a chunk with nothing of an earlier chunk kept.
+template <class Move>
+struct StagingSlots {
+    Move move;
+    int slot = 1;        // of the chunk in hand
+    size_t at = 0;
+    uint32_t n = 0;      // the chunk on its way into a slot, not yet in the result; 0: none
+    explicit StagingSlots(Move m) : move(m) {}
+    int begin() { return slot ^= 1; }
+    void staged(size_t at_, uint32_t n_) {
+        flush(slot ^ 1);
+        at = at_;
+        n = n_;
+    }
+    void finish() { flush(slot); }
+private:
+    void flush(int from) {
+        if (n) move(from, at, n);
+        n = 0;
+    }
+};
+template <class T>
+void restage(PinnedVec<T>& v, size_t n) {
+    v.resize(0);
+    v.resize(n);
+}
+
+// ---- the layer a chunk leaves for the next ---------------------------------------------------------------------
+// The first layer of a chunk reads the layer below it, the last of the chunk before: n items of b, reserved only
+// where the call has more than one chunk (d is null otherwise: the first chunk reads none).
+template <class T>
+struct CarriedLayer {
+    T* d = nullptr;
+    size_t n;
+    CarriedLayer(DevBuf& b, size_t n, bool chunked) : n(n) {
+        if (!chunked) return;
+        b.reserve(n * sizeof(T));
+        d = b.as<T>();
+    }
+    // behind the chunk's passes: its last layer, where a chunk follows
+    void keep(const T* d_last, bool more, hipStream_t s) {
+        if (more) IMPLI_HIP(hipMemcpyAsync(d, d_last, n * sizeof(T), hipMemcpyDeviceToDevice, s));
     }
 };
 

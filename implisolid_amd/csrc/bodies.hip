@@ -50,13 +50,12 @@
 #include <stdexcept>
 
 #include "kernels.hpp"
+#include "layer_device.hpp"
 #include "unionfind_device.hpp"   // find_glb, unite<>
 
 namespace impli {
 
 namespace {
-
-typedef unsigned long long u64;
 
 // One step of a row's walk: the pixels [x0, x0 + 256), four per lane.  t: the lane's four class bits (bit k: pixel
 // x0 + 4 lane + k is of the target class; 0 at and past pixel W); returns the lane's four "starts a run" bits and
@@ -65,12 +64,11 @@ typedef unsigned long long u64;
 __device__ __forceinline__ uint32_t body_step(const BodyGrid& g, const uint8_t* __restrict__ row, int x0, int lane, uint32_t& carry,
                                               uint32_t& t, uint32_t& fall) {
     const int px = x0 + 4 * lane;
-    uint32_t cov4 = 0;
-    if ((uint32_t)px < g.pitch) cov4 = *reinterpret_cast<const uint32_t*>(row + px);   // pitch % 16 == 0: px + 3 < pitch
+    const uint32_t cov4 = cov_load4(row + px, (uint32_t)px < g.pitch);   // pitch % 16 == 0: px + 3 < pitch
     t = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const bool solid = (int)((cov4 >> (8 * k)) & 0xffu) >= g.threshold;
+        const bool solid = cov_solid(cov4, (uint32_t)k, g.threshold);
         t |= (uint32_t)(px + k < g.W && solid == (g.target != 0)) << k;
     }
     const uint32_t up = ((uint32_t)__shfl_up((int)t, 1, 64) >> 3) & 1u;
@@ -78,19 +76,6 @@ __device__ __forceinline__ uint32_t body_step(const BodyGrid& g, const uint8_t* 
     fall = ~t & before;
     carry = ((uint32_t)__builtin_amdgcn_readlane((int)t, 63) >> 3) & 1u;
     return t & ~before;
-}
-
-// the set bits of the four ballots of bits 0 .. 3 of `bits` in the lanes below this one, and in `all` in every lane
-__device__ __forceinline__ uint32_t ranks_below(uint32_t bits, uint32_t& all) {
-    uint32_t below = 0;
-    all = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const u64 m = __ballot((bits >> k) & 1u);
-        below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, below));
-        all += (uint32_t)__popcll(m);
-    }
-    return below;
 }
 
 // rows a wave of the count and tally passes takes in turn: their sums reach the state and the records with one
@@ -117,10 +102,10 @@ __global__ __launch_bounds__(256) void k_body_count(BodyGrid g, uint32_t rows, c
         }
         if (lane == 0) counts[R] = cnt;
     }
-    if (lane == 0) s_vox[wv] = vox;
+    wave_put(s_vox, vox);
     __syncthreads();   // every lane of the block arrives: no lane has returned
     if (threadIdx.x == 0) {
-        const uint32_t total = s_vox[0] + s_vox[1] + s_vox[2] + s_vox[3];
+        const uint32_t total = block_sum(s_vox);
         if (total) atomicAdd(&st->voxels, (u64)total);
     }
 }
@@ -326,16 +311,15 @@ __global__ __launch_bounds__(256) void k_body_tally(BodyGrid g, uint32_t rows, c
 }
 
 void check(const BodyGrid& g) {
-    if (g.W < 1 || g.H < 1 || g.pitch < (uint32_t)g.W || g.pitch % 16u != 0u || g.threshold < 1 || g.threshold > 16 ||
-        (g.target != 0 && g.target != 1) || (g.connectivity != 6 && g.connectivity != 26))
+    check_layer_chunk(g, 1u, "bodies", "grid out of range");
+    if (g.threshold < 1 || g.threshold > 16 || (g.target != 0 && g.target != 1) || (g.connectivity != 6 && g.connectivity != 26))
         throw std::runtime_error("bodies: grid out of range");
 }
 // a chunk's rows, and the rows of the stack in front of it
 void check(const BodyGrid& g, uint32_t n_layers, int l0) {
     check(g);
-    if (n_layers < 1u || l0 < 0 || (uint64_t)n_layers * (uint64_t)g.H * (uint64_t)g.W > kBodyMaxPixels ||
-        ((uint64_t)l0 + n_layers) * (uint64_t)g.H > kBodyMaxRows)
-        throw std::runtime_error("bodies: chunk out of range");
+    check_layer_chunk(g, n_layers, "bodies");
+    if (l0 < 0 || ((uint64_t)l0 + n_layers) * (uint64_t)g.H > kBodyMaxRows) throw std::runtime_error("bodies: chunk out of range");
 }
 void check_stack(const BodyGrid& g, uint32_t rows) {
     check(g);
@@ -343,17 +327,6 @@ void check_stack(const BodyGrid& g, uint32_t rows) {
 }
 
 }  // namespace
-
-BodyGrid body_grid(int W, int H, uint32_t pitch, int threshold, int target, int connectivity) {
-    BodyGrid g;
-    g.W = W;
-    g.H = H;
-    g.pitch = pitch;
-    g.threshold = threshold;
-    g.target = target;
-    g.connectivity = connectivity;
-    return g;
-}
 
 void launch_body_count(BodyGrid g, uint32_t n_layers, const uint8_t* d_img, uint32_t* d_counts, BodyState* d_state, hipStream_t s) {
     check(g, n_layers, 0);

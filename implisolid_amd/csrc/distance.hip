@@ -34,30 +34,15 @@
 #include <stdexcept>
 
 #include "kernels.hpp"
+#include "layer_device.hpp"
 
 namespace impli {
 
 namespace {
 
-typedef unsigned long long u64;
 constexpr int kBatch = 8;   // rows a column lane reads ahead
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d, 64);
-    return v;
-}
-__device__ __forceinline__ u64 wave_max(u64 v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d, 64);
-        const u64 o = ((u64)hi << 32) | lo;
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
-__global__ __launch_bounds__(256) void k_distance_columns(DistGrid g, uint32_t n_cols, const uint8_t* __restrict__ img,
+__global__ __launch_bounds__(256) void k_distance_columns(LayerGrid g, uint32_t n_cols, const uint8_t* __restrict__ img,
                                                           int32_t* __restrict__ dist) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n_cols) return;
@@ -109,7 +94,7 @@ __global__ __launch_bounds__(256) void k_distance_columns(DistGrid g, uint32_t n
     }
 }
 
-__global__ __launch_bounds__(256) void k_distance_rows(DistGrid g, int l0, int32_t* __restrict__ dist, u64* __restrict__ rec) {
+__global__ __launch_bounds__(256) void k_distance_rows(LayerGrid g, int l0, int32_t* __restrict__ dist, u64* __restrict__ rec) {
     extern __shared__ uint16_t s_c[];   // the row: 2 W bytes, rounded up to 16 (the static arrays below take 64)
     __shared__ uint32_t s_real[4], s_solid[4];
     __shared__ u64 s_key[4];
@@ -128,12 +113,16 @@ __global__ __launch_bounds__(256) void k_distance_rows(DistGrid g, int l0, int32
     }
     real = __any(real);
     solid = wave_sum(solid);
+    // Not wave_put(): two of them compile to two branches and move the search loop below by 20 bytes, and with that
+    // placement layer_distance, layer_hollow and layer_supports each took 3 % longer as a whole call (config 4's tree,
+    // 2048 x 2048 x 64 on an MI355X: 63.9 against 62.0 ms for layer_distance, five calls each with a spread of 0.3 ms).
+    // As written the kernel is byte for byte the one from before the helpers.
     if (lane == 0) {
         s_real[wv] = real;
         s_solid[wv] = solid;
     }
     __syncthreads();   // every c of the row is in LDS: the stores below overwrite them
-    const uint32_t n_solid = s_solid[0] + s_solid[1] + s_solid[2] + s_solid[3];
+    const uint32_t n_solid = block_sum(s_solid);
     const bool one_class = !(s_real[0] | s_real[1] | s_real[2] | s_real[3]) && (n_solid == 0u || n_solid == (uint32_t)W);
     u64 key = 0;
     for (int x = t; x < W; x += 256) {
@@ -177,7 +166,7 @@ __global__ __launch_bounds__(256) void k_distance_rows(DistGrid g, int l0, int32
 
 constexpr uint32_t kPerBlock = 1024;   // pixels per block of k_distance_unsupported
 
-__global__ __launch_bounds__(256) void k_distance_unsupported(DistGrid g, uint32_t blocks_per_layer, int l0, int reach2,
+__global__ __launch_bounds__(256) void k_distance_unsupported(LayerGrid g, uint32_t blocks_per_layer, int l0, int reach2,
                                                               const int32_t* __restrict__ dist, const int32_t* __restrict__ carry,
                                                               u64* __restrict__ rec) {
     __shared__ uint32_t s_cnt[4];
@@ -193,47 +182,31 @@ __global__ __launch_bounds__(256) void k_distance_unsupported(DistGrid g, uint32
         const uint32_t p = b * kPerBlock + (uint32_t)j * 256u + (uint32_t)t;
         if (p < px && mine[p] > 0) cnt += below[p] < -reach2;
     }
-    cnt = wave_sum(cnt);
-    if ((t & 63) == 0) s_cnt[t >> 6] = cnt;
+    wave_put(s_cnt, wave_sum(cnt));
     __syncthreads();
     if (t == 0) {
-        const uint32_t total = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        const uint32_t total = block_sum(s_cnt);
         if (total) atomicAdd(rec + 4 * (size_t)((uint32_t)l0 + ll) + 2, (u64)total);
     }
 }
 
-void check(const DistGrid& g, uint32_t n_layers) {
-    if (g.W < 1 || g.H < 1 || g.W > kRasterMaxSide || g.H > kRasterMaxSide || g.pitch < (uint32_t)g.W || n_layers < 1u ||
-        (uint64_t)n_layers * (uint64_t)g.H * (uint64_t)g.W > kDistMaxPixels)
-        throw std::runtime_error("distance: chunk out of range");
-}
-
 }  // namespace
 
-DistGrid dist_grid(int W, int H, uint32_t pitch, int threshold) {
-    DistGrid g;
-    g.W = W;
-    g.H = H;
-    g.pitch = pitch;
-    g.threshold = threshold;
-    return g;
-}
-
-void launch_distance_columns(DistGrid g, uint32_t n_layers, const uint8_t* d_img, int32_t* d_dist, hipStream_t s) {
-    check(g, n_layers);
+void launch_distance_columns(LayerGrid g, uint32_t n_layers, const uint8_t* d_img, int32_t* d_dist, hipStream_t s) {
+    check_layer_chunk(g, n_layers, "distance");
     const uint32_t n_cols = n_layers * (uint32_t)g.W;   // <= 2^28
     k_distance_columns<<<(n_cols + 255u) / 256u, 256, 0, s>>>(g, n_cols, d_img, d_dist);
 }
 
-void launch_distance_rows(DistGrid g, uint32_t n_layers, int l0, int32_t* d_dist, unsigned long long* d_rec, hipStream_t s) {
-    check(g, n_layers);
+void launch_distance_rows(LayerGrid g, uint32_t n_layers, int l0, int32_t* d_dist, unsigned long long* d_rec, hipStream_t s) {
+    check_layer_chunk(g, n_layers, "distance");
     const size_t lds = ((size_t)g.W * sizeof(uint16_t) + 15u) & ~(size_t)15u;   // <= 32 KiB: W <= kRasterMaxSide (check)
     k_distance_rows<<<n_layers * (uint32_t)g.H, 256, lds, s>>>(g, l0, d_dist, d_rec);   // <= 2^28 blocks
 }
 
-void launch_distance_unsupported(DistGrid g, uint32_t n_layers, int l0, int64_t reach2, const int32_t* d_dist, const int32_t* d_carry,
+void launch_distance_unsupported(LayerGrid g, uint32_t n_layers, int l0, int64_t reach2, const int32_t* d_dist, const int32_t* d_carry,
                                  unsigned long long* d_rec, hipStream_t s) {
-    check(g, n_layers);
+    check_layer_chunk(g, n_layers, "distance");
     if (reach2 < 0 || reach2 >= (int64_t)kDistNone) throw std::runtime_error("distance: reach2 out of range");
     if (l0 > 0 && !d_carry) throw std::runtime_error("distance: a later chunk needs the carried layer");
     if (l0 == 0 && n_layers == 1u) return;   // the call's first layer has nothing below

@@ -28,20 +28,13 @@
 #include <stdexcept>
 
 #include "kernels.hpp"
+#include "layer_device.hpp"
 
 namespace impli {
 
 namespace {
 
-typedef unsigned long long u64;
 constexpr int kAhead = 4;              // distance layers in flight before the first compare
-constexpr uint32_t kGroups = 256;      // four-pixel groups per block: one per lane
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d, 64);
-    return v;
-}
 
 template <bool kVec>
 __global__ __launch_bounds__(256) void k_hollow_window(HollowGrid g, uint32_t blocks_per_layer, int l0,
@@ -52,21 +45,16 @@ __global__ __launch_bounds__(256) void k_hollow_window(HollowGrid g, uint32_t bl
     const int t = threadIdx.x;
     const uint32_t ll = blockIdx.x / blocks_per_layer, b = blockIdx.x % blocks_per_layer;
     const int l = l0 + (int)ll;                                  // block-uniform
-    const uint32_t W = (uint32_t)g.W, gpr = (W + 3u) / 4u;       // groups per row
-    const uint32_t gi = b * kGroups + (uint32_t)t;
-    const bool active = gi < gpr * (uint32_t)g.H;                // <= 2^26
-    const uint32_t y = active ? gi / gpr : 0u, x4 = active ? (gi % gpr) * 4u : 0u;
-    const uint32_t nv = active ? (W - x4 < 4u ? W - x4 : 4u) : 0u;   // the group's pixels inside the row
-    const size_t px = (size_t)W * (size_t)g.H, layer_img = (size_t)g.H * g.pitch;
-    const size_t at = (size_t)y * W + x4;                        // the group in a distance layer and in out
+    const PixelGroup pg = pixel_group(g.W, g.H, b, t);
+    const size_t px = (size_t)(uint32_t)g.W * (size_t)g.H, layer_img = (size_t)g.H * g.pitch;
+    const size_t at = pg.at;                                     // the group in a distance layer and in out
     const uint32_t slot_l = (uint32_t)l % g.ring;
 
-    uint32_t cov4 = 0;
-    if (active) cov4 = *reinterpret_cast<const uint32_t*>(img + (size_t)slot_l * layer_img + (size_t)y * g.pitch + x4);
+    const uint32_t cov4 = cov_load4(img + (size_t)slot_l * layer_img + (size_t)pg.y * g.pitch + pg.x4, pg.active);
     uint32_t solid = 0;
 #pragma unroll
     for (uint32_t i = 0; i < 4; ++i)
-        if (i < nv && (int)((cov4 >> (8u * i)) & 0xffu) >= g.threshold) solid |= 1u << i;
+        if (i < pg.nv && cov_solid(cov4, i, g.threshold)) solid |= 1u << i;
 
     // a layer within reach outside the call, on a side that counts as empty: no voxel of this layer is core
     const bool skinned = ((g.ends & 1) && l < g.reach) || ((g.ends & 2) && l + g.reach >= g.n_layers);
@@ -92,15 +80,9 @@ __global__ __launch_bounds__(256) void k_hollow_window(HollowGrid g, uint32_t bl
         if (kVec) {
             if (core) {
 #pragma unroll
-                for (int u = 0; u < kAhead; ++u) {
-                    const int4 v = *reinterpret_cast<const int4*>(p[u]);
-                    d[u][0] = v.x;
-                    d[u][1] = v.y;
-                    d[u][2] = v.z;
-                    d[u][3] = v.w;
-                }
+                for (int u = 0; u < kAhead; ++u) load4<true>(p[u], 4u, d[u]);
             }
-        } else {
+        } else {   // pixel by pixel, each pixel's kAhead layers together: the shared load goes layer by layer
 #pragma unroll
             for (int i = 0; i < 4; ++i)
                 if ((core >> i) & 1u) {   // a core pixel is solid: inside the row
@@ -115,7 +97,7 @@ __global__ __launch_bounds__(256) void k_hollow_window(HollowGrid g, uint32_t bl
                 if (!(d[u][i] > w[u])) core &= ~(1u << i);
     }
 
-    if (out && active) {
+    if (out && pg.active) {
         uint32_t v = cov4;
 #pragma unroll
         for (uint32_t i = 0; i < 4; ++i)
@@ -126,18 +108,18 @@ __global__ __launch_bounds__(256) void k_hollow_window(HollowGrid g, uint32_t bl
         } else {
 #pragma unroll
             for (uint32_t i = 0; i < 4; ++i)
-                if (i < nv) o[i] = (uint8_t)(v >> (8u * i));
+                if (i < pg.nv) o[i] = (uint8_t)(v >> (8u * i));
         }
     }
 
     const uint32_t n_solid = wave_sum((uint32_t)__popc(solid)), n_core = wave_sum((uint32_t)__popc(core));
-    if ((t & 63) == 0) {
+    if ((t & 63) == 0) {   // both counts under one branch: two wave_put() are two
         s_solid[t >> 6] = n_solid;
         s_core[t >> 6] = n_core;
     }
     __syncthreads();
     if (t == 0) {
-        const uint32_t ts = s_solid[0] + s_solid[1] + s_solid[2] + s_solid[3], tc = s_core[0] + s_core[1] + s_core[2] + s_core[3];
+        const uint32_t ts = block_sum(s_solid), tc = block_sum(s_core);
         if (ts) atomicAdd(rec + 2 * (size_t)l, (u64)ts);
         if (tc) atomicAdd(rec + 2 * (size_t)l + 1, (u64)tc);
     }
@@ -147,15 +129,13 @@ __global__ __launch_bounds__(256) void k_hollow_window(HollowGrid g, uint32_t bl
 
 void launch_hollow_window(HollowGrid g, int l0, uint32_t n_out, const uint8_t* d_img, const int32_t* d_dist, const int32_t* d_wall2,
                           uint8_t* d_out, unsigned long long* d_rec, hipStream_t s) {
-    if (g.W < 1 || g.H < 1 || g.W > kRasterMaxSide || g.H > kRasterMaxSide || g.pitch < (uint32_t)g.W || (g.pitch & 15u) ||
-        g.threshold < 1 || g.n_layers < 1 || g.reach < 0 || g.reach > kHollowMaxReach || g.ends < 0 || g.ends > 3 || g.ring < 1u ||
+    check_layer_chunk(g, 1u, "hollow", "grid out of range");
+    if (g.threshold < 1 || g.n_layers < 1 || g.reach < 0 || g.reach > kHollowMaxReach || g.ends < 0 || g.ends > 3 || g.ring < 1u ||
         g.ring > (uint32_t)g.n_layers || (g.ring < (uint32_t)g.n_layers && g.ring <= 2u * (uint32_t)g.reach))   // a window fits the ring
         throw std::runtime_error("hollow: grid out of range");
-    if (n_out < 1u || l0 < 0 || (uint64_t)l0 + n_out > (uint64_t)g.n_layers || n_out > g.ring ||
-        (uint64_t)n_out * (uint64_t)g.H * (uint64_t)g.W > kDistMaxPixels)
-        throw std::runtime_error("hollow: batch out of range");
-    const uint32_t gpr = ((uint32_t)g.W + 3u) / 4u;
-    const uint32_t bpl = (gpr * (uint32_t)g.H + kGroups - 1u) / kGroups;   // <= 2^18
+    check_layer_chunk(g, n_out, "hollow", "batch out of range");   // n_out >= 1, and the batch's pixels
+    if (l0 < 0 || (uint64_t)l0 + n_out > (uint64_t)g.n_layers || n_out > g.ring) throw std::runtime_error("hollow: batch out of range");
+    const uint32_t bpl = groups_blocks(g);
     if (g.W % 4 == 0)
         k_hollow_window<true><<<n_out * bpl, 256, 0, s>>>(g, bpl, l0, d_img, d_dist, d_wall2, d_out, d_rec);
     else

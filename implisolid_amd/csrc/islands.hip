@@ -34,13 +34,13 @@
 #include <stdexcept>
 
 #include "kernels.hpp"
+#include "layer_device.hpp"
 #include "unionfind_device.hpp"   // find_lds, find_glb, unite<>
 
 namespace impli {
 
 namespace {
 
-typedef unsigned long long u64;
 constexpr int kTW = kIslandTileW, kTH = kIslandTileH;
 static_assert(kTW == 64, "one ballot is one tile row");
 static_assert(kTH % 4 == 0, "the four waves of a block share the rows evenly");
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256) void k_island_tiles(IslandGrid g, const uint8_
         s_lab[r * kTW + lane] = solid ? r * kTW + run_start(w, lane) : -1;
         cnt += (uint32_t)__popcll((u64)w);
     }
-    if (lane == 0) s_cnt[wv] = cnt;
+    wave_put(s_cnt, cnt);
     __syncthreads();
     for (int r = wv; r < kTH; r += 4) {
         if (r == 0) continue;
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(256) void k_island_tiles(IslandGrid g, const uint8_
         if (py < g.H && px < g.W) out[(size_t)py * (size_t)g.W + (size_t)px] = o;
     }
     if (t == 0) {
-        const uint32_t total = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        const uint32_t total = block_sum(s_cnt);
         if (total) atomicAdd(&st->solid, (u64)total);
     }
 }
@@ -228,23 +228,14 @@ __global__ __launch_bounds__(256) void k_island_tally(IslandGrid g, uint32_t n_w
 }
 
 void check(const IslandGrid& g, uint32_t n_layers) {
-    if (g.W < 1 || g.H < 1 || g.ntx != (g.W + kTW - 1) / kTW || g.nty != (g.H + kTH - 1) / kTH || g.pitch < (uint32_t)g.W ||
-        n_layers < 1u || (uint64_t)n_layers * (uint64_t)g.H * (uint64_t)g.W > kIslandMaxPixels)
-        throw std::runtime_error("islands: chunk out of range");
+    check_layer_chunk(g, n_layers, "islands");
+    if (g.ntx != (g.W + kTW - 1) / kTW || g.nty != (g.H + kTH - 1) / kTH) throw std::runtime_error("islands: chunk out of range");
 }
 
 }  // namespace
 
-IslandGrid island_grid(int W, int H, uint32_t pitch, int threshold, int connectivity) {
-    IslandGrid g;
-    g.W = W;
-    g.H = H;
-    g.ntx = (W + kTW - 1) / kTW;
-    g.nty = (H + kTH - 1) / kTH;
-    g.pitch = pitch;
-    g.threshold = threshold;
-    g.connectivity = connectivity;
-    return g;
+IslandGrid island_grid(const LayerGrid& g, int connectivity) {
+    return {g, (g.W + kTW - 1) / kTW, (g.H + kTH - 1) / kTH, connectivity};
 }
 
 void launch_island_tiles(IslandGrid g, uint32_t n_layers, const uint8_t* d_img, int32_t* d_lab, IslandState* d_state, hipStream_t s) {

@@ -3,6 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <stdexcept>
+#include <string>
+
 #include "grid.hpp"
 #include "host.hpp"
 #include "mc_types.hpp"
@@ -183,6 +186,22 @@ void launch_raster_eval(const Program* d_prog, int prog_depth, const float* d_ta
 void launch_raster_fill(RasterGrid g, int64_t first, int l0, uint32_t n_fill, const uint32_t* d_fill, uint8_t* d_img,
                         unsigned long long* d_sums, hipStream_t s);
 
+// What every layer pass takes: a chunk's image as launch_raster_eval and launch_raster_fill left it, n_layers x
+// H rows of `pitch` bytes with the padding columns zero.  A pass with parameters of its own derives its grid.
+struct LayerGrid {
+    int W, H;            // pixels per axis
+    uint32_t pitch;      // bytes per image row
+    int threshold;       // solid: cov >= threshold
+};
+constexpr uint64_t kLayerMaxPixels = 1ull << 28;   // what one launch takes: a chunk is never less than one layer
+// what every layer pass relies on; the passes add their own conditions.  what: the refusal's text behind "<who>: ",
+// for the passes that tell a bad grid from a bad chunk
+inline void check_layer_chunk(const LayerGrid& g, uint32_t n_layers, const char* who, const char* what = "chunk out of range") {
+    if (g.W < 1 || g.H < 1 || g.W > kRasterMaxSide || g.H > kRasterMaxSide || g.pitch < (uint32_t)g.W || g.pitch % 16u != 0u ||
+        n_layers < 1u || (uint64_t)n_layers * (uint64_t)g.H * (uint64_t)g.W > kLayerMaxPixels)
+        throw std::runtime_error(std::string(who) + ": " + what);
+}
+
 // Islands of the layers (implisolid_islands; DESIGN "Islands of the layers", islands.hip): the connected
 // components of the solid pixels (cov >= threshold) of a chunk's image, as launch_raster_eval and
 // launch_raster_fill left it (n_layers x H rows of `pitch` bytes, padding columns zero).  d_lab: int32
@@ -190,19 +209,16 @@ void launch_raster_fill(RasterGrid g, int64_t first, int l0, uint32_t n_fill, co
 // not solid.  The launches go on s in the order tiles, merge, rows, scan of d_counts (launch_scan_u32),
 // roots, tally; only the chunk's per-layer offsets (every H-th entry of the scan and its last) are read
 // back, between the scan and roots, to size the records.
-struct IslandGrid {
-    int W, H;            // pixels per axis
+struct IslandGrid : LayerGrid {
     int ntx, nty;        // label tiles per axis
-    uint32_t pitch;      // bytes per image row
-    int threshold, connectivity;
+    int connectivity;
 };
 struct IslandState {     // zeroed before the first chunk; the chunks add to it
     unsigned long long solid;     // solid pixels
 };
 constexpr int kIslandTileW = 64, kIslandTileH = 32;   // pixels per label tile
 constexpr uint32_t kIslandMaxChunk = 1u << 18;   // (layer, raster tile) pairs per chunk: 2^26 pixels, a 256 MiB label array
-constexpr uint64_t kIslandMaxPixels = 1ull << 28;   // what one launch takes: a chunk is never less than one layer
-IslandGrid island_grid(int W, int H, uint32_t pitch, int threshold, int connectivity);
+IslandGrid island_grid(const LayerGrid& g, int connectivity);
 // tiles: one block per tile; the tile-local components, labelled with their smallest index, into d_lab (every
 // pixel is written), the solid pixels onto d_state->solid
 void launch_island_tiles(IslandGrid g, uint32_t n_layers, const uint8_t* d_img, int32_t* d_lab, IslandState* d_state, hipStream_t s);
@@ -226,26 +242,19 @@ void launch_island_tally(IslandGrid g, uint32_t n_layers, int l0, const uint8_t*
 // by the pixel's own class.  d_dist: int32 [n_layers][H][W].  d_rec: four u64 per layer of the call {solid,
 // key, unsupported, unused}, zeroed before the first chunk; key = (D2 << 32) | (0xFFFFFFFF - index) of the
 // widest solid pixel, 0 when the layer has none.  The launches go on s in the order columns, rows, unsupported.
-struct DistGrid {
-    int W, H;            // pixels per axis
-    uint32_t pitch;      // bytes per image row
-    int threshold;
-};
 constexpr int kDistNone = 1 << 30;                // no pixel of the other class in the layer
 constexpr int kDistFar = 32768;                   // the column pass's "none in this column": kDistFar^2 == kDistNone
 constexpr uint32_t kDistMaxChunk = 1u << 18;      // (layer, raster tile) pairs per chunk, as kIslandMaxChunk
-constexpr uint64_t kDistMaxPixels = 1ull << 28;   // what one launch takes: a chunk is never less than one layer
-DistGrid dist_grid(int W, int H, uint32_t pitch, int threshold);
 // columns: one lane per (layer, column); d_dist = the signed vertical distance to the nearest pixel of the
 // other class in the column (+ solid, - empty), magnitude kDistFar where the column holds none
-void launch_distance_columns(DistGrid g, uint32_t n_layers, const uint8_t* d_img, int32_t* d_dist, hipStream_t s);
+void launch_distance_columns(LayerGrid g, uint32_t n_layers, const uint8_t* d_img, int32_t* d_dist, hipStream_t s);
 // rows: one block per (layer, row); d_dist = +-D2 in place, the layer's solid pixels and widest key onto d_rec
 // (layer l0 + ll of the call)
-void launch_distance_rows(DistGrid g, uint32_t n_layers, int l0, int32_t* d_dist, unsigned long long* d_rec, hipStream_t s);
+void launch_distance_rows(LayerGrid g, uint32_t n_layers, int l0, int32_t* d_dist, unsigned long long* d_rec, hipStream_t s);
 // unsupported: the solid pixels of every layer but the call's first whose pixel in the distance layer below is
 // < -reach2, onto d_rec.  Below the chunk's first layer lies d_carry (the last distance layer of the chunk
 // before, H x W; not read when l0 == 0)
-void launch_distance_unsupported(DistGrid g, uint32_t n_layers, int l0, int64_t reach2, const int32_t* d_dist, const int32_t* d_carry,
+void launch_distance_unsupported(LayerGrid g, uint32_t n_layers, int l0, int64_t reach2, const int32_t* d_dist, const int32_t* d_carry,
                                  unsigned long long* d_rec, hipStream_t s);
 
 // Hollowed layers (implisolid_layer_hollow; DESIGN "Hollowing the layer stack", hollow.hip): the window pass over
@@ -253,10 +262,7 @@ void launch_distance_unsupported(DistGrid g, uint32_t n_layers, int l0, int64_t 
 // them, H rows of `pitch` bytes, pitch a multiple of 16) and the distance fields (int32 [H][W], as
 // launch_distance_rows left them) live in two rings of `ring` layers, layer m of the call in slot m % ring; ring ==
 // n_layers, or ring > 2 reach (a voxel's window never meets itself).
-struct HollowGrid {
-    int W, H;            // pixels per axis
-    uint32_t pitch;      // bytes per image row
-    int threshold;
+struct HollowGrid : LayerGrid {
     int n_layers;        // of the call
     int reach, ends;     // layers within reach on either side; bit 0 / 1: the layers in front of / behind the call are empty
     uint32_t ring;       // layers in either ring
@@ -279,16 +285,13 @@ void launch_hollow_window(HollowGrid g, int l0, uint32_t n_out, const uint8_t* d
 // and a 4-byte load; both zeroed before the cell pass.  Per chunk the launches go on s in the order cells,
 // count, scan of d_counts (launch_scan_u32), launch_slice_layer_offsets with tpl = ncx ncy, emit, top; only
 // the chunk's per-layer offsets are read back, between the scan and emit, to size the records.
-struct SupportGrid {
-    int W, H;            // pixels per axis
-    uint32_t pitch;      // bytes per image row
-    int threshold;
+struct SupportGrid : LayerGrid {
     int cell;            // the side of a cell in pixels
     uint32_t ncx, ncy;   // cells per axis: ceil(W / cell), ceil(H / cell)
 };
 constexpr uint32_t kSupportMaxChunk = 1u << 18;   // (layer, raster tile) pairs per chunk, as kDistMaxChunk
 constexpr int kSupportMaxCell = 16384;
-SupportGrid support_grid(int W, int H, uint32_t pitch, int threshold, int cell);
+SupportGrid support_grid(const LayerGrid& g, int cell);
 // cells: every unsupported pixel's key and count onto its cell of the table, each layer's unsupported pixels
 // onto d_unsupported[l0 + layer].  Below the chunk's first layer lies d_carry (the last distance layer of the
 // chunk before, H x W; not read when l0 == 0: the call's first layer has no unsupported pixel)
@@ -314,19 +317,12 @@ void launch_support_top(SupportGrid g, uint32_t n_layers, int l0, const uint8_t*
 // differs from the stream's pixel before, across row ends too.  The launches go on s in the order count, scan of
 // d_counts (launch_scan_u32), launch_slice_layer_offsets with tpl = H, emit; only the chunk's per-layer offsets
 // are read back, between the scan and emit, to size the records.
-struct RunGrid {
-    int W, H;            // pixels per axis
-    uint32_t pitch;      // bytes per image row
-    int threshold;       // 0: the value is the coverage byte
-};
 constexpr uint32_t kRunMaxChunk = 1u << 20;       // (layer, raster tile) pairs per chunk, as kRasterMaxChunk: a 256 MiB image
-constexpr uint64_t kRunMaxPixels = 1ull << 28;    // what one launch takes: a chunk is never less than one layer
-RunGrid run_grid(int W, int H, uint32_t pitch, int threshold);
 // count: d_counts[layer * H + py] = the runs that start in the row
-void launch_run_count(RunGrid g, uint32_t n_layers, const uint8_t* d_img, uint32_t* d_counts, hipStream_t s);
+void launch_run_count(LayerGrid g, uint32_t n_layers, const uint8_t* d_img, uint32_t* d_counts, hipStream_t s);
 // emit: per run its start (p within its layer) and value, in (layer, start) order; d_offsets: the exclusive scan
 // of d_counts, total: its last entry (nothing is written at or past it)
-void launch_run_emit(RunGrid g, uint32_t n_layers, const uint8_t* d_img, const uint32_t* d_offsets, uint32_t total,
+void launch_run_emit(LayerGrid g, uint32_t n_layers, const uint8_t* d_img, const uint32_t* d_offsets, uint32_t total,
                      uint32_t* d_start, uint8_t* d_value, hipStream_t s);
 
 // Bodies of the layer stack (implisolid_layer_bodies; DESIGN "Bodies of the layer stack", bodies.hip): the
@@ -337,18 +333,14 @@ void launch_run_emit(RunGrid g, uint32_t n_layers, const uint8_t* d_img, const u
 // order count, scan of d_counts (launch_scan_u32), launch_slice_layer_offsets with tpl = H, emit, link; only the
 // chunk's per-layer offsets are read back, between the scan and emit, to size the arrays.  Behind the last chunk:
 // root_rows over the stack's rows, the scan of its counts, roots, tally.
-struct BodyGrid {
-    int W, H;            // pixels per axis
-    uint32_t pitch;      // bytes per image row
-    int threshold, target, connectivity;
+struct BodyGrid : LayerGrid {
+    int target, connectivity;
 };
 struct BodyState {       // zeroed before the first chunk; the chunks add to it
     unsigned long long voxels;    // target voxels
 };
 constexpr uint32_t kBodyMaxChunk = 1u << 20;      // (layer, raster tile) pairs per chunk, as kRasterMaxChunk: a 256 MiB image
-constexpr uint64_t kBodyMaxPixels = 1ull << 28;   // what one chunk launch takes: a chunk is never less than one layer
 constexpr uint64_t kBodyMaxRows = 1ull << 30;     // image rows of a stack: 65536 layers of 16384 rows
-BodyGrid body_grid(int W, int H, uint32_t pitch, int threshold, int target, int connectivity);
 // count: d_counts[layer * H + py] = the row's target runs; the chunk's target voxels onto d_state->voxels
 void launch_body_count(BodyGrid g, uint32_t n_layers, const uint8_t* d_img, uint32_t* d_counts, BodyState* d_state, hipStream_t s);
 // emit: the chunk's `total` runs behind the `base` runs of the chunks before (base + total < 2^31): {x0, x1},

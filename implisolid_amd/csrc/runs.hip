@@ -18,31 +18,26 @@
 #include <stdexcept>
 
 #include "kernels.hpp"
+#include "layer_device.hpp"
 
 namespace impli {
 
 namespace {
 
-typedef unsigned long long u64;
-
 // the four pixel values of a dword of coverage bytes, byte for byte
 __device__ __forceinline__ uint32_t run_values(uint32_t cov4, int threshold) {
     if (threshold == 0) return cov4;
-    uint32_t v = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v |= (uint32_t)((int)((cov4 >> (8 * k)) & 0xffu) >= threshold) << (8 * k);
-    return v;
+    const uint32_t s = cov_solid4(cov4, threshold);
+    return (s & 1u) | ((s & 2u) << 7) | ((s & 4u) << 14) | ((s & 8u) << 21);   // bit k into byte k
 }
 
 // One step of a row's walk: the pixels [x0, x0 + 256) of row R, four per lane.  v: the lane's four values;
 // returns the lane's four "starts a run" flags (bit k: pixel x0 + 4 lane + k).  carry: in, the value in front
 // of pixel x0 (not used for x0 == 0 of a layer's first row); out, the value of pixel x0 + 255.
-__device__ __forceinline__ uint32_t run_step(const RunGrid& g, const uint8_t* __restrict__ row, int py, int x0, int lane,
+__device__ __forceinline__ uint32_t run_step(const LayerGrid& g, const uint8_t* __restrict__ row, int py, int x0, int lane,
                                              uint32_t& carry, uint32_t& v) {
     const int px = x0 + 4 * lane;
-    uint32_t cov4 = 0;
-    if ((uint32_t)px < g.pitch) cov4 = *reinterpret_cast<const uint32_t*>(row + px);   // pitch % 16 == 0: px + 3 < pitch
-    v = run_values(cov4, g.threshold);
+    v = run_values(cov_load4(row + px, (uint32_t)px < g.pitch), g.threshold);   // pitch % 16 == 0: px + 3 < pitch
     const uint32_t up = (uint32_t)__shfl_up((int)v, 1, 64) >> 24;
     const uint32_t before = (v << 8) | (lane ? up : carry);
     const uint32_t diff = v ^ before;
@@ -58,13 +53,13 @@ __device__ __forceinline__ uint32_t run_step(const RunGrid& g, const uint8_t* __
 }
 
 // the value in front of a row's first pixel: pixel W - 1 of the row above, a pitched address (py > 0)
-__device__ __forceinline__ uint32_t run_row_carry(const RunGrid& g, const uint8_t* __restrict__ row, int py) {
+__device__ __forceinline__ uint32_t run_row_carry(const LayerGrid& g, const uint8_t* __restrict__ row, int py) {
     if (py == 0) return 0u;
     const uint32_t c = row[(ptrdiff_t)(g.W - 1) - (ptrdiff_t)g.pitch];
     return g.threshold ? (uint32_t)((int)c >= g.threshold) : c;
 }
 
-__global__ __launch_bounds__(256) void k_run_count(RunGrid g, uint32_t rows, const uint8_t* __restrict__ img,
+__global__ __launch_bounds__(256) void k_run_count(LayerGrid g, uint32_t rows, const uint8_t* __restrict__ img,
                                                    uint32_t* __restrict__ counts) {
     const int lane = threadIdx.x & 63;
     const uint32_t R = blockIdx.x * 4u + (threadIdx.x >> 6);   // wave-uniform
@@ -80,7 +75,7 @@ __global__ __launch_bounds__(256) void k_run_count(RunGrid g, uint32_t rows, con
     if (lane == 0) counts[R] = cnt;
 }
 
-__global__ __launch_bounds__(256) void k_run_emit(RunGrid g, uint32_t rows, const uint8_t* __restrict__ img,
+__global__ __launch_bounds__(256) void k_run_emit(LayerGrid g, uint32_t rows, const uint8_t* __restrict__ img,
                                                   const uint32_t* __restrict__ offsets, uint32_t total,
                                                   uint32_t* __restrict__ start, uint8_t* __restrict__ value) {
     const int lane = threadIdx.x & 63;
@@ -92,14 +87,8 @@ __global__ __launch_bounds__(256) void k_run_emit(RunGrid g, uint32_t rows, cons
     uint32_t base = offsets[R];   // the row's offset, then the row's running count on top of it
     for (int x0 = 0; x0 < g.W; x0 += 256) {
         const uint32_t starts = run_step(g, row, py, x0, lane, carry, v);
-        uint32_t below = 0, step = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const u64 m = __ballot((starts >> k) & 1u);
-            below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, below));
-            step += (uint32_t)__popcll(m);
-        }
-        uint32_t at = base + below;
+        uint32_t step;
+        uint32_t at = base + ranks_below(starts, step);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             if ((starts >> k) & 1u) {
@@ -114,30 +103,20 @@ __global__ __launch_bounds__(256) void k_run_emit(RunGrid g, uint32_t rows, cons
     }
 }
 
-void check(const RunGrid& g, uint32_t n_layers) {
-    if (g.W < 1 || g.H < 1 || g.pitch < (uint32_t)g.W || g.pitch % 16u != 0u || g.threshold < 0 || g.threshold > 16 ||
-        n_layers < 1u || (uint64_t)n_layers * (uint64_t)g.H * (uint64_t)g.W > kRunMaxPixels)
-        throw std::runtime_error("runs: chunk out of range");
+void check(const LayerGrid& g, uint32_t n_layers) {
+    check_layer_chunk(g, n_layers, "runs");
+    if (g.threshold < 0 || g.threshold > 16) throw std::runtime_error("runs: chunk out of range");   // 0: the value is the coverage byte
 }
 
 }  // namespace
 
-RunGrid run_grid(int W, int H, uint32_t pitch, int threshold) {
-    RunGrid g;
-    g.W = W;
-    g.H = H;
-    g.pitch = pitch;
-    g.threshold = threshold;
-    return g;
-}
-
-void launch_run_count(RunGrid g, uint32_t n_layers, const uint8_t* d_img, uint32_t* d_counts, hipStream_t s) {
+void launch_run_count(LayerGrid g, uint32_t n_layers, const uint8_t* d_img, uint32_t* d_counts, hipStream_t s) {
     check(g, n_layers);
     const uint32_t rows = n_layers * (uint32_t)g.H;   // <= 2^28
     k_run_count<<<(rows + 3u) / 4u, 256, 0, s>>>(g, rows, d_img, d_counts);
 }
 
-void launch_run_emit(RunGrid g, uint32_t n_layers, const uint8_t* d_img, const uint32_t* d_offsets, uint32_t total,
+void launch_run_emit(LayerGrid g, uint32_t n_layers, const uint8_t* d_img, const uint32_t* d_offsets, uint32_t total,
                      uint32_t* d_start, uint8_t* d_value, hipStream_t s) {
     check(g, n_layers);
     if (total == 0u) return;

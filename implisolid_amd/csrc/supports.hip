@@ -32,21 +32,14 @@
 #include <stdexcept>
 
 #include "kernels.hpp"
+#include "layer_device.hpp"
 
 namespace impli {
 
 namespace {
 
-typedef unsigned long long u64;
-constexpr uint32_t kGroups = 256;          // four-pixel groups per block: one per lane
 constexpr uint32_t kNoCell = 0xFFFFFFFFu;  // a lane that takes no part in the wave's runs
 constexpr int kAhead = 4;                  // image layers in flight in the foot walk and the top pass
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d, 64);
-    return v;
-}
 
 __device__ __forceinline__ u64 tip_key(int dist, uint32_t p) { return ((u64)(uint32_t)dist << 32) | (u64)(0xFFFFFFFFu - p); }
 
@@ -58,23 +51,20 @@ __global__ __launch_bounds__(256) void k_support_cells(SupportGrid g, uint32_t b
     const int t = threadIdx.x, lane = t & 63;
     const uint32_t ll = blockIdx.x / blocks_per_layer, b = blockIdx.x % blocks_per_layer;
     if (ll == 0u && l0 == 0) return;   // the call's first layer rests on the plate: block-uniform
-    const uint32_t W = (uint32_t)g.W, gpr = (W + 3u) / 4u;       // groups per row
-    const uint32_t gi = b * kGroups + (uint32_t)t;
-    const bool active = gi < gpr * (uint32_t)g.H;                // <= 2^26
-    const uint32_t y = active ? gi / gpr : 0u, x4 = active ? (gi % gpr) * 4u : 0u;
-    const uint32_t nv = active ? (W - x4 < 4u ? W - x4 : 4u) : 0u;   // the group's pixels inside the row
-    const size_t px = (size_t)W * (size_t)g.H, at = (size_t)y * W + x4;
+    const PixelGroup pg = pixel_group(g.W, g.H, b, t);
+    const bool active = pg.active;
+    const uint32_t W = (uint32_t)g.W, y = pg.y, x4 = pg.x4, nv = pg.nv;
+    const size_t px = (size_t)W * (size_t)g.H, at = pg.at;
     const int32_t* mine = dist + (size_t)ll * px + at;
     const int32_t* below = ll ? mine - px : carry + at;
 
     int dm[4] = {}, db[4] = {};
     if (kVec) {
         if (active) {
-            const int4 a = *reinterpret_cast<const int4*>(mine), c = *reinterpret_cast<const int4*>(below);
-            dm[0] = a.x, dm[1] = a.y, dm[2] = a.z, dm[3] = a.w;
-            db[0] = c.x, db[1] = c.y, db[2] = c.z, db[3] = c.w;
+            load4<true>(mine, 4u, dm);
+            load4<true>(below, 4u, db);
         }
-    } else {
+    } else {   // pixel by pixel, both layers of a pixel together: the shared load goes layer by layer
 #pragma unroll
         for (uint32_t i = 0; i < 4; ++i)
             if (i < nv) {
@@ -137,8 +127,7 @@ __global__ __launch_bounds__(256) void k_support_cells(SupportGrid g, uint32_t b
 #pragma unroll
         for (int d = 1; d <= 32; d <<= 1) {
             const uint32_t oc = (uint32_t)__shfl_up((int)cnt, d, 64);
-            const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)key, d, 64), hi = (uint32_t)__shfl_up((int)(uint32_t)(key >> 32), d, 64);
-            const u64 ok = ((u64)hi << 32) | lo;
+            const u64 ok = shfl_up64(key, d);
             if (lane - d >= start) {
                 cnt += oc;
                 key = ok > key ? ok : key;
@@ -151,11 +140,10 @@ __global__ __launch_bounds__(256) void k_support_cells(SupportGrid g, uint32_t b
         }
     }
 
-    const uint32_t n_un = wave_sum((uint32_t)__popc(un));
-    if (lane == 0) s_cnt[t >> 6] = n_un;
+    wave_put(s_cnt, wave_sum((uint32_t)__popc(un)));
     __syncthreads();
     if (t == 0) {
-        const uint32_t total = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        const uint32_t total = block_sum(s_cnt);
         if (total) atomicAdd(unsupported + (size_t)((uint32_t)l0 + ll), (u64)total);
     }
 }
@@ -199,34 +187,25 @@ __global__ __launch_bounds__(256) void k_support_emit(SupportGrid g, uint32_t n,
 template <bool kVec>
 __global__ __launch_bounds__(256) void k_support_top(SupportGrid g, uint32_t n_layers, int l0, const uint8_t* __restrict__ img,
                                                      int32_t* __restrict__ top) {
-    const uint32_t W = (uint32_t)g.W, gpr = (W + 3u) / 4u;
-    const uint32_t gi = blockIdx.x * kGroups + threadIdx.x;
-    if (gi >= gpr * (uint32_t)g.H) return;
-    const uint32_t y = gi / gpr, x4 = (gi % gpr) * 4u;
-    const uint32_t nv = W - x4 < 4u ? W - x4 : 4u;
-    int32_t* tp = top + (size_t)y * W + x4;
+    const PixelGroup pg = pixel_group(g.W, g.H, blockIdx.x, (int)threadIdx.x);
+    if (!pg.active) return;
+    const uint32_t nv = pg.nv;
+    int32_t* tp = top + pg.at;
     int v[4] = {-1, -1, -1, -1};
-    if (l0 > 0) {
-        if (kVec) {
-            const int4 a = *reinterpret_cast<const int4*>(tp);
-            v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w;
-        } else {
-#pragma unroll
-            for (uint32_t i = 0; i < 4; ++i)
-                if (i < nv) v[i] = tp[i];
-        }
-    }
+    if (l0 > 0) load4<kVec>(tp, nv, v);
     const size_t layer_img = (size_t)g.H * g.pitch;
-    const uint8_t* q = img + (size_t)y * g.pitch + x4;   // x4 + 4 <= pitch: the padding columns are zero, never solid
+    const uint8_t* q = img + (size_t)pg.y * g.pitch + pg.x4;   // x4 + 4 <= pitch: the padding columns are zero, never solid
     for (uint32_t m0 = 0; m0 < n_layers; m0 += kAhead) {
         uint32_t w[kAhead];
 #pragma unroll
-        for (uint32_t u = 0; u < kAhead; ++u) w[u] = m0 + u < n_layers ? *reinterpret_cast<const uint32_t*>(q + (size_t)(m0 + u) * layer_img) : 0u;
+        for (uint32_t u = 0; u < kAhead; ++u) w[u] = cov_load4(q + (size_t)(m0 + u) * layer_img, m0 + u < n_layers);
 #pragma unroll
-        for (uint32_t u = 0; u < kAhead; ++u)
+        for (uint32_t u = 0; u < kAhead; ++u) {
+            const uint32_t solid = cov_solid4(w[u], g.threshold);
 #pragma unroll
             for (uint32_t i = 0; i < 4; ++i)
-                if ((int)((w[u] >> (8u * i)) & 0xffu) >= g.threshold) v[i] = l0 + (int)(m0 + u);
+                if ((solid >> i) & 1u) v[i] = l0 + (int)(m0 + u);
+        }
     }
     if (kVec) {
         *reinterpret_cast<int4*>(tp) = make_int4(v[0], v[1], v[2], v[3]);
@@ -238,30 +217,16 @@ __global__ __launch_bounds__(256) void k_support_top(SupportGrid g, uint32_t n_l
 }
 
 void check(const SupportGrid& g, uint32_t n_layers) {
-    if (g.W < 1 || g.H < 1 || g.W > kRasterMaxSide || g.H > kRasterMaxSide || g.pitch < (uint32_t)g.W || (g.pitch & 15u) || g.threshold < 1 ||
-        g.cell < 1 || g.cell > kSupportMaxCell || g.ncx != ((uint32_t)g.W + (uint32_t)g.cell - 1u) / (uint32_t)g.cell ||
-        g.ncy != ((uint32_t)g.H + (uint32_t)g.cell - 1u) / (uint32_t)g.cell || n_layers < 1u ||
-        (uint64_t)n_layers * (uint64_t)g.H * (uint64_t)g.W > kDistMaxPixels)
+    check_layer_chunk(g, n_layers, "supports");
+    if (g.threshold < 1 || g.cell < 1 || g.cell > kSupportMaxCell || g.ncx != ((uint32_t)g.W + (uint32_t)g.cell - 1u) / (uint32_t)g.cell ||
+        g.ncy != ((uint32_t)g.H + (uint32_t)g.cell - 1u) / (uint32_t)g.cell)
         throw std::runtime_error("supports: chunk out of range");
-}
-
-uint32_t groups_blocks(const SupportGrid& g) {
-    const uint32_t gpr = ((uint32_t)g.W + 3u) / 4u;
-    return (gpr * (uint32_t)g.H + kGroups - 1u) / kGroups;   // <= 2^18
 }
 
 }  // namespace
 
-SupportGrid support_grid(int W, int H, uint32_t pitch, int threshold, int cell) {
-    SupportGrid g;
-    g.W = W;
-    g.H = H;
-    g.pitch = pitch;
-    g.threshold = threshold;
-    g.cell = cell;
-    g.ncx = cell >= 1 ? (uint32_t)((W + cell - 1) / cell) : 0u;
-    g.ncy = cell >= 1 ? (uint32_t)((H + cell - 1) / cell) : 0u;
-    return g;
+SupportGrid support_grid(const LayerGrid& g, int cell) {
+    return {g, cell, cell >= 1 ? (uint32_t)((g.W + cell - 1) / cell) : 0u, cell >= 1 ? (uint32_t)((g.H + cell - 1) / cell) : 0u};
 }
 
 void launch_support_cells(SupportGrid g, uint32_t n_layers, int l0, int64_t reach2, const int32_t* d_dist, const int32_t* d_carry,

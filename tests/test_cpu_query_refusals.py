@@ -2,7 +2,7 @@
 spans, mass, their host-only companions and the two interval probes): the return value and the exact
 implisolid_last_error() text of every request that is refused before anything reaches a device, and
 that the library answers the next call.  The literals in EXPECTED were recorded from the library before
-the queries moved to csrc/abi_queries.hip, and those of the layer and ray entries before these came to
+the queries moved to csrc/abi_queries.hip (the layer queries since to csrc/abi_layers.hip), and those of the layer and ray entries before these came to
 share their request checks (LayerRequest, ray_request): they pin that neither changed an error path, nor
 which of two faults at once is reported.  No GPU."""
 import ctypes
