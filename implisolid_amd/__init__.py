@@ -62,6 +62,7 @@ ABI_SYMBOLS = [
     "implisolid_layer_supports", "implisolid_layer_supports_copy", "implisolid_debug_layer_supports_ms",
     "implisolid_layer_runs", "implisolid_layer_runs_copy", "implisolid_debug_layer_runs_ms",
     "implisolid_layer_bodies", "implisolid_layer_bodies_copy", "implisolid_debug_layer_bodies_ms",
+    "implisolid_layer_cups", "implisolid_layer_cups_copy", "implisolid_debug_layer_cups_ms",
     "implisolid_raycast", "implisolid_ray_params", "implisolid_debug_raycast_ms",
     "implisolid_ray_spans", "implisolid_ray_spans_copy", "implisolid_debug_ray_spans_ms",
 ]
@@ -244,6 +245,11 @@ def lib():
                                      ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)], ctypes.c_int64),
         "implisolid_layer_bodies_copy": ([ctypes.POINTER(ctypes.c_int64), ip], c_int),
         "implisolid_debug_layer_bodies_ms": ([c_int, ctypes.POINTER(ctypes.c_double)], c_int),
+        "implisolid_layer_cups": ([c_char_p, c_int, fp, c_int, c_int, c_int, fp, c_int, c_int, c_int, c_int,
+                                   ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)],
+                                  ctypes.c_int64),
+        "implisolid_layer_cups_copy": ([ctypes.POINTER(ctypes.c_int64), ip], c_int),
+        "implisolid_debug_layer_cups_ms": ([c_int, ctypes.POINTER(ctypes.c_double)], c_int),
         "implisolid_raycast": ([c_char_p, c_int, fp, fp, ctypes.c_int64, ctypes.c_float, ctypes.c_float, c_int, c_int, ip, fp,
                                 fp, fp, ctypes.POINTER(ctypes.c_int64)], c_int),
         "implisolid_ray_params": ([ctypes.c_float, ctypes.c_float, c_int, fp], c_int),
@@ -767,7 +773,7 @@ def _rect4(rect, what):
 
 
 def _layer_args(what, rect, z, width, height, supersample):
-    """What raster_layers, layer_islands, layer_distance, layer_hollow, layer_supports, layer_runs and layer_bodies do with their arguments first: (rect, z, W, H, s)."""
+    """What raster_layers, layer_islands, layer_distance, layer_hollow, layer_supports, layer_runs, layer_bodies and layer_cups do with their arguments first: (rect, z, W, H, s)."""
     r = _rect4(rect, what)
     zz = np.ascontiguousarray(z, np.float32).reshape(-1)
     W, H, s = int(width), int(height), int(supersample)
@@ -1219,24 +1225,29 @@ def _body_rows(a, dtype, what):
     return np.ascontiguousarray(a.reshape(-1, len(dtype.names)), dtype[0]).view(dtype).reshape(-1)
 
 
-def bodies_decode(run_offsets, runs, width, height):
-    """Host only: the label stack of layer_bodies()'s row runs, int32 (L, height, width): the voxel's body index,
-    or -1 where the voxel is not of the target class."""
+def _runs_decode(run_offsets, runs, width, height, dtype, what):
+    """the label stack of row runs {start, length, label} (bodies_decode, cups_decode): the run's label on its voxels, -1 elsewhere"""
     W, H = int(width), int(height)
     offs = np.asarray(run_offsets, np.int64).reshape(-1)
-    rr = _body_rows(runs, BODY_RUN_DTYPE, "bodies_decode")
+    rr = _body_rows(runs, dtype, what)
     if offs.size < 2 or offs[0] != 0 or offs[-1] != rr.size or (np.diff(offs) < 0).any():
-        raise ValueError("bodies_decode: run_offsets must run from 0 to len(runs) without decreasing")
+        raise ValueError("%s: run_offsets must run from 0 to len(runs) without decreasing" % what)
     start, length = rr["start"].astype(np.int64), rr["length"].astype(np.int64)
     if (length < 1).any() or (start < 0).any() or (start % W + length > W).any() or (start // W >= H).any():
-        raise ValueError("bodies_decode: every run must lie inside one image row")
+        raise ValueError("%s: every run must lie inside one image row" % what)
     L = offs.size - 1
     first = start + np.repeat(np.arange(L, dtype=np.int64), np.diff(offs)) * (W * H)
     out = np.full(L * H * W, -1, np.int32)
     # every voxel of every run: its run's first key plus its position in the run
     at = np.repeat(first - np.concatenate(([0], np.cumsum(length)[:-1])), length) + np.arange(int(length.sum()), dtype=np.int64)
-    out[at] = np.repeat(rr["body"], length)
+    out[at] = np.repeat(rr[dtype.names[2]], length)
     return out.reshape(L, H, W)
+
+
+def bodies_decode(run_offsets, runs, width, height):
+    """Host only: the label stack of layer_bodies()'s row runs, int32 (L, height, width): the voxel's body index,
+    or -1 where the voxel is not of the target class."""
+    return _runs_decode(run_offsets, runs, width, height, BODY_RUN_DTYPE, "bodies_decode")
 
 
 def enclosed_voids(bodies, width, height, n_layers):
@@ -1258,6 +1269,67 @@ def layer_bodies_kernel_ms(enable=True):
     """Diagnostics: switch the event timing of layer_bodies()'s kernels on or off; returns the last timed call's
     (raster passes, row-run count + scan + emit, link, finish) ms, -1 before any."""
     return _pass_ms("layer_bodies", 4, enable)
+
+
+CUP_DTYPE = np.dtype([(name, np.int64) for name in ("seed", "area", "x0", "y0", "x1", "y1", "pocket")])
+CUP_RUN_DTYPE = np.dtype([(name, np.int32) for name in ("start", "length", "cup")])
+
+
+def layer_cups(shape, rect, width, height, z, supersample=1, threshold=1, connectivity=6, ignore_root_matrix=False, want_runs=False,
+               return_stats=False):
+    """The suction cups of the layer stack z = z[l] on the GPU (include/implisolid.h implisolid_layer_cups): per layer
+    l the empty voxels (coverage < threshold) of layer l whose pocket -- their connected class among the empty voxels
+    of layers 0 .. l, 6- or 26-connected -- reaches no pixel of the image frame.  The order of z is the print order;
+    the plate below layer 0 and the film above layer l are closed.  The images are raster_layers'.  Returns
+    (cup_offsets int64 (L + 1,): layer l's cups are [cup_offsets[l], cup_offsets[l + 1]); cups, a structured array
+    (CUP_DTYPE) of {seed = the smallest py * W + px of the cup in its layer, area, x0, y0, x1, y1 = the inclusive box,
+    pocket = the smallest key l' * W * H + py * W + px of the whole pocket}, layer by layer in increasing seed), then
+    with want_runs run_offsets int64 (L + 1,) and runs, a structured array (CUP_RUN_DTYPE) of {start = py * W + x0,
+    length, cup = the index of its cup's record} per cupped row run, and with return_stats [raster_layers' five
+    figures, the empty row runs of the stack, cups, cupped voxels]."""
+    fp, lp = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64)
+    r, zz, W, H, s = _layer_args("layer_cups", rect, z, width, height, supersample)
+    offs = np.zeros(zz.size + 1, np.int64)
+    roffs = np.zeros(zz.size + 1, np.int64)
+    stats = (ctypes.c_int64 * 8)()
+    C = lib().implisolid_layer_cups(_s(shape), int(bool(ignore_root_matrix)), r.ctypes.data_as(fp), W, H, s, zz.ctypes.data_as(fp),
+                                    int(zz.size), int(threshold), int(connectivity), int(bool(want_runs)), offs.ctypes.data_as(lp),
+                                    roffs.ctypes.data_as(lp), stats)
+    if C < 0:
+        raise ImplisolidError(last_error())
+    cups = np.empty(C, CUP_DTYPE)
+    runs = np.empty(int(roffs[-1]), CUP_RUN_DTYPE) if want_runs else None
+    if lib().implisolid_layer_cups_copy(cups.ctypes.data_as(lp),
+                                        runs.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if want_runs else None) != 0:
+        raise ImplisolidError(last_error())
+    out = (offs, cups)
+    if want_runs:
+        out += (roffs, runs)
+    if return_stats:
+        out += ([int(v) for v in stats],)
+    return out
+
+
+def cups_decode(run_offsets, runs, width, height):
+    """Host only: the label stack of layer_cups()'s cupped row runs, int32 (L, height, width): the index of the
+    voxel's cup, or -1 where the voxel lies in no cup."""
+    return _runs_decode(run_offsets, runs, width, height, CUP_RUN_DTYPE, "cups_decode")
+
+
+def cup_areas(cup_offsets, cups):
+    """Host only: the sealed area of every layer, int64 (L,): the areas of layer_cups()'s records added up per layer."""
+    offs = np.asarray(cup_offsets, np.int64).reshape(-1)
+    c = _body_rows(cups, CUP_DTYPE, "cup_areas")
+    if offs.size < 2 or offs[0] != 0 or offs[-1] != c.size or (np.diff(offs) < 0).any():
+        raise ValueError("cup_areas: cup_offsets must run from 0 to len(cups) without decreasing")
+    total = np.concatenate(([0], np.cumsum(c["area"].astype(np.int64))))
+    return total[offs[1:]] - total[offs[:-1]]
+
+
+def layer_cups_kernel_ms(enable=True):
+    """Diagnostics: switch the event timing of layer_cups()'s kernels on or off; returns the last timed call's
+    (raster passes, row-run count + scan + emit + frame, the layers' link + mark + head, finish) ms, -1 before any."""
+    return _pass_ms("layer_cups", 4, enable)
 
 
 def ray_params(t0, t1, steps):

@@ -1,7 +1,7 @@
 // abi_layers.hip -- the layer queries of the C ABI: layer images and their islands, distance fields, hollowed
-// shells, support tips, run-length streams and bodies.  The seven share their entry (layer_entry), their request
+// shells, support tips, run-length streams, bodies and suction cups.  The eight share their entry (layer_entry), their request
 // (LayerRequest) and the passes that make a chunk's image (LayerImages): each reads as what it does with the
-// image.  The scaffolding is abi_common.hpp's: islands, supports, runs and bodies place their records with
+// image.  The scaffolding is abi_common.hpp's: islands, supports, runs, bodies and cups place their records with
 // CountedOutput and keep them in a ResultSlot; raster, supports and runs bring theirs down through StagingSlots;
 // islands, distance and supports hand a CarriedLayer from chunk to chunk; the timed queries keep their figures
 // in a PassTimer.
@@ -17,7 +17,7 @@
 using namespace impli;
 using namespace impli::cabi;
 
-// ---- what the layer queries share: the request and the image (raster, islands, layer distance, hollow, supports, runs, bodies) ------
+// ---- what the layer queries share: the request and the image (raster, islands, layer distance, hollow, supports, runs, bodies, cups) ------
 namespace {
 // The request of implisolid_<entry>, refused in this order: n_layers, z, width / height, supersample, threshold
 // (an entry without one passes 1, which every supersample admits).  The entry's own checks follow, then
@@ -1065,6 +1065,165 @@ int implisolid_layer_bodies_copy(int64_t* bodies, int32_t* runs) {
 
 int implisolid_debug_layer_bodies_ms(int enable, double ms[4]) {
     return g_body_timer.entry(enable, ms);
+}
+
+}  // extern "C"
+
+// ---- suction cups of the layer stack (implisolid_layer_cups) ---------------------------------------------------
+// Per chunk, behind LayerImages' head, bodies.hip's count, the scan, a read-back of the chunk's per-layer run
+// offsets, bodies.hip's emit with the runs numbered from 1 (run 0 is the outside), cups.hip's frame; then for
+// every layer of the chunk bodies.hip's link of that one layer and cups.hip's mark and head, enqueued back to
+// back: the host knows every layer's runs from the read-back and waits for none of them.  The stack-wide arrays
+// grow with the chunks as the bodies' do.  Behind the last chunk the finish passes: the heads and the cupped runs
+// per row, their scans (per-layer offsets: cup_offsets and run_offsets), the records, the tally; then the
+// records, and the cupped runs when asked for, come down into the result slot.  Scratch of its own: 14 the counted
+// output over a chunk's rows, 0 the runs, 1 the union-find, 2 the rows' offsets, 3 the counted output of the heads
+// over the stack's rows, 4 rootat, 5 cup, 6 first (the heads' ordinals in the finish), 7 the counted output of the
+// cupped runs, 8 the records with the run records behind them.
+namespace {
+struct CupSlot : ResultSlot {    // the last call's records, and its cupped runs when it asked for them
+    PinnedVec<int64_t> cups;
+    PinnedVec<int32_t> runs;
+    int64_t n_runs = -1;         // < 0: the call did not ask for runs
+};
+CupSlot g_cups;
+PassTimer<4> g_cup_timer;        // implisolid_debug_layer_cups_ms: HIP events around the launches
+
+int64_t cup_layers(const QueryShape& q, const LayerRequest& r, int threshold, int connectivity, bool want_runs, int64_t* cup_offsets,
+                   int64_t* run_offsets, int64_t stats[8]) {
+    Engine& E = *q.E;
+    hipStream_t s = q.s;
+    const int H = r.H, n_layers = r.n_layers;
+    LayerImages im(q, r, "cups", "IMPLISOLID_CUPS_CHUNK", kBodyMaxChunk, true, g_cup_timer.on);
+    const BodyGrid bg{im.grid(threshold), 0, connectivity};
+    const size_t rows = (size_t)n_layers * (size_t)H;   // <= 2^30
+    // every reserve before any pointer is taken; the runs' arrays grow in the loop and are addressed through their DevBuf
+    CountedOutput placed(E.scratch(14), (size_t)im.chunk_layers * (size_t)H, (uint32_t)H);   // a row's runs, a layer's offset
+    CountedOutput heads(E.scratch(3), rows, (uint32_t)H);                                    // a row's heads, a layer's offset
+    CountedOutput kept(E.scratch(7), rows, (uint32_t)H);                                     // a row's cupped runs, a layer's offset
+    E.scratch(2).reserve((rows + 1) * sizeof(uint32_t));
+    DevBuf& b_runs = E.scratch(0);
+    DevBuf& b_parent = E.scratch(1);
+    DevBuf& b_rootat = E.scratch(4);
+    DevBuf& b_cup = E.scratch(5);
+    DevBuf& b_first = E.scratch(6);
+    uint32_t* d_rowoff = E.scratch(2).as<uint32_t>();
+    static_assert(sizeof(RasterState) + sizeof(BodyState) + sizeof(CupState) <= kStateBytes, "the three states share the state block");
+    BodyState* d_bstate = reinterpret_cast<BodyState*>(im.d_state + 1);
+    CupState* d_cstate = reinterpret_cast<CupState*>(d_bstate + 1);
+    IMPLI_HIP(hipMemsetAsync(d_bstate, 0, sizeof(BodyState) + sizeof(CupState), s));
+    g_cups.cups.resize(0);
+    g_cups.runs.resize(0);
+    Timed<4, 4> tm(g_cup_timer);   // behind im.ev[3], the end of the raster passes: count + scan + emit + frame, the layers' loop; around the finish
+    std::vector<int64_t> at((size_t)n_layers + 1);   // layer l's empty row runs are [at[l], at[l + 1]), run 1 + k of the arrays being run k
+    int64_t total = 0;
+    while (im.next()) {
+        const int l0 = im.l0;
+        const uint32_t nl = im.nl;
+        launch_body_count(bg, nl, im.d_img, placed.d_counts, d_bstate, s);
+        const char* limit = "implisolid_layer_cups: the stack reaches 2^31 row runs";
+        const uint32_t cc = placed.place(nl, s, total, limit, at.data() + l0);
+        if (total + (int64_t)cc + 1 >= ((int64_t)1 << 31)) throw InputError(limit);   // run 0 takes an index too
+        // entries 0 .. total + cc, and one to spare; entry 0 is the outside, so the first chunk has nothing to keep
+        const size_t have = total ? (size_t)total + 1 : 0, want = (size_t)total + cc + 2;
+        grow_keeping(b_runs, have * 2 * sizeof(int32_t), want * 2 * sizeof(int32_t), s);
+        for (DevBuf* b : {&b_parent, &b_rootat, &b_cup, &b_first}) grow_keeping(*b, have * sizeof(int32_t), want * sizeof(int32_t), s);
+        if (!total) IMPLI_HIP(hipMemsetAsync(b_parent.p, 0, sizeof(int32_t), s));   // parent[0] = 0
+        IMPLI_HIP(hipMemsetAsync(b_first.as<uint32_t>() + total + 1, 0, (size_t)cc * sizeof(uint32_t), s));
+        launch_body_emit(bg, nl, l0, im.d_img, placed.d_offsets, (uint32_t)total + 1u, cc, b_runs.as<int32_t>(), b_parent.as<int32_t>(),
+                         d_rowoff, s);
+        launch_cup_frame(bg, nl, l0, b_runs.as<int32_t>(), d_rowoff, b_parent.as<int32_t>(), s);
+        tm.mark(0, s);
+        for (uint32_t k = 0; k < nl; ++k) {   // nothing here waits for the device
+            const uint32_t lo = 1u + (uint32_t)at[(size_t)l0 + k], hi = 1u + (uint32_t)(k + 1u < nl ? at[(size_t)l0 + k + 1] : total + cc);
+            if (lo == hi) continue;   // a layer without an empty voxel
+            launch_body_link(bg, 1, l0 + (int)k, b_runs.as<int32_t>(), d_rowoff, b_parent.as<int32_t>(), s);
+            launch_cup_mark(lo, hi, b_parent.as<int32_t>(), b_rootat.as<int32_t>(), b_first.as<uint32_t>(), s);
+            launch_cup_head(lo, hi, b_rootat.as<int32_t>(), b_first.as<uint32_t>(), b_cup.as<int32_t>(), s);
+        }
+        tm.mark(1, s);
+        IMPLI_HIP(hipGetLastError());
+        total += cc;
+        if (tm) {   // only a timed call synchronises here
+            IMPLI_HIP(hipStreamSynchronize(s));
+            tm.add(0, im.raster_ms());
+            tm.add(1, im.ev[3], tm.ev[0]);
+            tm.add(2, tm.ev[0], tm.ev[1]);
+        }
+    }
+    at[(size_t)n_layers] = total;
+    // the finish: the heads in run order are the cups in (layer, seed) order
+    tm.mark(2, s);
+    launch_cup_rows(bg, (uint32_t)rows, b_runs.as<int32_t>(), d_rowoff, b_cup.as<int32_t>(), heads.d_counts, kept.d_counts, d_cstate, s);
+    const uint32_t C = heads.place((uint32_t)n_layers, s, 0, "implisolid_layer_cups: the stack reaches 2^31 cups", cup_offsets);
+    cup_offsets[n_layers] = C;
+    std::vector<int64_t> own(run_offsets ? 0 : (size_t)n_layers + 1);
+    int64_t* ro = run_offsets ? run_offsets : own.data();
+    const uint32_t K = kept.place((uint32_t)n_layers, s, 0, "implisolid_layer_cups: the stack reaches 2^31 row runs", ro);
+    ro[n_layers] = K;
+    if ((int64_t)C > (int64_t)K || (int64_t)K > total) throw HipError("cups: more cups than cupped runs, or more of those than runs");
+    const size_t rec_bytes = (size_t)(C + 1u) * 7 * sizeof(int64_t);
+    E.scratch(8).reserve(rec_bytes + (want_runs ? (size_t)(K + 1u) * 3 * sizeof(int32_t) : 0));
+    long long* d_rec = E.scratch(8).as<long long>();
+    int32_t* d_out = want_runs ? reinterpret_cast<int32_t*>(E.scratch(8).as<char>() + rec_bytes) : nullptr;
+    launch_cup_heads(bg, (uint32_t)rows, b_runs.as<int32_t>(), d_rowoff, b_cup.as<int32_t>(), b_rootat.as<int32_t>(), heads.d_offsets, C,
+                     b_first.as<uint32_t>(), d_rec, s);
+    launch_cup_tally(bg, (uint32_t)rows, (uint32_t)total + 1u, b_runs.as<int32_t>(), d_rowoff, b_cup.as<int32_t>(), b_first.as<uint32_t>(), C,
+                     d_rec, kept.d_offsets, K, d_out, s);
+    tm.mark(3, s);
+    IMPLI_HIP(hipGetLastError());
+    g_cups.cups.resize((size_t)C * 7);
+    if (C) IMPLI_HIP(hipMemcpyAsync(g_cups.cups.data(), d_rec, (size_t)C * 7 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    if (want_runs) {
+        g_cups.runs.resize((size_t)K * 3);
+        if (K) IMPLI_HIP(hipMemcpyAsync(g_cups.runs.data(), d_out, (size_t)K * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    }
+    CupState hc{};
+    IMPLI_HIP(hipMemcpyAsync(&hc, d_cstate, sizeof hc, hipMemcpyDeviceToHost, s));
+    IMPLI_HIP(hipStreamSynchronize(s));
+    if (tm) tm.add(3, tm.ev[2], tm.ev[3]);
+    int64_t area = 0;
+    for (uint32_t c = 0; c < C; ++c) area += g_cups.cups.data()[7 * (size_t)c + 1];
+    if (area != (int64_t)hc.cupped) throw HipError("cups: the records' areas and the cupped voxels disagree");
+    g_cups.n_runs = want_runs ? (int64_t)K : -1;
+    if (stats) {
+        im.stats(stats);
+        stats[5] = total;
+        stats[6] = (int64_t)C;
+        stats[7] = (int64_t)hc.cupped;
+    }
+    return (int64_t)C;
+}
+}  // namespace
+
+extern "C" {
+
+int64_t implisolid_layer_cups(const char* shape_json, int ignore_root_matrix, const float rect[4], int width, int height,
+                              int supersample, const float* z, int n_layers, int threshold, int connectivity, int want_runs,
+                              int64_t* cup_offsets, int64_t* run_offsets, int64_t stats[8]) {
+    g_cups.reset();
+    g_cups.n_runs = -1;
+    return layer_entry(
+        "layer_cups", cup_offsets && (run_offsets || want_runs == 0), shape_json, ignore_root_matrix, rect, width, height, supersample, z,
+        n_layers, threshold,
+        [&] {
+            if (connectivity != 6 && connectivity != 26) throw InputError("implisolid_layer_cups: connectivity must be 6 or 26");
+            if (want_runs != 0 && want_runs != 1) throw InputError("implisolid_layer_cups: want_runs must be 0 or 1");
+        },
+        [&](const QueryShape& q, const LayerRequest& r) {
+            return g_cups.publish(cup_layers(q, r, threshold, connectivity, want_runs != 0, cup_offsets, run_offsets, stats));
+        });
+}
+
+int implisolid_layer_cups_copy(int64_t* cups, int32_t* runs) {
+    if (g_cups.refuses_copy("layer_cups", "cups", (g_cups.n == 0 || cups) && (g_cups.n_runs <= 0 || runs))) return -1;
+    if (g_cups.n > 0) std::memcpy(cups, g_cups.cups.data(), (size_t)g_cups.n * 7 * sizeof(int64_t));
+    if (g_cups.n_runs > 0) std::memcpy(runs, g_cups.runs.data(), (size_t)g_cups.n_runs * 3 * sizeof(int32_t));
+    return 0;
+}
+
+int implisolid_debug_layer_cups_ms(int enable, double ms[4]) {
+    return g_cup_timer.entry(enable, ms);
 }
 
 }  // extern "C"

@@ -229,15 +229,6 @@ __global__ __launch_bounds__(256) void k_body_roots(BodyGrid g, uint32_t rows, c
     }
 }
 
-// min and max onto a record's field.  Both only ever move one way, so a field that already holds a value at
-// least as small (as large) stays as it is whatever lands later, and the atomic is left out: a body's extent
-// settles after a few runs, and the thousands that follow would queue up on its record for nothing.
-__device__ __forceinline__ void rec_min(long long* p, long long v) {
-    if (__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > v) __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void rec_max(long long* p, long long v) {
-    if (__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < v) __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 // voxels and an extent onto a record; l0 is the seed's layer and was stored with the record
 __device__ __forceinline__ void rec_add(long long* r, long long len, int x0, int x1, int y0, int y1, int l1) {
     __hip_atomic_fetch_add(r + 1, len, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

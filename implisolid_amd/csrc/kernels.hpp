@@ -362,6 +362,41 @@ void launch_body_roots(BodyGrid g, uint32_t rows, const int32_t* d_runs, const u
 void launch_body_tally(BodyGrid g, uint32_t rows, const int32_t* d_runs, const uint32_t* d_rowoff, int32_t* d_parent,
                        const uint32_t* d_ord, uint32_t n_bodies, long long* d_rec, int32_t* d_out, hipStream_t s);
 
+// Suction cups of the layer stack (implisolid_layer_cups; DESIGN "Suction cups of the layer stack", cups.hip): per
+// layer l the empty voxels of layer l whose pocket of the prefix 0 .. l (the bodies of the empty class of layers
+// 0 .. l) holds no voxel of the image frame.  The runs, their union-find and the rows' offsets are the bodies'
+// with target 0, except that the caller numbers the stack's runs from 1 (launch_body_emit's base is 1 + the runs
+// of the chunks before) and keeps d_parent[0] = 0: run 0 is the outside.  Stack-wide beside them, one entry a run:
+// d_rootat int32, d_cup int32, d_first uint32 (zeroed; the finish keeps the heads' ordinals there).  Per chunk the
+// launches go on s in the order body count, scan, body emit, frame; then per layer body link of that layer, mark,
+// head, with no host synchronisation between layers.  Behind the last chunk: rows over the stack's rows, the scans
+// of its two counts (launch_slice_layer_offsets with tpl = H gives cup_offsets and run_offsets), heads, tally.
+struct CupState {        // zeroed before the first chunk
+    unsigned long long cupped;    // the voxels of the cupped runs, counted by launch_cup_rows
+};
+// frame: parent = 0 for every run of the chunk that holds a frame voxel; behind emit, before any link of the chunk
+void launch_cup_frame(BodyGrid g, uint32_t n_layers, int l0, const int32_t* d_runs, const uint32_t* d_rowoff, int32_t* d_parent,
+                      hipStream_t s);
+// mark: over one layer's runs [lo, hi), all linked: d_rootat[run] = its root, and the layer's smallest run of
+// every closed root onto d_first[root] (as lo + hi - 1 - run, by maximum)
+void launch_cup_mark(uint32_t lo, uint32_t hi, int32_t* d_parent, int32_t* d_rootat, uint32_t* d_first, hipStream_t s);
+// head: d_cup[run] = the smallest run of the layer with the same closed root, or -1 where the root is 0
+void launch_cup_head(uint32_t lo, uint32_t hi, const int32_t* d_rootat, const uint32_t* d_first, int32_t* d_cup, hipStream_t s);
+// rows: per image row of the stack its heads (d_cup[run] == run) and its cupped runs (d_cup[run] >= 0); their
+// voxels onto d_state->cupped
+void launch_cup_rows(BodyGrid g, uint32_t rows, const int32_t* d_runs, const uint32_t* d_rowoff, const int32_t* d_cup,
+                     uint32_t* d_head_counts, uint32_t* d_run_counts, CupState* d_state, hipStream_t s);
+// heads: d_ord[head run] = its ordinal, and the records {seed, 0, MAX, MAX, -1, -1, pocket} in (layer, seed) order;
+// d_offsets: the exclusive scan of d_head_counts, total: its last entry (nothing is written at or past it)
+void launch_cup_heads(BodyGrid g, uint32_t rows, const int32_t* d_runs, const uint32_t* d_rowoff, const int32_t* d_cup,
+                      const int32_t* d_rootat, const uint32_t* d_offsets, uint32_t total, uint32_t* d_ord, long long* d_rec,
+                      hipStream_t s);
+// tally: every cupped run's length and extent added to its cup's record; end: 1 + the stack's runs; d_out
+// (nullable): {start, length, cup} per cupped run at d_offsets, the exclusive scan of d_run_counts, n_out: its last entry
+void launch_cup_tally(BodyGrid g, uint32_t rows, uint32_t end, const int32_t* d_runs, const uint32_t* d_rowoff, const int32_t* d_cup,
+                      const uint32_t* d_ord, uint32_t n_cups, long long* d_rec, const uint32_t* d_offsets, uint32_t n_out,
+                      int32_t* d_out, hipStream_t s);
+
 // Rays against the solid (implisolid_raycast; DESIGN "Rays against the solid", raycast.hip): per ray the
 // first solid sample of the table d_ts (host.hpp ray_params, N + 1 floats), the bisection inside its
 // bracket and the normal there.  One chunk = n rays (3 n floats of origins and directions each); both

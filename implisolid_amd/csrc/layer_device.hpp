@@ -1,6 +1,7 @@
 // layer_device.hpp -- what the kernels of the layer passes share (islands.hip, distance.hip, hollow.hip,
-// supports.hip, runs.hip, bodies.hip): sums, maxima and ranks over a wave of 64 lanes, a block's sum of its four
-// waves' values, the four neighbouring pixels a lane takes, and the solid bits of a dword of coverage bytes.
+// supports.hip, runs.hip, bodies.hip, cups.hip): sums, maxima and ranks over a wave of 64 lanes, a block's sum of its
+// four waves' values, the four neighbouring pixels a lane takes, the solid bits of a dword of coverage bytes, and
+// the one-way minimum and maximum onto a record's field.
 // Device-only, and no part of the JIT's headers.  Internal linkage: every file that includes this has its own
 // copies, inlined into its kernels.
 #pragma once
@@ -116,6 +117,17 @@ __device__ __forceinline__ uint32_t cov_solid4(uint32_t cov4, int threshold) {
 #pragma unroll
     for (uint32_t i = 0; i < 4; ++i) s |= (uint32_t)cov_solid(cov4, i, threshold) << i;
     return s;
+}
+
+// ---- records that waves add to ----------------------------------------------------------------------------------
+// min and max onto a record's field.  Both only ever move one way, so a field that already holds a value at
+// least as small (as large) stays as it is whatever lands later, and the atomic is left out: a body's extent
+// settles after a few runs, and the thousands that follow would queue up on its record for nothing.
+__device__ __forceinline__ void rec_min(long long* p, long long v) {
+    if (__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > v) __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void rec_max(long long* p, long long v) {
+    if (__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < v) __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 }  // namespace

@@ -703,6 +703,62 @@ int implisolid_layer_bodies_copy(int64_t* bodies, int32_t* runs);
  * milliseconds summed over its chunks, -1 before any.  Returns 0 */
 int implisolid_debug_layer_bodies_ms(int enable, double ms[4]);
 
+/* Additive: the suction cups of the layer stack on the GPU -- per layer the empty regions that seal against the
+ * film when that layer is cured, because their pocket has no way out through the part as printed so far (no
+ * reference counterpart).  Arguments, limits, refusals and their order are implisolid_layer_bodies' without
+ * target: shape_json, ignore_root_matrix, rect, width, height in [1, 16384], supersample s in {1, 2, 4}, z,
+ * n_layers, threshold in [1, s^2]; further
+ *   connectivity  6 or 26, of the empty voxels; anything else is refused.  6 is the dual of 26 for the solid
+ *   want_runs     0 or 1; anything else is refused
+ * cov[l][py][px] is exactly implisolid_raster's.  A voxel (l, py, px) is empty iff cov[l][py][px] < threshold; l
+ * is the position in the caller's z list, and that order is the print order.  Two empty voxels are adjacent as
+ * implisolid_layer_bodies' target voxels are.  The prefix P_l is layers 0 .. l.  A frame voxel has px in {0, W -
+ * 1} or py in {0, H - 1}.  The plate below layer 0 and the film above layer l are closed: neither is outside (a
+ * caller whose model does not start on the plate puts an empty plane first).  A pocket of P_l is a class of the
+ * transitive closure of adjacency among the empty voxels of P_l, paths inside P_l only; it is open if it holds a
+ * frame voxel and closed otherwise.  A cup of layer l is the set of the layer-l voxels of one closed pocket of P_l
+ * that has a voxel in layer l: one record per cup, even where the cup is several separate regions of the layer
+ * that join further down.  Seven int64 {seed, area, x0, y0, x1, y1, pocket}:
+ *   seed              the smallest py * W + px of the cup's voxels (all in layer l)
+ *   area              their count
+ *   x0, y0, x1, y1    their inclusive bounding box
+ *   pocket            the smallest key l' * W * H + py * W + px of the whole pocket in P_l: pocket / (W * H) is the
+ *                     layer where the pocket begins, and the value stays the same from layer to layer until the
+ *                     pocket merges with one that has a smaller key
+ * layer by layer, in increasing seed within a layer.  With want_runs the row runs of empty voxels (maximal within
+ * one image row) that lie in a cup are kept, three int32 {start = py * W + x0, length, cup}, cup being the index
+ * of the run's record in the whole array; a run lies in one pocket, so it is cupped whole or not at all.  The runs
+ * come layer by layer, within a layer in increasing start.
+ *   cup_offsets  n_layers + 1 entries, required, always filled: layer l's cups are [cup_offsets[l],
+ *                cup_offsets[l + 1])
+ *   run_offsets  n_layers + 1 entries, may be NULL iff want_runs == 0; filled when given: layer l's cupped runs
+ *                are [run_offsets[l], run_offsets[l + 1])
+ *   stats        (may be NULL) implisolid_raster's five figures, then the empty row runs of the stack, the cups and
+ *                the cupped voxels (the sum of area)
+ *   returns      the number of cups, or -1 with implisolid_last_error(): implisolid_raster's refusals, a bad
+ *                threshold, connectivity or want_runs, or a needed pointer NULL -- all refused before anything is
+ *                compiled or reaches a device --, or at run time a stack that reaches 2^31 row runs or 2^31 cups
+ * The records, and the runs when asked for, stay in one library-owned host slot until the next
+ * implisolid_layer_cups call; a failed call empties the slot.  implisolid_layer_cups_copy copies them out (cups: 7
+ * int64 per cup; runs: 3 int32 per cupped run, may be NULL when the call did not ask for runs): 0, or -1 when
+ * there is nothing to copy or a needed pointer is NULL.
+ * Everything is an integer: no result depends on the pruning level, the chunking, the order in which atomics
+ * land or the launch geometry; before returning the library checks that the areas add up to the cupped voxels
+ * counted on the device.  The volume of a pocket is left out on purpose.  One union-find over the empty row runs
+ * of the whole stack answers every prefix: joins only add up as layers arrive, and the pockets are read off
+ * behind each layer's joins.  Stack-wide device memory is 24 bytes per empty row run, 20 per image row, 56 per cup
+ * and 12 per cupped run with want_runs; the only per-pixel memory is a chunk's image.  Layers are processed in
+ * chunks of whole layers of at most IMPLISOLID_CUPS_CHUNK (layer, 16 x 16 tile) pairs (environment, read at each
+ * call; default and maximum 2^20, at least one layer's tiles).  One device, the interpreter kernels. */
+int64_t implisolid_layer_cups(const char* shape_json, int ignore_root_matrix, const float rect[4], int width, int height,
+                              int supersample, const float* z, int n_layers, int threshold, int connectivity, int want_runs,
+                              int64_t* cup_offsets, int64_t* run_offsets, int64_t stats[8]);
+int implisolid_layer_cups_copy(int64_t* cups, int32_t* runs);
+/* diagnostics: with enable != 0 the following implisolid_layer_cups calls time their kernels with HIP events;
+ * ms (may be NULL) = the last timed call's {raster passes, row-run count + scan + emit + frame, the layers' link +
+ * mark + head, finish} milliseconds summed over its chunks, -1 before any.  Returns 0 */
+int implisolid_debug_layer_cups_ms(int enable, double ms[4]);
+
 /* Additive: rays cast at the solid on the GPU -- per ray the first hit, its distance, the field value
  * and the normal there (no reference counterpart: the reference front end ray-casts the mesh).
  *   origins, dirs  3 n floats each, n in [0, 2^24], every float finite.  A direction need not have unit
